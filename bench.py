@@ -26,6 +26,16 @@ objects: ``roofline`` (dominant kernel vs the HBM roofline, live HIP-event
 timing) and ``cpu_baseline`` (the oracle's C restatement of the reference's
 numba-cpu operator timed on this box's host cores; rank 0, N = 1 only).
 
+A plain run does only what the headline needs: set-up, W warm-up steps, the K
+timed steps, the outputs (``--dump-outputs DIR``) and the line.  ``--full``
+adds everything else, after the timed steps: the isolated-launch and copy-
+ceiling figures of ``roofline``, ``cpu_baseline``, the result check against the
+oracle (``check``), the auxiliary lines of N = 1 (``aux``) and, at N > 1, the
+transport comparison and the harvest.
+
+    python bench.py --gpus 1 --steps K --warmup W --dump-outputs DIR
+    python bench.py --gpus 1 --steps K --warmup W --full
+
 The code lives in ``benchlib/`` (modes, transports, roofline, CPU legs); this file is the entry the driver runs and hashes:
 argument parsing, process / device bring-up, dispatch.
 """
@@ -73,13 +83,13 @@ def main():
                          "libfusgpu.so (default); native = grouped ncclSend/ncclRecv issued by libfusgpu.so; torch = "
                          "torch.distributed all_to_all_single.  A transport that does not come up on every rank or "
                          "fails the run's halo check is replaced by the next one (peer -> native -> torch)")
-    ap.add_argument("--halo-compare", dest="halo_compare", action="store_true", default=True,
-                    help="N > 1 (default since round 6: the driver's fixed command carries no extra flags): after the timed region, time the apply over "
+    ap.add_argument("--halo-compare", dest="halo_compare", action="store_true", default=None,
+                    help="N > 1 (on by default with --full): after the timed region, time the apply over "
                          "EVERY transport that comes up (peer, peer-fenced, native = RCCL) in alternating rounds in this one process and put each one's "
                          "exposed cost in config.halo_compare")
     ap.add_argument("--no-halo-compare", dest="halo_compare", action="store_false")
     ap.add_argument("--no-harvest", action="store_true",
-                    help="default mode at N > 1: skip the secondary lines (partitioned mass apply, fused RK4 steps, Westervelt P = 6 step) that follow "
+                    help="default mode at N > 1 with --full: skip the secondary lines (partitioned mass apply, fused RK4 steps, Westervelt P = 6 step) that follow "
                          "the headline's timed region on the same partition and communicator (roofline.secondary)")
     ap.add_argument("--single-gather", action="store_true",
                     help="--mode westervelt: the single-gather cell pass (uniform c4 / c3: the vector pass writes w = u_n + kappa v_n) instead of the default two-gather pass")
@@ -92,10 +102,19 @@ def main():
                     help="--mode mass: the batch plan carries exclusive-dof marks (plain load + store instead of an atomic for dofs "
                          "one batch touches alone; opt-in, measured slower from P = 4 up: profiles/r04d_ab_mass_exclusive_marks.log)")
     ap.add_argument("--no-check", action="store_true",
-                    help="skip the comparison of the timed run's y with the oracle's K x (stiffness / mass modes; done by default, the "
+                    help="skip the comparison of the timed run's y with the oracle's K x (stiffness / mass modes; done with --full, the "
                          "run exits non-zero when it fails)")
-    ap.add_argument("--no-aux", action="store_true", help="default mode at N = 1: skip the mass and RK4-step lines of 'aux'")
+    ap.add_argument("--no-aux", action="store_true", help="default mode at N = 1 with --full: skip the mass and RK4-step lines of 'aux'")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also measure and check what the headline does not need: isolated launches, copy ceiling, "
+                         "CPU baselines, the result check against the oracle, the auxiliary lines (N = 1), the transport comparison and the "
+                         "harvest (N > 1).  Off by default: a plain run sets up, warms up, times --steps steps and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the timed path computed (the arrays its caller receives after the last step) "
+                         "as DIR/<name>.npy (float32 / float64, at most 48 MiB in all: a fixed, seeded sample of a larger array)")
     args = ap.parse_args()
+    if args.halo_compare is None:
+        args.halo_compare = args.full
 
     if args.gpus < 1:
         raise SystemExit("--gpus must be >= 1")
@@ -164,6 +183,8 @@ def main():
             raise SystemExit("--mode scatter is the N = 1 self-neighbour line (at N > 1 the exchange is inside every other mode's step)")
         from benchlib.transports import measure_scatter
 
+        if args.dump_outputs:
+            raise SystemExit("--dump-outputs: --mode scatter times exchanges of a scratch buffer and has no outputs to write")
         sc = measure_scatter(device, np.float64 if args.dtype == "f64" else np.float32, reps=max(1, args.steps), P=args.degree, cells=args.cells)
         first = next((v for v in sc["transports"].values() if "scatter_forward" in v), None)
         emit({"metric": "scatter_forward_reverse_us", "value": None if first is None else first["scatter_forward"]["us_per_call_stream"], "unit": "us",

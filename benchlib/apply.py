@@ -2,7 +2,8 @@
 y += K x (or M x) over the whole (partitioned) mesh -- forward halo of x, the kernel over all local cells, reverse halo of y.
 Set-up (mesh, tables, geometry factors on the device, batch plans, at N > 1 the choice of the halo transport by the run's own
 halo check), the timed region, the roofline figures, the CPU leg, the result check, and then either the auxiliary lines of the
-N = 1 default run (aux_lines.py) or the N > 1 harvest (harvest.py)."""
+N = 1 default run (aux_lines.py) or the N > 1 harvest (harvest.py).  Everything after the timed region except the outputs
+(``--dump-outputs``) and the line itself runs with ``--full`` only."""
 import os
 import time
 import types
@@ -10,7 +11,7 @@ import types
 import numpy as np
 
 from .aux_lines import aux_lines, failed_aux_checks
-from .common import HBM_PEAK_GBS, coll_device, emit, host_cores, kernel_src_sha, lib_built_from_tree, lib_sha, log, rehearsal
+from .common import DUMP_BUDGET_BYTES, HBM_PEAK_GBS, coll_device, dump_outputs, emit, host_cores, kernel_src_sha, lib_built_from_tree, lib_sha, log, rehearsal
 from .cpu_legs import compare_with_oracle, cpu_baseline, cpu_baseline_mass, oracle_apply
 from .harvest import harvest, owned_dofs_check
 from .roofline import geom_bytes_per_cell, load_traffic, mass_bytes_per_cell, secondary_summary, stiffness_bytes_per_cell
@@ -217,25 +218,31 @@ def run_apply(args, rank, world, device, use_dist, lib, ops, boxmesh, gll, pre):
     ms_per_step = elapsed / args.steps * 1e3
     region_ms = r0.elapsed_time(r1) / args.steps
     # what the timed region left in y: K accumulated applies (y was zeroed right before it) -- kept for result_check below
-    y_region = y_d.clone() if (not use_dist and not args.no_check) else None
+    y_region = y_d.clone() if (args.full and not use_dist and not args.no_check) else None
     if halo is not None:
         # a device-side wait that gave up inside the timed region means an exchange did not deliver: no line then
         late = torch.tensor([float(halo.health())], dtype=torch.float64, device=coll_device(device))
         dist.all_reduce(late)
         if float(late.item()) != 0.0:
             raise SystemExit(f"rank {rank}: {int(late.item())} device-side halo wait(s) timed out during the timed region: the run is invalid")
+    if args.dump_outputs:
+        # what the caller of the timed path holds after its last step: y (zeroed before the region, K accumulated applies), owned dofs
+        dump_outputs(args.dump_outputs, {"y" if world == 1 else f"y_rank{rank}": y_d[:mesh.nlocal].cpu().numpy()},
+                     budget=DUMP_BUDGET_BYTES // world)
 
     # isolated launches (outside the timed region): one event pair per step, as the reference's
     # protocol times one apply at a time (cuda/time_operators.py:272-282); agrees with the per-dispatch
     # durations of rocprofv3 --kernel-trace
-    ev0 = [torch.cuda.Event(enable_timing=True) for _ in range(args.steps)]
-    ev1 = [torch.cuda.Event(enable_timing=True) for _ in range(args.steps)]
-    for i in range(args.steps):
-        ev0[i].record()
-        step()
-        ev1[i].record()
-    torch.cuda.synchronize()
-    ev_ms = np.array([a.elapsed_time(b) for a, b in zip(ev0, ev1)])
+    ev_ms = None
+    if args.full:
+        ev0 = [torch.cuda.Event(enable_timing=True) for _ in range(args.steps)]
+        ev1 = [torch.cuda.Event(enable_timing=True) for _ in range(args.steps)]
+        for i in range(args.steps):
+            ev0[i].record()
+            step()
+            ev1[i].record()
+        torch.cuda.synchronize()
+        ev_ms = np.array([a.elapsed_time(b) for a, b in zip(ev0, ev1)])
 
     def timed_launches(fn, reps=10):
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
@@ -247,8 +254,8 @@ def run_apply(args, rank, world, device, use_dist, lib, ops, boxmesh, gll, pre):
         torch.cuda.synchronize()
         return e0.elapsed_time(e1) / reps
 
-    sched_ms = None
-    if halo is not None:
+    sched_ms = kern_ms = None
+    if halo is not None and (args.full or args.halo_compare):  # the transport comparison is priced against the one-launch kernel time
         # kernel time at N > 1 (after, outside the timed region): ONE launch over all local cells -- the kernel the
         # N = 1 line times, and what the halo overhead is measured against -- and the apply's own launch schedule
         # (sub-ranges, streams, events) with no exchange in it: what cutting the launch costs by itself
@@ -256,41 +263,42 @@ def run_apply(args, rank, world, device, use_dist, lib, ops, boxmesh, gll, pre):
             op.prepare(dm_d)
         kern_ms = timed_launches(lambda: op(x_d, cc_d, y_d, G_d, dm_d))
         sched_ms = timed_launches(lambda: halo.apply_no_exchange(x_d, cc_d, y_d, G_d, dm_d))
-    else:
+    elif halo is None:
         kern_ms = region_ms  # N = 1: the step IS the stiffness kernel launch
 
     # measured streaming ceiling of THIS device (outside the timed region): copy of 1 GiB -> 1 GiB
     # with the library's copy kernel (working set far beyond the 256 MiB Infinity Cache)
     copy_gbs = read_gbs = None
-    try:
-        nel = (1 << 30) // 8
-        src = torch.empty(nel, dtype=torch.float64, device=device).fill_(1.0)
-        dst = torch.empty_like(src)
-        ops.copy(src, dst)
-        c0, c1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        c0.record()
-        for _ in range(5):
+    if args.full:
+        try:
+            nel = (1 << 30) // 8
+            src = torch.empty(nel, dtype=torch.float64, device=device).fill_(1.0)
+            dst = torch.empty_like(src)
             ops.copy(src, dst)
-        c1.record()
-        torch.cuda.synchronize()
-        copy_gbs = 2 * nel * 8 * 5 / (c0.elapsed_time(c1) * 1e-3) / 1e9
-        # read-only stream (the stiffness kernel is ~90 % reads): torch's reduction over 1 GiB
-        src.sum()
-        c0.record()
-        for _ in range(5):
+            c0, c1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            c0.record()
+            for _ in range(5):
+                ops.copy(src, dst)
+            c1.record()
+            torch.cuda.synchronize()
+            copy_gbs = 2 * nel * 8 * 5 / (c0.elapsed_time(c1) * 1e-3) / 1e9
+            # read-only stream (the stiffness kernel is ~90 % reads): torch's reduction over 1 GiB
             src.sum()
-        c1.record()
-        torch.cuda.synchronize()
-        read_gbs = nel * 8 * 5 / (c0.elapsed_time(c1) * 1e-3) / 1e9
-        del src, dst
-    except Exception as e:  # never let the side measurement break the bench line
-        log(f"copy ceiling measurement failed: {e!r}")
+            c0.record()
+            for _ in range(5):
+                src.sum()
+            c1.record()
+            torch.cuda.synchronize()
+            read_gbs = nel * 8 * 5 / (c0.elapsed_time(c1) * 1e-3) / 1e9
+            del src, dst
+        except Exception as e:  # never let the side measurement break the bench line
+            log(f"copy ceiling measurement failed: {e!r}")
 
     ndofs_global = mesh.ndofs_global
     value = ndofs_global / (elapsed / args.steps)
     bpc = geom_bytes_per_cell(P, T) if geom else (mass_bytes_per_cell(P, T) if mass else stiffness_bytes_per_cell(P, T))
     alg_bytes = 3 * T * mesh.ndofs if mass_diag else mesh.ncells * bpc  # cached diagonal: w, x read, y read-modify-write
-    achieved = alg_bytes / (kern_ms * 1e-3) / 1e9
+    achieved = None if kern_ms is None else alg_bytes / (kern_ms * 1e-3) / 1e9
     sha = lib_sha()
     traffic, traffic_source = (None, "not profiled for this mode") if (geom or mass) else load_traffic(P, mesh.ncells, sha, args.dtype)
     if geom:
@@ -338,11 +346,11 @@ def run_apply(args, rank, world, device, use_dist, lib, ops, boxmesh, gll, pre):
             "first_contact": first_contact,
             "halo_compare": halo_compare,
             # the step against ONE launch over all local cells (the kernel of the N = 1 line) ...
-            "halo_exposed_ms": None if halo is None else ms_per_step - kern_ms,
-            "halo_exposed_frac": None if halo is None else (ms_per_step - kern_ms) / kern_ms,
+            "halo_exposed_ms": None if (halo is None or kern_ms is None) else ms_per_step - kern_ms,
+            "halo_exposed_frac": None if (halo is None or kern_ms is None) else (ms_per_step - kern_ms) / kern_ms,
             # ... of which: cutting that launch into the schedule's sub-launches (no exchange), and the exchanges
-            "halo_split_cost_ms": None if halo is None else sched_ms - kern_ms,
-            "halo_exchange_exposed_ms": None if halo is None else ms_per_step - sched_ms,
+            "halo_split_cost_ms": None if sched_ms is None else sched_ms - kern_ms,
+            "halo_exchange_exposed_ms": None if sched_ms is None else ms_per_step - sched_ms,
             "schedule_launches_ms": sched_ms,
             "ranks": world,
             "lib_sha": sha,
@@ -355,23 +363,25 @@ def run_apply(args, rank, world, device, use_dist, lib, ops, boxmesh, gll, pre):
             "achieved": achieved,
             "peak": HBM_PEAK_GBS,
             "unit": "GB/s",
-            "frac": achieved / HBM_PEAK_GBS,
+            "frac": None if achieved is None else achieved / HBM_PEAK_GBS,
             "traffic": traffic,
             "traffic_source": traffic_source,
             "kernel": kname,
             "kernel_ms": kern_ms,
             "kernel_ms_how": ("one HIP-event pair around the K back-to-back launches of the timed region / K" if halo is None
-                              else "event pair around 10 back-to-back launches over ALL local cells (one launch each, no exchange), after the timed region"),
-            "isolated_launch_ms_mean": float(ev_ms.mean()),  # one event pair per launch, outside the timed region
-            "isolated_launch_ms_min": float(ev_ms.min()),
-            "isolated_launch_ms_std": float(ev_ms.std()),
-            "isolated_frac": None if halo is not None else alg_bytes / (float(ev_ms.mean()) * 1e-3) / 1e9 / HBM_PEAK_GBS,
+                              else "event pair around 10 back-to-back launches over ALL local cells (one launch each, no exchange), after the timed region"
+                              if kern_ms is not None else "not measured (N > 1: --full)"),
+            # one event pair per launch, outside the timed region (--full)
+            "isolated_launch_ms_mean": None if ev_ms is None else float(ev_ms.mean()),
+            "isolated_launch_ms_min": None if ev_ms is None else float(ev_ms.min()),
+            "isolated_launch_ms_std": None if ev_ms is None else float(ev_ms.std()),
+            "isolated_frac": None if (halo is not None or ev_ms is None) else alg_bytes / (float(ev_ms.mean()) * 1e-3) / 1e9 / HBM_PEAK_GBS,
             "algorithmic_bytes_per_cell": None if mass_diag else bpc,
             "algorithmic_bytes_per_launch": alg_bytes,
             "bytes_contract": ("cached diagonal: y += (M(c) 1) (.) x, 3 vector touches per dof; NOT the reference's gather-scale-scatter contract "
                                "(that is --mode mass)") if mass_diag else None,
             "cells_per_launch": mesh.ncells,
-            "pct_of_hbm_roofline_dofs": 100.0 * achieved / HBM_PEAK_GBS,
+            "pct_of_hbm_roofline_dofs": None if achieved is None else 100.0 * achieved / HBM_PEAK_GBS,
             "measured_copy_gbs": copy_gbs,   # 1 GiB -> 1 GiB with fus_copy (read + write bytes)
             "measured_read_gbs": read_gbs,   # 1 GiB read-only reduction (torch.sum)
         },
@@ -380,7 +390,7 @@ def run_apply(args, rank, world, device, use_dist, lib, ops, boxmesh, gll, pre):
         out.update(valid=False, rehearsal="ranks share the visible GPU(s) (bootstrap over gloo): NOT a measurement")
     out["cpu_baseline"] = None
     pb = None
-    if rank == 0 and world == 1 and not use_dist:
+    if args.full and rank == 0 and world == 1 and not use_dist:
         if not args.no_cpu_baseline and mass:
             try:
                 out["cpu_baseline"] = cpu_baseline_mass(P, mesh, x.astype(np.float64), cc.astype(np.float64), G_d.cpu().numpy().astype(np.float64))
@@ -397,7 +407,7 @@ def run_apply(args, rank, world, device, use_dist, lib, ops, boxmesh, gll, pre):
     # ---- result check bound to the timed run (the reference keeps cuda/test_operators.py:213-312 next to cuda/time_operators.py:204-290
     # on the same operators): what the timed region left in y, against the oracle's apply on the same inputs
     check = None
-    if not args.no_check:
+    if args.full and not args.no_check:
         try:
             x64, cc64, D64 = x.astype(np.float64), cc.astype(np.float64), D.astype(np.float64)
             if mass:
@@ -453,7 +463,7 @@ def run_apply(args, rank, world, device, use_dist, lib, ops, boxmesh, gll, pre):
     if pb is not None:
         pb.pop("G", None)  # 945 MB of host memory the auxiliary lines do not need
     bad_aux = []
-    if world == 1 and not use_dist and not (geom or mass) and not args.no_aux and not args.no_plan:
+    if args.full and world == 1 and not use_dist and not (geom or mass) and not args.no_aux and not args.no_plan:
         # SURVEY 8d asks for the mass apply next to the stiffness apply, north_star names the RK4 step: all after the timed region
         # and the check of the headline, same mesh, each with its own bytes contract and its own check (reference:
         # numba-cpu/time_operators.py:176-268 times the operators in one script)
@@ -467,7 +477,7 @@ def run_apply(args, rank, world, device, use_dist, lib, ops, boxmesh, gll, pre):
     # (a transport's bring-up on a platform it has never seen, a collective whose peer is gone) must not take the line with it: a timer emits what
     # the run has -- the headline with its check, and what the extras finished -- and leaves (every rank has its own; rank 0 prints)
     extras_timer, extras_phase = None, ["halo_compare"]
-    if use_dist and halo is not None:
+    if (args.full or args.halo_compare) and use_dist and halo is not None:
         import threading
 
         budget = float(os.environ.get("FUS_BENCH_EXTRAS_TIMEOUT_S", "420"))
@@ -517,7 +527,7 @@ def run_apply(args, rank, world, device, use_dist, lib, ops, boxmesh, gll, pre):
         out["config"]["halo_compare"] = halo_compare
     extras_phase[0] = "harvest"
     harvested = None
-    if use_dist and halo is not None and not (geom or mass) and not args.no_harvest and not args.no_plan:
+    if args.full and use_dist and halo is not None and not (geom or mass) and not args.no_harvest and not args.no_plan:
         # N > 1, the driver's fixed command (no extra flags): the other lines of the path on the SAME partition and communicator, after
         # the headline's timed region -- partitioned mass apply, fused RK4 steps, Westervelt P = 6 step (BASELINE config 5)
         harvested = out["harvest"] = {}

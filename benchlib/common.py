@@ -113,13 +113,61 @@ def lib_built_from_tree():
 
 
 def _free_port():
+    """A free TCP port for the rendezvous, taken from BELOW the kernel's ephemeral range: a port the kernel hands out
+    (bind to port 0) is free only until the next outgoing connection takes it, and the ranks that retry connecting to
+    it while rank 0 is still starting are such connections (a retry that draws the port itself connects to itself,
+    and rank 0 then fails with EADDRINUSE)."""
+    import random
     import socket
 
-    s = socket.socket()
-    s.bind(("127.0.0.1", 0))
-    p = s.getsockname()[1]
-    s.close()
-    return p
+    try:
+        with open("/proc/sys/net/ipv4/ip_local_port_range") as f:
+            low = int(f.read().split()[0])
+    except (OSError, ValueError, IndexError):
+        low = 32768
+    hi = max(1025, low)
+    lo = max(1024, min(10000, hi - 1000))
+    rng = random.Random()  # seeded from the OS: concurrent launchers draw different ports
+    for _ in range(200):
+        p = rng.randrange(lo, hi)
+        with socket.socket() as s:
+            try:
+                s.bind(("127.0.0.1", p))
+            except OSError:
+                continue
+        return p
+    with socket.socket() as s:  # nothing free below the ephemeral range: the kernel's choice
+        s.bind(("127.0.0.1", 0))
+        return s.getsockname()[1]
+
+
+DUMP_BUDGET_BYTES = 48 << 20  # --dump-outputs writes at most this much in all (the contract allows 64 MB)
+
+
+def dump_outputs(directory, arrays, budget=DUMP_BUDGET_BYTES, seed=20240601):
+    """``--dump-outputs DIR``: write each array of ``arrays`` (name -> host array) as ``DIR/<name>.npy`` in float32 /
+    float64.  Together they stay within ``budget`` bytes: an array that does not fit its share keeps a fixed sample of
+    its entries -- the same sorted indices for the same length and seed, so two builds run with the same arguments are
+    compared entry for entry.  Returns {name: what was written}."""
+    import numpy as np
+
+    os.makedirs(directory, exist_ok=True)
+    arrays = {k: np.ascontiguousarray(v).reshape(-1) for k, v in arrays.items()}
+    share = budget // max(1, len(arrays))
+    written = {}
+    for name, a in arrays.items():
+        if a.dtype not in (np.float32, np.float64):
+            a = a.astype(np.float64)
+        keep = share // a.itemsize
+        if a.size > keep:
+            idx = np.sort(np.random.default_rng(seed).choice(a.size, size=keep, replace=False))
+            a = a[idx]
+            written[name] = f"{keep} of {arrays[name].size} entries (sorted indices drawn with numpy default_rng({seed}))"
+        else:
+            written[name] = f"all {a.size} entries"
+        np.save(os.path.join(directory, name + ".npy"), a)
+    log(f"outputs written to {directory}: {written}")
+    return written
 
 
 def rehearsal():

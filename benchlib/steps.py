@@ -7,15 +7,17 @@ import time
 
 import numpy as np
 
-from .common import HBM_PEAK_GBS, coll_device, emit, host_cores, lib_built_from_tree, lib_sha, log, rehearsal
+from .common import DUMP_BUDGET_BYTES, HBM_PEAK_GBS, coll_device, dump_outputs, emit, host_cores, lib_built_from_tree, lib_sha, log, rehearsal
 from .roofline import aux_traffic, rk4_step_bytes, rk4_step_traffic
 from .cpu_legs import compare_with_oracle, cpu_baseline_rk4, oracle_step_field
 from .transports import first_comm
 
 
-def measure_rk4(args, rank, world, device, mode, perturbed, in_kernel_geometry, steps, warmup, comm=None, cpu_leg=False, single_gather=False, check=True):
+def measure_rk4(args, rank, world, device, mode, perturbed, in_kernel_geometry, steps, warmup, comm=None, cpu_leg=False, single_gather=False, check=True,
+                extras=True, dump=None):
     """Full RK4 steps of the linear (BASELINE config 3: demo_linear_box, P = 4, ~10 M dofs per GPU) or Westervelt
-    (config 5 shape) solver, fused stage kernels; returns the bench line as a dict."""
+    (config 5 shape) solver, fused stage kernels; returns the bench line as a dict.  ``extras``: at N > 1, the same steps
+    once more without the exchange (``local_step_ms``); ``dump``: directory the fields after the timed steps are written to."""
     import torch
     import torch.distributed as dist
 
@@ -111,13 +113,17 @@ def measure_rk4(args, rank, world, device, mode, perturbed, in_kernel_geometry, 
         if float(late.item()) != 0.0:
             raise SystemExit(f"rank {rank}: {int(late.item())} device-side halo wait(s) timed out: the run is invalid")
     dev_ms = e0.elapsed_time(e1) / steps  # device time of the region on the launch stream
+    if dump:  # the solver's fields after its last timed step (owned dofs), what a caller of rk4() reads
+        sfx = "" if world == 1 else f"_rank{rank}"
+        dump_outputs(dump, {"u" + sfx: solver.u[: mesh.nlocal].cpu().numpy(), "v" + sfx: solver.v[: mesh.nlocal].cpu().numpy()},
+                     budget=DUMP_BUDGET_BYTES // world)
     ranks_ms = local_ms = None
     if world > 1:
         every = [torch.zeros(1, dtype=torch.float64, device=coll_device(device)) for _ in range(world)]
         dist.all_gather(every, torch.tensor([dev_ms], dtype=torch.float64, device=coll_device(device)))
         per = [float(t.item()) for t in every]
         ranks_ms = {"min": min(per), "max": max(per), "per_rank": per, "what": "HIP-event time of the K steps on each rank's launch stream / K"}
-        if getattr(solver, "halo", None) is not None:
+        if extras and getattr(solver, "halo", None) is not None:
             # the same steps with the exchange switched off: ONE launch over all local cells per stage, no scatter -- the
             # N = 1 step on this rank's cells (the field is not a solution any more; it is not looked at again)
             h, solver.halo = solver.halo, None
@@ -199,7 +205,8 @@ def measure_rk4(args, rank, world, device, mode, perturbed, in_kernel_geometry, 
 
 
 def bench_rk4(args, rank, world, device):
-    """Auxiliary metric (not the headline): ``--mode rk4`` / ``--mode westervelt``."""
+    """Auxiliary metric (not the headline): ``--mode rk4`` / ``--mode westervelt``.  The CPU leg, the check against the oracle's time
+    loop and, at N > 1, the steps without the exchange run with ``--full``."""
     import torch.distributed as dist
 
     import fusgpu_loader
@@ -207,7 +214,8 @@ def bench_rk4(args, rank, world, device):
     scat = fusgpu_loader.submodule("scatterer")
     comm = first_comm(args, scat, world, device)[0] if world > 1 else None
     out = measure_rk4(args, rank, world, device, args.mode, args.perturbed, args.in_kernel_geometry, args.steps, args.warmup, comm,
-                      cpu_leg=not args.no_cpu_baseline, single_gather=args.single_gather, check=not args.no_check)
+                      cpu_leg=args.full and not args.no_cpu_baseline, single_gather=args.single_gather, check=args.full and not args.no_check,
+                      extras=args.full, dump=args.dump_outputs)
     if rank == 0:
         emit(out)
     if world > 1:

@@ -98,7 +98,37 @@ class FakeComm:
         return complete
 
 
+def sumfact_fixture():
+    """``--only sumfact``: the reference's C++ contract / transpose templates (cpp/common/sum_factorisation.hpp, built into
+    oracle/_ref/libref_sumfact.so by ``make -C oracle ref``) on seeded inputs -> ref_sumfact_primitives.npz, so that
+    tests/test_oracle_golden.py::test_primitives_vs_reference_cpp needs no reference checkout."""
+    import ctypes as C
+
+    lib = C.CDLL(os.path.join(ROOT, "oracle", "_ref", "libref_sumfact.so"))
+    vp = C.c_void_p
+    lib.ref_contract_f64.argtypes = [C.c_int, C.c_int, vp, vp, vp]
+    lib.ref_transpose_f64.argtypes = [C.c_int, C.c_int, vp, vp]
+    rng = np.random.default_rng(0)  # the draw order of the test
+    out = {}
+    for n in (3, 4, 5, 7):
+        A, B = rng.standard_normal(n * n), rng.standard_normal(n**3)
+        out[f"A_{n}"], out[f"B_{n}"] = A, B
+        for tr in (0, 1):
+            c = rng.standard_normal(n**3)
+            out[f"c_in_{n}_{tr}"] = c.copy()
+            assert lib.ref_contract_f64(n, tr, A.ctypes.data, B.ctypes.data, c.ctypes.data) == 0
+            out[f"ref_contract_{n}_{tr}"] = c
+        for which in (0, 1):
+            t = np.zeros(n**3)
+            assert lib.ref_transpose_f64(n, which, B.ctypes.data, t.ctypes.data) == 0
+            out[f"ref_transpose_{n}_{which}"] = t
+    np.savez_compressed(os.path.join(HERE, "ref_sumfact_primitives.npz"), **out)
+    print("wrote ref_sumfact_primitives")
+
+
 def main():
+    if "--only" in sys.argv and sys.argv[sys.argv.index("--only") + 1] == "sumfact":
+        return sumfact_fixture()
     _install_stubs()
     sys.path.insert(0, os.path.join(REF, "numba-cpu"))
     import operators as ref_ops  # noqa: E402  (reference)
@@ -116,7 +146,7 @@ def main():
         # numba-cpu/test_operators.py:274-279
         return 100 * np.sin(2 * np.pi * xyz[:, 0]) * np.cos(3 * np.pi * xyz[:, 1]) * np.sin(4 * np.pi * xyz[:, 2])
 
-    only = sys.argv[sys.argv.index("--only") + 1] if "--only" in sys.argv else "all"  # all | ops | scatter | plan | rk4 | rk4nl
+    only = sys.argv[sys.argv.index("--only") + 1] if "--only" in sys.argv else "all"  # all | ops | scatter | plan | rk4 | rk4nl | sumfact
     # --match SUBSTRING: (re)write only the ops / rk4nl fixtures whose tag contains it (round 6 added P = 5, P = 8 and the P = 3 two-rank
     # Westervelt case without touching the committed ones: ``--only ops --match ops_P5``, ``--only rk4nl --match P3``)
     match = sys.argv[sys.argv.index("--match") + 1] if "--match" in sys.argv else ""

@@ -85,7 +85,7 @@ def test_distributed_code_path_on_one_gpu(halo):
     """The N > 1 code path (HaloApply, three cell sub-ranges, halo begin/end, communicator bring-up) in a
     1-rank world on the GPU box, through bench.py itself."""
     r = subprocess.run([sys.executable, BENCH, "--gpus", "1", "--steps", "5", "--warmup", "2", "--cells", "16", "--no-cpu-baseline",
-                        "--halo", halo], env=_env(FUS_BENCH_FORCE_DIST="1"), capture_output=True, text=True, timeout=900)
+                        "--halo", halo, "--full"], env=_env(FUS_BENCH_FORCE_DIST="1"), capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, (r.stdout + r.stderr)[-3000:]
     out = _one_json_line(r.stdout)
     cfg = out["config"]
@@ -129,7 +129,7 @@ def test_transport_fallback_after_a_failed_halo_check():
     is brought up and checked: peer rejected -> native (RCCL) used; peer and native rejected -> torch; the line says
     what was tried.  (The rejection is injected: FUS_BENCH_TEST_REJECT.)"""
     for reject, used in (("peer", "ncclSend"), ("peer,native", "all_to_all_single")):
-        r = subprocess.run([sys.executable, BENCH, "--gpus", "1", "--steps", "3", "--warmup", "1", "--cells", "12", "--no-cpu-baseline"],
+        r = subprocess.run([sys.executable, BENCH, "--gpus", "1", "--steps", "3", "--warmup", "1", "--cells", "12", "--no-cpu-baseline", "--full"],
                            env=_env(FUS_BENCH_FORCE_DIST="1", FUS_BENCH_TEST_REJECT=reject), capture_output=True, text=True, timeout=900)
         assert r.returncode == 0, (r.stdout + r.stderr)[-3000:]
         cfg = _one_json_line(r.stdout)["config"]
@@ -142,7 +142,7 @@ def test_transport_fallback_after_a_failed_halo_check():
         assert all("rejected" in t["result"] for t in tried[:-1]) and tried[-1]["result"] == "ok"
     # the middle rung of the ladder: only the fence-free PEER protocol fails its check -> the SAME arenas and kernels
     # with a system-scope release before / acquire after every flag are brought up, checked and used; RCCL is never started
-    r = subprocess.run([sys.executable, BENCH, "--gpus", "1", "--steps", "3", "--warmup", "1", "--cells", "12", "--no-cpu-baseline"],
+    r = subprocess.run([sys.executable, BENCH, "--gpus", "1", "--steps", "3", "--warmup", "1", "--cells", "12", "--no-cpu-baseline", "--full"],
                        env=_env(FUS_BENCH_FORCE_DIST="1", FUS_BENCH_TEST_REJECT="=peer"), capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, (r.stdout + r.stderr)[-3000:]
     out = _one_json_line(r.stdout)
@@ -160,7 +160,7 @@ def test_transport_fallback_after_a_failed_halo_check():
 @pytest.mark.parametrize("dist_path", [False, True])
 def test_mass_mode_line(dist_path):
     """SURVEY 8d's second operator line (cell mass apply), alone and through the N > 1 code path."""
-    r = subprocess.run([sys.executable, BENCH, "--mode", "mass", "--steps", "5", "--warmup", "2", "--cells", "16"],
+    r = subprocess.run([sys.executable, BENCH, "--mode", "mass", "--steps", "5", "--warmup", "2", "--cells", "16", "--full"],
                        env=_env(FUS_BENCH_FORCE_DIST="1" if dist_path else "0"), capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, (r.stdout + r.stderr)[-3000:]
     out = _one_json_line(r.stdout)
@@ -178,7 +178,7 @@ def test_multi_rank_rehearsal_on_one_gpu(n, mode):
     PEER transport itself -- arenas mapped across the processes with HIP IPC handles, send / receive kernels
     (FUS_BENCH_REHEARSAL=1; the line is marked invalid: the ranks share one GPU).  Covers what the N = 1 forced-dist run cannot: real
     neighbours inside the timed loop, the max-over-ranks reduction, rank 0 printing for the whole job."""
-    cmd = [sys.executable, BENCH, "--gpus", str(n), "--mode", mode, "--steps", "3", "--warmup", "1", "--cells", "10", "--no-cpu-baseline"]
+    cmd = [sys.executable, BENCH, "--gpus", str(n), "--mode", mode, "--steps", "3", "--warmup", "1", "--cells", "10", "--no-cpu-baseline", "--full"]
     if mode == "westervelt":
         cmd += ["--degree", "6", "--cells", "4"]
     r = subprocess.run(cmd, env=_env(FUS_BENCH_REHEARSAL="1"), capture_output=True, text=True, timeout=900)
@@ -230,7 +230,7 @@ def test_hung_optional_phase_does_not_take_the_headline_with_it():
     import time
 
     t0 = time.time()
-    r = subprocess.run([sys.executable, BENCH, "--gpus", "2", "--steps", "3", "--warmup", "1", "--cells", "8", "--no-cpu-baseline"],
+    r = subprocess.run([sys.executable, BENCH, "--gpus", "2", "--steps", "3", "--warmup", "1", "--cells", "8", "--no-cpu-baseline", "--full"],
                        env=_env(FUS_BENCH_REHEARSAL="1", FUS_BENCH_TEST_HANG_EXTRAS="1", FUS_BENCH_EXTRAS_TIMEOUT_S="25"), capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, (r.stdout + r.stderr)[-3000:]
     assert time.time() - t0 < 300
@@ -281,10 +281,10 @@ def test_scatter_mode_line():
 
 @pytest.mark.gpu
 def test_default_line_carries_the_aux_entries():
-    """The driver's default command at a small size: the headline line with every ``aux`` entry of DESIGN.md section 6 (mass, its
+    """The driver's default command with ``--full`` at a small size: the headline line with every ``aux`` entry of DESIGN.md section 6 (mass, its
     cached-diagonal form, sustained applies, in-kernel geometry, the RK4 step with and without in-kernel geometry -- with its
     CPU oracle leg --, the Westervelt step of config 5's shape, scatter)."""
-    r = subprocess.run([sys.executable, BENCH, "--steps", "5", "--warmup", "2", "--cells", "12"], env=_env(), capture_output=True, text=True, timeout=900)
+    r = subprocess.run([sys.executable, BENCH, "--steps", "5", "--warmup", "2", "--cells", "12", "--full"], env=_env(), capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, (r.stdout + r.stderr)[-3000:]
     out = _one_json_line(r.stdout)
     aux = out["aux"]
@@ -327,7 +327,7 @@ def test_bench_result_check_fails_loudly(monkeypatch):
     """A wrong result must not produce a valid line: with the oracle's constants perturbed (test hook) the check fails, the line
     says ``valid: false`` and the exit code is non-zero."""
     env = dict(_env(), FUS_BENCH_TEST_BREAK_CHECK="1")
-    r = subprocess.run([sys.executable, BENCH, "--steps", "3", "--warmup", "1", "--cells", "8", "--no-aux", "--no-cpu-baseline"], env=env,
+    r = subprocess.run([sys.executable, BENCH, "--steps", "3", "--warmup", "1", "--cells", "8", "--no-aux", "--no-cpu-baseline", "--full"], env=env,
                        capture_output=True, text=True, timeout=600)
     assert r.returncode != 0
     out = _one_json_line(r.stdout)
@@ -362,3 +362,72 @@ def test_config4_topology_rehearsal_tool():
     assert out["ok"] is True and out["ranks"] == 8 and out["processes"] == 4 and out["failed_device_waits"] == 0
     assert out["forward_max_abs_err"] == 0.0 and out["owned_sum_defect_over_sum_abs"] < 1e-9
     assert sorted(out["rank0_ghosted_by"]) == [str(k) for k in range(1, 8)] and out["rank0_ghosted_by"]["7"] == 1
+
+
+def test_dump_outputs_is_bounded_and_repeatable(tmp_path):
+    """``--dump-outputs``: float arrays as <name>.npy, all of them within the budget, a larger array sampled at the same indices on
+    every call (two builds run with the same arguments are compared entry for entry)."""
+    import numpy as np
+
+    from benchlib.common import DUMP_BUDGET_BYTES, dump_outputs
+
+    assert DUMP_BUDGET_BYTES <= 64 * 10**6
+    rng = np.random.default_rng(0)
+    big, small = rng.standard_normal(5000), rng.standard_normal(100).astype(np.float32)
+    for d in ("a", "b"):
+        dump_outputs(str(tmp_path / d), {"big": big, "small": small}, budget=16000)
+    a_big, b_big = np.load(tmp_path / "a" / "big.npy"), np.load(tmp_path / "b" / "big.npy")
+    assert a_big.dtype == np.float64 and a_big.size == 1000 and np.array_equal(a_big, b_big)
+    assert np.isin(a_big, big).all() and len(np.unique(a_big)) == a_big.size
+    a_small = np.load(tmp_path / "a" / "small.npy")
+    assert a_small.dtype == np.float32 and np.array_equal(a_small, small)
+    assert sum(os.path.getsize(tmp_path / "a" / f) for f in os.listdir(tmp_path / "a")) <= 16000 + 2 * 256
+
+
+def test_rendezvous_port_is_below_the_ephemeral_range():
+    """The launcher's rendezvous port is never one the kernel hands out to outgoing connections (the other ranks' connect
+    retries could take it before rank 0 listens on it)."""
+    from benchlib.common import _free_port
+
+    with open("/proc/sys/net/ipv4/ip_local_port_range") as f:
+        low = int(f.read().split()[0])
+    for _ in range(20):
+        p = _free_port()
+        assert 1024 <= p < low
+        with socket.socket() as s:
+            s.bind(("127.0.0.1", p))
+
+
+@pytest.mark.gpu
+def test_plain_line_is_lean_and_dumps_its_outputs(tmp_path):
+    """A plain run sets up, warms up, times --steps steps and prints the line: no check, no CPU baseline, no aux lines.
+    ``--dump-outputs`` writes y after the last timed step; the same arguments with ``--full`` write the same y and check it
+    against the oracle."""
+    import numpy as np
+
+    base = [sys.executable, BENCH, "--gpus", "1", "--steps", "5", "--warmup", "2", "--cells", "12"]
+    r = subprocess.run(base + ["--dump-outputs", str(tmp_path / "plain")], env=_env(), capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, (r.stdout + r.stderr)[-3000:]
+    out = _one_json_line(r.stdout)
+    assert out["metric"] == "stiffness_apply_dof_per_s" and out["unit"] == "DOF/s" and out["higher_is_better"] is True and out["dtype"] == "f64"
+    assert out["steps"] == 5 and out["warmup"] == 2 and out["ms_per_step"] > 0
+    assert abs(out["value"] - out["config"]["global_dofs"] / (out["ms_per_step"] * 1e-3)) <= 1e-9 * out["value"]
+    assert "check" not in out and "aux" not in out and out["cpu_baseline"] is None
+    assert out["roofline"]["isolated_launch_ms_mean"] is None and out["roofline"]["measured_copy_gbs"] is None and out["roofline"]["kernel_ms"] > 0
+    assert os.listdir(tmp_path / "plain") == ["y.npy"]
+    y = np.load(tmp_path / "plain" / "y.npy")
+    assert y.dtype == np.float64 and y.size == out["config"]["global_dofs"] == 49**3 and np.isfinite(y).all() and np.abs(y).max() > 0
+    r = subprocess.run(base + ["--full", "--no-aux", "--no-cpu-baseline", "--dump-outputs", str(tmp_path / "full")], env=_env(),
+                       capture_output=True, text=True, timeout=900)
+    assert r.returncode == 0, (r.stdout + r.stderr)[-3000:]
+    full = _one_json_line(r.stdout)
+    assert full["check"]["ok"] is True and full["check"]["rel_l2"] <= 1e-12 and full["roofline"]["isolated_launch_ms_mean"] > 0
+    y_full = np.load(tmp_path / "full" / "y.npy")
+    assert np.linalg.norm(y_full - y) <= 1e-12 * np.linalg.norm(y)
+    r = subprocess.run([sys.executable, BENCH, "--mode", "rk4", "--steps", "3", "--warmup", "1", "--cells", "6", "--dump-outputs", str(tmp_path / "rk4")],
+                       env=_env(), capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, (r.stdout + r.stderr)[-3000:]
+    out = _one_json_line(r.stdout)
+    assert out["steps"] == 3 and out["check"] is None and out["cpu_baseline"] is None
+    u, v = np.load(tmp_path / "rk4" / "u.npy"), np.load(tmp_path / "rk4" / "v.npy")
+    assert u.size == v.size == out["config"]["global_dofs"] and np.isfinite(u).all() and np.abs(v).max() > 0

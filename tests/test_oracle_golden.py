@@ -1,7 +1,7 @@
 """Pin the ORACLE (numpy and C restatements) against the golden vectors that were
 produced by running the reference itself (tests/golden/generate_golden.py), and
-its two primitives against the reference's own C++ templates where
-oracle/_ref/libref_sumfact.so could be built."""
+its two primitives against the reference's own C++ templates (their stored outputs,
+and the templates themselves where oracle/_ref/libref_sumfact.so could be built)."""
 
 import ctypes as C
 import os
@@ -67,26 +67,37 @@ def test_scatter_vs_reference_closures(path):
 
 def test_primitives_vs_reference_cpp(oracle_c):
     """contract / transpose of the C oracle vs the reference's C++ templates
-    (cpp/common/sum_factorisation.hpp:43-49,70-86) compiled into oracle/_ref."""
+    (cpp/common/sum_factorisation.hpp:43-49,70-86): against their outputs stored in
+    tests/golden/ref_sumfact_primitives.npz (generate_golden.py --only sumfact), and against
+    the templates themselves where oracle/_ref could be built."""
+    d = np.load(os.path.join(ROOT, "tests", "golden", "ref_sumfact_primitives.npz"))
     so = os.path.join(ROOT, "oracle", "_ref", "libref_sumfact.so")
-    if not os.path.exists(so):
-        pytest.skip("oracle/_ref not built (reference checkout absent on this machine)")
-    ref = C.CDLL(so)
-    vp = C.c_void_p
-    ref.ref_contract_f64.argtypes = [C.c_int, C.c_int, vp, vp, vp]
-    ref.ref_transpose_f64.argtypes = [C.c_int, C.c_int, vp, vp]
+    ref = None
+    if os.path.exists(so):
+        ref = C.CDLL(so)
+        vp = C.c_void_p
+        ref.ref_contract_f64.argtypes = [C.c_int, C.c_int, vp, vp, vp]
+        ref.ref_transpose_f64.argtypes = [C.c_int, C.c_int, vp, vp]
     rng = np.random.default_rng(0)
     for n in (3, 4, 5, 7):
         A, B = rng.standard_normal(n * n), rng.standard_normal(n**3)
+        assert np.array_equal(A, d[f"A_{n}"]) and np.array_equal(B, d[f"B_{n}"])
         for tr in (0, 1):
-            c_ref, c_mine = rng.standard_normal(n**3), None
-            c_mine = c_ref.copy()
-            assert ref.ref_contract_f64(n, tr, A.ctypes.data, B.ctypes.data, c_ref.ctypes.data) == 0
+            c_in = rng.standard_normal(n**3)
+            assert np.array_equal(c_in, d[f"c_in_{n}_{tr}"])
+            c_ref, c_mine = d[f"ref_contract_{n}_{tr}"], c_in.copy()
+            if ref is not None:
+                c_live = c_in.copy()
+                assert ref.ref_contract_f64(n, tr, A.ctypes.data, B.ctypes.data, c_live.ctypes.data) == 0
+                assert np.allclose(c_live, c_ref, rtol=1e-14, atol=1e-14)
             oracle_c.lib.oracle_contract_f64(n, n, n, n, tr, A.ctypes.data, B.ctypes.data, c_mine.ctypes.data)
             assert np.allclose(c_mine, c_ref, rtol=1e-14, atol=1e-14)
         for which, offs in ((0, (n, n * n, 1)), (1, (1, n, n * n))):
-            t_ref, t_mine = np.zeros(n**3), np.zeros(n**3)
-            assert ref.ref_transpose_f64(n, which, B.ctypes.data, t_ref.ctypes.data) == 0
+            t_ref, t_mine = d[f"ref_transpose_{n}_{which}"], np.zeros(n**3)
+            if ref is not None:
+                t_live = np.zeros(n**3)
+                assert ref.ref_transpose_f64(n, which, B.ctypes.data, t_live.ctypes.data) == 0
+                assert np.array_equal(t_live, t_ref)
             oracle_c.lib.oracle_transpose_f64(n, n, n, *offs, B.ctypes.data, t_mine.ctypes.data)
             assert np.array_equal(t_mine, t_ref)
 
