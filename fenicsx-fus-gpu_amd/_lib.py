@@ -106,6 +106,7 @@ def _signatures():
         sig[f"fus_rk4_stage_nl_{suf}"] = [ct, ct, _int] + [_vp] * 9 + [_i64, _i64, _vp]
         sig[f"fus_rk4_stage_nl2_{suf}"] = [ct, ct, _int] + [_vp] * 10 + [ct, _vp, _i64, _i64, _vp]
         sig[f"fus_rk4_stage_{suf}"] = [ct, ct, _int] + [_vp] * 8 + [_i64, _i64, _vp]
+        sig[f"fus_probe_eval_{suf}"] = [_vp, _vp, _i64, _vp, _i64, _vp, _int, _vp, _i64, _int] + [_vp] * 5 + [_int, _vp]
         sig[f"fus_pack_fwd_{suf}"] = [_vp, _vp, _vp, _i64, _vp]
         sig[f"fus_unpack_fwd_{suf}"] = [_vp, _vp, _vp, _i64, _i64, _vp]
         sig[f"fus_pack_rev_{suf}"] = [_vp, _vp, _vp, _i64, _i64, _vp]

@@ -17,6 +17,7 @@
 #include "mass.hpp"
 #include "mass_gather.hpp"
 #include "plan_build.hpp"
+#include "probe.hpp"
 #include "rk4.hpp"
 #include "stiffness.hpp"
 #include "vecops.hpp"
@@ -164,6 +165,34 @@ int mass_apply_gather_static(const T* x, const T* c, T* y, const void* ws, const
   if (!x || !c || !y) return FUS_ERR_INVALID_ARGUMENT;
   return hip_rc(fus::launch_mass_gather_static<T>(x, c, y, ws, h, const_cast<void*>(sws), static_cast<hipStream_t>(stream),
                                                   g_mass_variant.load(std::memory_order_relaxed)));
+}
+
+// point sensors (csrc/probe.hpp): every check before any device work; npts == 0 is a no-op
+template <typename T>
+int probe_eval(const T* u, const int32_t* cells, int64_t npts, const int32_t* dofmap, int64_t ncells, const T* weights, int P, T* rec,
+               int64_t capacity, int slot, double* pmax, double* pmin, double* hre, double* him, const double* coef, int H,
+               void* stream) {
+  if (npts < 0 || ncells < 0 || capacity < 0 || H < 0) return FUS_ERR_INVALID_ARGUMENT;
+  if (P < FUS_MIN_DEGREE || P > FUS_MAX_DEGREE) return FUS_ERR_UNSUPPORTED_DEGREE;
+  if (npts == 0) return FUS_OK;
+  if (!u || !cells || !dofmap || !weights) return FUS_ERR_INVALID_ARGUMENT;
+  if (rec && (slot < 0 || slot >= capacity)) return FUS_ERR_INVALID_ARGUMENT;
+  if ((hre || him || H > 0) && (!hre || !him || !coef || H < 1)) return FUS_ERR_INVALID_ARGUMENT;
+  if (misaligned(u, sizeof(T)) || misaligned(weights, sizeof(T)) || misaligned(cells, sizeof(int32_t)) ||
+      misaligned(dofmap, sizeof(int32_t)))
+    return FUS_ERR_INVALID_ARGUMENT;
+  T* row = rec ? rec + (int64_t)slot * npts : nullptr;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  hipError_t e = hipErrorInvalidValue;
+  switch (P) {
+#define FUS_CASE(PP)                                                                                                        \
+  case PP:                                                                                                                  \
+    e = fus::launch_probe_eval<T, PP>(u, cells, dofmap, weights, npts, ncells, row, pmax, pmin, hre, him, coef, H, s); \
+    break;
+    FUS_CASE(1) FUS_CASE(2) FUS_CASE(3) FUS_CASE(4) FUS_CASE(5) FUS_CASE(6) FUS_CASE(7) FUS_CASE(8) FUS_CASE(9) FUS_CASE(10)
+#undef FUS_CASE
+  }
+  return hip_rc(e);
 }
 
 }  // namespace
@@ -529,6 +558,17 @@ FUS_VEC(float, f32)
 FUS_GEOM(double, f64)
 FUS_GEOM(float, f32)
 #undef FUS_GEOM
+
+int fus_probe_eval_f64(const double* u, const int32_t* cells, int64_t npts, const int32_t* dofmap, int64_t ncells,
+                       const double* weights, int P, double* rec, int64_t capacity, int slot, double* pmax, double* pmin, double* hre,
+                       double* him, const double* coef, int H, void* stream) {
+  return probe_eval<double>(u, cells, npts, dofmap, ncells, weights, P, rec, capacity, slot, pmax, pmin, hre, him, coef, H, stream);
+}
+int fus_probe_eval_f32(const float* u, const int32_t* cells, int64_t npts, const int32_t* dofmap, int64_t ncells,
+                       const float* weights, int P, float* rec, int64_t capacity, int slot, double* pmax, double* pmin, double* hre,
+                       double* him, const double* coef, int H, void* stream) {
+  return probe_eval<float>(u, cells, npts, dofmap, ncells, weights, P, rec, capacity, slot, pmax, pmin, hre, him, coef, H, stream);
+}
 
 #define FUS_AFFINE(T, SUF)                                                                                       \
   int fus_stiffness_apply_planned_affine_##SUF(const T* x, const T* cc, T* y, const T* G, const T* wratio,       \

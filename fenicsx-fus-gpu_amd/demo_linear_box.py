@@ -34,6 +34,8 @@ def main():
     ap.add_argument("--eval-out", default=None, metavar="DIR",
                     help="evaluate the final pressure field at the reference's 100 x 100 points of the z = 0 plane and append the rows "
                          "'x,y,value' to DIR/pressure_field_nproc<N>.txt, rank after rank (cuda/demo_linear_box.py:128-141,587-605)")
+    ap.add_argument("--device-eval", action="store_true",
+                    help="--eval-out evaluates on the device (sensors.PointSensors.evaluate) instead of the host's eval_function; same rows")
     a = ap.parse_args()
 
     import torch
@@ -93,12 +95,21 @@ def main():
         X_p, Y_p = np.meshgrid(xp, xp)
         points = np.zeros((3, 100 * 100), dtype=float_type)
         points[0], points[1] = X_p.flatten(), Y_p.flatten()
-        x_eval, cell_eval = pe.compute_eval_params(mesh, points, float_type)
-        u_full = solver.u_sol(with_ghosts=True)
-        data = np.zeros_like(x_eval)
-        if len(cell_eval):
-            data[:, 0], data[:, 1] = x_eval[:, 0], x_eval[:, 1]
-            data[:, 2] = pe.eval_function(mesh, u_full, x_eval, cell_eval)
+        if a.device_eval:
+            sens = fusgpu_loader.submodule("sensors").PointSensors(mesh, points, float_type)
+            if solver.halo is not None:
+                solver.halo.fwd(solver.u)  # the ghosts the points' cells read
+            order = np.argsort(sens.point_ids)  # the caller's point order, as compute_eval_params keeps it
+            data = np.zeros((order.size, 3))
+            data[:, 0], data[:, 1] = sens.points[order, 0], sens.points[order, 1]
+            data[:, 2] = sens.evaluate(solver.u).cpu().numpy()[order]
+        else:
+            x_eval, cell_eval = pe.compute_eval_params(mesh, points, float_type)
+            u_full = solver.u_sol(with_ghosts=True)
+            data = np.zeros_like(x_eval)
+            if len(cell_eval):
+                data[:, 0], data[:, 1] = x_eval[:, 0], x_eval[:, 1]
+                data[:, 2] = pe.eval_function(mesh, u_full, x_eval, cell_eval)
         if rank == 0:
             os.makedirs(a.eval_out, exist_ok=True)
         for i in range(world):  # :597-605: one rank after the other appends to the same file

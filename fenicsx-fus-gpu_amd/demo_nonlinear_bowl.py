@@ -10,6 +10,7 @@ a structured box is warped by a smooth bowl map, which gives what its geometry g
 cells (G varies per quadrature point; P1 geometry, cuda/demo_nonlinear_bowl.py:317).
 
     python fenicsx-fus-gpu_amd/demo_nonlinear_bowl.py [--degree 6] [--cells N] [--out-dir DIR] [--max-steps K]
+    python fenicsx-fus-gpu_amd/demo_nonlinear_bowl.py --sensor-plane 141,241 --out-dir DIR [--peak-out FILE]   # recorded on the device
     python -m torch.distributed.run --nproc-per-node 8 fenicsx-fus-gpu_amd/demo_nonlinear_bowl.py
 
 Dumps: ``DIR/pressure_field_<k>.txt`` for k = 0 .. steps_per_period-1, rows ``x,y,p`` on the mid-z plane of the dof grid
@@ -40,7 +41,14 @@ def main():
     ap.add_argument("--in-kernel-geometry", action="store_true", help="same as --geometry kernel")
     ap.add_argument("--max-steps", type=int, default=None)
     ap.add_argument("--out-dir", default=None, help="write the last-period pressure fields there")
+    ap.add_argument("--sensor-plane", default=None, metavar="NX,NY",
+                    help="evaluate on the device at an NX x NY grid of points on the mid-z plane of the domain (the counterpart of the "
+                         "reference's own point grid, cuda/demo_linear_piston.py) and record the last period in ONE rk4 call")
+    ap.add_argument("--peak-out", default=None, metavar="FILE",
+                    help="with --sensor-plane: write rows 'x,y,max,min,|H1|,|H2|' over the last period to FILE")
     a = ap.parse_args()
+    if a.peak_out and not a.sensor_plane:
+        ap.error("--peak-out needs --sensor-plane")
 
     import torch
     import torch.distributed as dist
@@ -116,6 +124,10 @@ def main():
     t0 = time.perf_counter()
     t_collect = L / speed_of_sound + 6.0 / source_frequency  # :662
     budget = a.max_steps if a.max_steps is not None else nstep
+    if a.sensor_plane:
+        run_with_sensors(a, solver, mesh, comm, rank, world, L, float_type, t0, tf, dt, nstep, budget, t_collect, step_per_period,
+                         source_frequency)
+        return
     # up to the collection window in one go (no host round trip per step), then step by step with one dump per step
     n_before = min(budget, max(0, int(np.floor(t_collect / dt)) - 1))  # t stays <= the threshold: no dump is skipped
     t, steps = solver.rk4(0.0, tf, dt, max_steps=n_before) if n_before > 0 else (0.0, 0)
@@ -138,6 +150,52 @@ def main():
         print(f"Fields collected over the last period: {step_period}/{step_per_period}")
         print(f"Solve time: {el}")
         print(f"Solve time per step: {el / max(steps, 1)}")
+    if world > 1:
+        dist.destroy_process_group()
+
+
+def run_with_sensors(a, solver, mesh, comm, rank, world, L, float_type, t0, tf, dt, nstep, budget, t_collect, step_per_period, f0):
+    """The whole run in ONE rk4 call with point sensors recording the last period on the device (no full-field copy per step)."""
+    import torch
+    import torch.distributed as dist
+
+    import fusgpu_loader
+
+    sens = fusgpu_loader.submodule("sensors")
+    nx, ny = (int(v) for v in a.sensor_plane.split(","))
+    X, Y = np.meshgrid(np.linspace(0.0, L, nx), np.linspace(0.0, L, ny), indexing="ij")
+    points = np.stack([X.reshape(-1), Y.reshape(-1), np.full(X.size, 0.5 * L)], axis=1)
+    s = sens.PointSensors(mesh, points, float_type, capacity=step_per_period, peak=bool(a.peak_out),
+                          harmonics=(1, 2) if a.peak_out else (), frequency=f0)
+    t, steps = solver.rk4(0.0, tf, dt, max_steps=budget, sensors=s, record_from=t_collect)
+    torch.cuda.synchronize()
+    el = time.perf_counter() - t0
+    series = s.series()
+    # every rank's points merged over the global list (a point on a face shared by two ranks: the lower rank's value)
+    merged = s.gather(comm, series) if world > 1 else sens.merge([(s.point_ids, series)], points.shape[0])
+    located = np.nonzero(~np.isnan(merged[0]))[0] if merged.shape[0] else np.zeros(0, np.int64)
+    if rank == 0:
+        print(f"t: {t:5.5},\t Steps: {steps}/{nstep}", flush=True)
+        print(f"Fields collected over the last period: {s.nrec}/{step_per_period}")
+        print(f"Sensor points on this plane: {located.size}/{points.shape[0]}")
+        print(f"Solve time: {el}")
+        print(f"Solve time per step: {el / max(steps, 1)}")
+        data = np.zeros((located.size, 3))
+        data[:, 0], data[:, 1] = points[located, 0], points[located, 1]
+        if a.out_dir:
+            os.makedirs(a.out_dir, exist_ok=True)
+            for k in range(merged.shape[0]):
+                data[:, 2] = merged[k, located]
+                with open(os.path.join(a.out_dir, f"pressure_field_{k}.txt"), "a") as f:
+                    np.savetxt(f, data, fmt="%.8f", delimiter=",")  # the reference's format, :675
+    if a.peak_out:
+        pmax, pmin = s.peak()
+        cols = np.stack([pmax, pmin, s.harmonic_amplitude(1), s.harmonic_amplitude(2)])  # [4, m]
+        allc = s.gather(comm, cols) if world > 1 else sens.merge([(s.point_ids, cols)], points.shape[0])
+        if rank == 0:
+            keep = np.nonzero(~np.isnan(allc[0]))[0]
+            rows = np.column_stack([points[keep, 0], points[keep, 1], allc[:, keep].T])
+            np.savetxt(a.peak_out, rows, fmt="%.8f", delimiter=",")
     if world > 1:
         dist.destroy_process_group()
 

@@ -33,6 +33,7 @@ import torch
 from . import _lib
 from . import operators as ops
 from .gll import gll_points_weights, tabulate_1d, tensor_points_3d, tensor_weights_2d, tensor_weights_3d
+from .sensors import record_schedule
 from .step_graph import StepGraphMixin
 from .precompute import (
     compute_boundary_facets_scaled_jacobian_determinant_device,
@@ -311,10 +312,11 @@ class LinearSpectral3D(StepGraphMixin):
         last = i == 3
         return B_RUNGE[i] * dt, 0.0 if last else A_RUNGE[i + 1] * dt, 3 if last else (2 if i == 0 else 0)
 
-    def rk4(self, start_time, final_time, dt, max_steps=None):
+    def rk4(self, start_time, final_time, dt, max_steps=None, sensors=None, record_from=None):
         """Advance from ``start_time`` to ``final_time`` (cuda/demo_linear_box.py:487-566).
-        Returns ``(t, steps)``."""
-        gen = self.rk4_schedule(start_time, final_time, dt, max_steps)
+        Returns ``(t, steps)``.  ``sensors``: a ``sensors.PointSensors`` recorded after every step that ends after
+        ``record_from`` (default: every step) while its series has room -- the supported way to observe the field mid-run."""
+        gen = self.rk4_schedule(start_time, final_time, dt, max_steps, sensors, record_from)
         while True:
             try:
                 next(gen)
@@ -329,12 +331,18 @@ class LinearSpectral3D(StepGraphMixin):
         if self.halo is not None:
             self.halo.check_health(what)
 
-    def rk4_schedule(self, start_time, final_time, dt, max_steps=None):
+    def rk4_schedule(self, start_time, final_time, dt, max_steps=None, sensors=None, record_from=None):
         """``rk4`` as a generator that yields whenever this rank has posted halo exchanges (see
         ``HaloApply.schedule``); its return value is ``(t, steps)``.  A driver that advances several ranks' generators
-        itself calls ``check_halo_health()`` when they are exhausted (``rk4`` does)."""
+        itself calls ``check_halo_health()`` when they are exhausted (``rk4`` does).  ``u`` / ``v`` are valid only once
+        the generator is exhausted (the fused path keeps the solution in ``u0`` / ``v0`` between steps): observe the field
+        mid-run through ``sensors`` (see ``rk4``; on a partitioned mesh a recording step posts a forward exchange of the
+        field first, with a yield)."""
         t, step = float(start_time), 0
         tf = float(final_time)
+        rf = -np.inf if record_from is None else float(record_from)
+        if sensors is not None:
+            sensors.expect_steps(t, tf, dt, max_steps, record_from)
         if self.fused:
             # between steps the solution lives in (u0, v0): they are the first stage's inputs as they
             # stand, and the last stage writes the new solution straight into them (stage kinds 2, 0, 0,
@@ -359,6 +367,8 @@ class LinearSpectral3D(StepGraphMixin):
                     yield from self._stage_reference(i, t, dt)
             t += dt
             step += 1
+            if sensors is not None and t > rf and not sensors.full:
+                yield from record_schedule(sensors, self.u0 if self.fused else self.u, t, self.halo)
         if self.fused:
             ops.copy(self.u0, self.u)
             ops.copy(self.v0, self.v)
@@ -391,7 +401,8 @@ class LinearSpectral3D(StepGraphMixin):
 
     def u_sol(self, with_ghosts=False):
         """Owned part of the pressure field on the host; ``with_ghosts``: the whole local vector after a forward scatter
-        (``scatter_fwd(u_n_d); u_n_d.copy_to_host(u_n)``, cuda/demo_linear_box.py:568-570 -- what point evaluation needs)."""
+        (``scatter_fwd(u_n_d); u_n_d.copy_to_host(u_n)``, cuda/demo_linear_box.py:568-570 -- what point evaluation needs).
+        Valid once ``rk4()`` has returned; mid-run, ``rk4(..., sensors=...)`` observes the field on the device."""
         if not with_ghosts:
             return self.u[: self.nlocal].detach().cpu().numpy()
         if self.halo is not None:

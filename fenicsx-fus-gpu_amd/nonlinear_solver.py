@@ -22,6 +22,7 @@ from . import _lib
 from . import operators as ops
 from .linear_solver import A_RUNGE, B_RUNGE, C_RUNGE
 from .linear_solver import device_geometry
+from .sensors import record_schedule
 from .step_graph import StepGraphMixin
 
 
@@ -337,8 +338,10 @@ class WesterveltSpectral3D(StepGraphMixin):
         last = i == 3
         return B_RUNGE[i] * dt, 0.0 if last else A_RUNGE[i + 1] * dt, 3 if last else (2 if i == 0 else 0)
 
-    def rk4(self, start_time, final_time, dt, max_steps=None):
-        gen = self.rk4_schedule(start_time, final_time, dt, max_steps)
+    def rk4(self, start_time, final_time, dt, max_steps=None, sensors=None, record_from=None):
+        """Advance from ``start_time`` to ``final_time``; returns ``(t, steps)``.  ``sensors`` / ``record_from``: as
+        ``LinearSpectral3D.rk4``."""
+        gen = self.rk4_schedule(start_time, final_time, dt, max_steps, sensors, record_from)
         while True:
             try:
                 next(gen)
@@ -350,9 +353,13 @@ class WesterveltSpectral3D(StepGraphMixin):
         if self.halo is not None:
             self.halo.check_health(what)
 
-    def rk4_schedule(self, start_time, final_time, dt, max_steps=None):
-        """``rk4`` as a generator that yields whenever this rank has posted halo exchanges; returns ``(t, steps)``."""
+    def rk4_schedule(self, start_time, final_time, dt, max_steps=None, sensors=None, record_from=None):
+        """``rk4`` as a generator that yields whenever this rank has posted halo exchanges; returns ``(t, steps)``.  ``u`` /
+        ``v`` are valid only once it is exhausted; ``sensors`` observe the field mid-run (``LinearSpectral3D.rk4_schedule``)."""
         t, step, tf = float(start_time), 0, float(final_time)
+        rf = -np.inf if record_from is None else float(record_from)
+        if sensors is not None:
+            sensors.expect_steps(t, tf, dt, max_steps, record_from)
         if self.fused:
             ops.fill(1.0, self.g)  # source enters through scaled facet constants
             ops.fill(0.0, self.b)
@@ -378,12 +385,15 @@ class WesterveltSpectral3D(StepGraphMixin):
                     self._stage(i, t, dt)
             t += dt
             step += 1
+            if sensors is not None and t > rf and not sensors.full:
+                yield from record_schedule(sensors, self.u0 if self.fused else self.u, t, self.halo)
         if self.fused:
             ops.copy(self.u0, self.u)
             ops.copy(self.v0, self.v)
         return t, step
 
     def u_sol(self):
+        """Owned part of the pressure field on the host, valid once ``rk4()`` has returned (mid-run: ``sensors``)."""
         return self.u[: self.nlocal].detach().cpu().numpy()
 
     def v_sol(self):

@@ -61,17 +61,22 @@ class StepGraphMixin:
             self._graph_plans[dt] = held
         return g
 
-    def rk4_graph(self, start_time, final_time, dt, max_steps=None):
+    def rk4_graph(self, start_time, final_time, dt, max_steps=None, sensors=None, record_from=None):
         """``rk4`` with the full-size steps replayed from ONE captured hipGraph.  Same kernels in the same
         order on the same data as ``rk4``.  One rank, fused path; a last shorter step runs through ``rk4``.
-        Returns ``(t, steps)``."""
+        ``sensors`` / ``record_from`` as in ``rk4``: the sensor launch follows a replay on the same stream, outside the
+        captured graph.  Returns ``(t, steps)``."""
         if not self.fused or self.halo is not None:
             raise _lib.FusGpuError("rk4_graph: single-rank fused path only")
         t, tf = float(start_time), float(final_time)
-        rows = []
+        rf = -np.inf if record_from is None else float(record_from)
+        rows, ends = [], []
+        if sensors is not None:
+            sensors.expect_steps(t, tf, dt, max_steps, record_from)
         while t < tf and (max_steps is None or len(rows) < max_steps) and min(dt, tf - t) == dt:
             rows.append([self._graph_scalars(t + C_RUNGE[i] * dt if self.source_time == "tn" else t) for i in range(4)])
             t += dt
+            ends.append(t)
         if rows:
             if not hasattr(self, "_graphs"):
                 self._graphs = {}
@@ -82,9 +87,11 @@ class StepGraphMixin:
             for k in range(len(rows)):
                 self._scal.copy_(table[k])
                 graph.replay()
+                if sensors is not None and ends[k] > rf and not sensors.full:
+                    sensors.record(self.u0, ends[k])
             self._graph_exit()
         steps = len(rows)
         if t < tf and (max_steps is None or steps < max_steps):
-            t, more = self.rk4(t, tf, dt, None if max_steps is None else max_steps - steps)
+            t, more = self.rk4(t, tf, dt, None if max_steps is None else max_steps - steps, sensors, record_from)
             steps += more
         return t, steps

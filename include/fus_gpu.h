@@ -53,7 +53,8 @@ extern "C" {
  *      enforce their one-caller-stream contract (FUS_ERR_INVALID_ARGUMENT); new: fus_comm_fork_lazy, fus_comm_arm_join,
  *      fus_comm_health; the PEER blob identifies the exporting process by a random token and its device by PCI bus id.
  *      Added since without a bump (new symbols only): fus_mass_gather_plan_bytes / _build / _info, fus_mass_apply_gather_*,
- *      fus_mass_gather_plan_build_rows, fus_mass_gather_static_bytes / _build_* , fus_mass_apply_gather_static_*.
+ *      fus_mass_gather_plan_build_rows, fus_mass_gather_static_bytes / _build_* , fus_mass_apply_gather_static_*,
+ *      fus_probe_eval_*.
  * There are deliberately NO fus_cpu_* twins of the entry points (SURVEY.md 8b proposed them): a CPU path inside the
  * product would be a silent fallback; the CPU restatement of the reference is test infrastructure and lives outside the product tree.
  */
@@ -145,6 +146,27 @@ int fus_facet_terms_dev_f64(double* y, const double* cA1, const double* cA2, con
 int fus_facet_terms_dev_f32(float* y, const float* cA1, const float* cA2, const float* scalars, const float* detJA,
                             const int32_t* dmA, int64_t nentA, const float* xB, const float* cB, const float* detJB,
                             const int32_t* dmB, int64_t nentB, int ndof_per_entity, void* stream);
+
+/*
+ * Point sensors (csrc/probe.hpp) -- replaces the reference's per-step host evaluation of its collection window,
+ * ``u_n_.eval(x_eval, cell_eval)`` (cuda/demo_linear_piston.py, cuda/demo_nonlinear_bowl.py: a full-field copy to the host
+ * and a dolfinx Function.eval per step).  One launch evaluates the degree-P interpolant of ``u`` at ``npts`` points:
+ *   cells    int32[npts]           the cell of each point, in [0, ncells)
+ *   dofmap   int32[ncells][n^3]    tensor-product local order (the operators' dofmap)
+ *   weights  T[npts][3][n]         the 1-D Lagrange rows Lx, Ly, Lz of each point's reference coordinates
+ *   value[p] = sum_ijk Lx[i] Ly[j] Lz[k] u[dofmap[c][i n^2 + j n + k]]   (summed in double, rounded to T)
+ * and applies every output whose pointer is non-null:
+ *   rec      T[capacity][npts]     row ``slot`` = the values (slot in [0, capacity))
+ *   pmax / pmin  double[npts]      running maximum / minimum
+ *   hre / him    double[H][npts]   += value * coef[2h] / += value * coef[2h + 1]; coef double[2H] in DEVICE memory (H >= 1)
+ * Each point's outputs are written by one thread: no atomics.  npts == 0 is a no-op.
+ */
+int fus_probe_eval_f64(const double* u, const int32_t* cells, int64_t npts, const int32_t* dofmap, int64_t ncells,
+                       const double* weights, int P, double* rec, int64_t capacity, int slot, double* pmax, double* pmin,
+                       double* hre, double* him, const double* coef, int H, void* stream);
+int fus_probe_eval_f32(const float* u, const int32_t* cells, int64_t npts, const int32_t* dofmap, int64_t ncells,
+                       const float* weights, int P, float* rec, int64_t capacity, int slot, double* pmax, double* pmin,
+                       double* hre, double* him, const double* coef, int H, void* stream);
 
 /*
  * Opt-in fast path for AFFINE cells (reported separately from the headline, whose

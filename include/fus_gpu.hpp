@@ -76,6 +76,10 @@ struct Abi<double> {
   static int mass_gather_static(const double* x, const double* c, double* y, const void* ws, const void* sws, int N, int64_t ne, void* s) {
     return fus_mass_apply_gather_static_f64(x, c, y, ws, sws, N, ne, s);
   }
+  static int probe(const double* u, const int32_t* cells, int64_t m, const int32_t* dm, int64_t nc, const double* w, int P, double* rec,
+                   int64_t cap, int slot, double* pmax, double* pmin, double* hre, double* him, const double* coef, int H, void* s) {
+    return fus_probe_eval_f64(u, cells, m, dm, nc, w, P, rec, cap, slot, pmax, pmin, hre, him, coef, H, s);
+  }
 };
 template <>
 struct Abi<float> {
@@ -98,6 +102,10 @@ struct Abi<float> {
   }
   static int mass_gather_static(const float* x, const float* c, float* y, const void* ws, const void* sws, int N, int64_t ne, void* s) {
     return fus_mass_apply_gather_static_f32(x, c, y, ws, sws, N, ne, s);
+  }
+  static int probe(const float* u, const int32_t* cells, int64_t m, const int32_t* dm, int64_t nc, const float* w, int P, float* rec,
+                   int64_t cap, int slot, double* pmax, double* pmin, double* hre, double* him, const double* coef, int H, void* s) {
+    return fus_probe_eval_f32(u, cells, m, dm, nc, w, P, rec, cap, slot, pmax, pmin, hre, him, coef, H, s);
   }
 };
 
@@ -311,6 +319,36 @@ private:
   detail::DeviceBuffer<T> G_own_;
   const T* dphi_ = nullptr;
   detail::Plan plan_;
+};
+
+// Point sensors (fus_probe_eval_*): the field at fixed points after every step, in place of the reference's per-step
+// ``u_n_.eval(x_eval, cell_eval)`` (cuda/demo_linear_piston.py).  The host locates the points once: ``cells`` [npts] (rows of
+// ``dofmap``), ``weights`` [npts][3][P + 1] (1-D Lagrange rows at the reference coordinates).  All device arrays, caller-owned.
+template <typename T, int P>
+class PointProbe {
+ public:
+  PointProbe(const int32_t* cells, int64_t npts, const int32_t* dofmap, int64_t ncells, const T* weights)
+      : cells_(cells), npts_(npts), dofmap_(dofmap), ncells_(ncells), weights_(weights) {
+    static_assert(P >= FUS_MIN_DEGREE && P <= FUS_MAX_DEGREE, "degree out of range");
+    check_abi();
+  }
+  // out[npts] = u at the points
+  void operator()(const T* u, T* out, void* stream = nullptr) const { (*this)(u, out, 1, 0, nullptr, nullptr, nullptr, nullptr, nullptr, 0, stream); }
+  // the general launch: row ``slot`` of rec[capacity][npts], running max / min, H harmonic accumulators (null = off)
+  void operator()(const T* u, T* rec, int64_t capacity, int slot, double* pmax, double* pmin, double* hre, double* him,
+                  const double* coef, int H, void* stream = nullptr) const {
+    check(detail::Abi<T>::probe(u, cells_, npts_, dofmap_, ncells_, weights_, P, rec, capacity, slot, pmax, pmin, hre, him, coef, H,
+                                stream),
+          "fus_probe_eval");
+  }
+  int64_t npts() const { return npts_; }
+
+ private:
+  const int32_t* cells_;
+  int64_t npts_;
+  const int32_t* dofmap_;
+  int64_t ncells_;
+  const T* weights_;
 };
 
 }  // namespace fus_gpu
