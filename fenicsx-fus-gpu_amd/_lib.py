@@ -106,6 +106,8 @@ def _signatures():
         sig[f"fus_rk4_stage_nl_{suf}"] = [ct, ct, _int] + [_vp] * 9 + [_i64, _i64, _vp]
         sig[f"fus_rk4_stage_nl2_{suf}"] = [ct, ct, _int] + [_vp] * 10 + [ct, _vp, _i64, _i64, _vp]
         sig[f"fus_rk4_stage_{suf}"] = [ct, ct, _int] + [_vp] * 8 + [_i64, _i64, _vp]
+        sig[f"fus_facet_source_array_{suf}"] = [_vp] * 6 + [_i64] + [_vp] * 3 + [_i64] + [_vp] * 4 + [_i64, _int, _vp, _vp]
+        sig[f"fus_facet_source_array_dev_{suf}"] = [_vp] * 6 + [_i64] + [_vp] * 3 + [_i64] + [_vp] * 4 + [_i64, _int, _vp, _vp]
         sig[f"fus_probe_eval_{suf}"] = [_vp, _vp, _i64, _vp, _i64, _vp, _int, _vp, _i64, _int] + [_vp] * 5 + [_int, _vp]
         sig[f"fus_pack_fwd_{suf}"] = [_vp, _vp, _vp, _i64, _vp]
         sig[f"fus_unpack_fwd_{suf}"] = [_vp, _vp, _vp, _i64, _i64, _vp]

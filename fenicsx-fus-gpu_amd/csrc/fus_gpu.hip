@@ -19,6 +19,7 @@
 #include "plan_build.hpp"
 #include "probe.hpp"
 #include "rk4.hpp"
+#include "source_array.hpp"
 #include "stiffness.hpp"
 #include "vecops.hpp"
 #include "westervelt.hpp"
@@ -193,6 +194,30 @@ int probe_eval(const T* u, const int32_t* cells, int64_t npts, const int32_t* do
 #undef FUS_CASE
   }
   return hip_rc(e);
+}
+
+// phased-array source facets (csrc/source_array.hpp): every check before any device work; nA + nB == 0 is a no-op.
+// ``stage``: the fp64 block {t, w0, A, f0, alpha, D} in host memory (copied into the launch) or, with ``dev``, in device memory.
+template <typename T>
+int facet_source_array(T* y, const T* cA1, const T* cA2, const T* detJA, const int32_t* dmA, const int32_t* eid, int64_t nA,
+                       const double* amp, const double* phase, const double* delay, int64_t E, const T* xB, const T* cB, const T* detJB,
+                       const int32_t* dmB, int64_t nB, int N, const double* stage, bool dev, void* stream) {
+  if (nA < 0 || nB < 0 || E < 0 || N < 1) return FUS_ERR_INVALID_ARGUMENT;
+  if (nA == 0 && nB == 0) return FUS_OK;
+  if (!y || !stage) return FUS_ERR_INVALID_ARGUMENT;
+  if (nA > 0 && (E < 1 || !cA1 || !detJA || !dmA || !eid || !amp || !phase || !delay)) return FUS_ERR_INVALID_ARGUMENT;
+  if (nB > 0 && (!xB || !cB || !detJB || !dmB)) return FUS_ERR_INVALID_ARGUMENT;
+  if (misaligned(y, sizeof(T)) || misaligned(stage, sizeof(double)) || misaligned(amp, sizeof(double)) ||
+      misaligned(phase, sizeof(double)) || misaligned(delay, sizeof(double)) || misaligned(eid, sizeof(int32_t)))
+    return FUS_ERR_INVALID_ARGUMENT;
+  fus::SourceStage st{0.0, 0.0, 0.0, 1.0, 1.0, 0.0};
+  if (!dev) {
+    st = fus::SourceStage{stage[0], stage[1], stage[2], stage[3], stage[4], stage[5]};
+    // a NaN fails every comparison: f0 and alpha must be positive, D zero (continuous wave) or positive
+    if (!(st.f0 > 0.0) || !(st.alpha > 0.0) || !(st.D >= 0.0)) return FUS_ERR_INVALID_ARGUMENT;
+  }
+  return hip_rc(fus::launch_facet_source_array<T>(y, cA1, cA2, detJA, dmA, eid, nA, amp, phase, delay, xB, cB, detJB, dmB, nB, N, st,
+                                                  dev ? stage : nullptr, static_cast<hipStream_t>(stream)));
 }
 
 }  // namespace
@@ -497,6 +522,26 @@ int fus_mass_apply_f32(const float* x, const float* c, float* y, const float* de
 FUS_FACET(double, f64)
 FUS_FACET(float, f32)
 #undef FUS_FACET
+
+#define FUS_SOURCE_ARRAY(T, SUF)                                                                                          \
+  int fus_facet_source_array_##SUF(T* y, const T* cA1, const T* cA2, const T* detJA, const int32_t* dmA,                    \
+                                   const int32_t* element_of_facet, int64_t nentA, const double* amplitude, const double* phase, \
+                                   const double* delay, int64_t nelem, const T* xB, const T* cB, const T* detJB,             \
+                                   const int32_t* dmB, int64_t nentB, int N, const double* stage, void* s) {                 \
+    return facet_source_array<T>(y, cA1, cA2, detJA, dmA, element_of_facet, nentA, amplitude, phase, delay, nelem, xB, cB, \
+                                 detJB, dmB, nentB, N, stage, false, s);                                                  \
+  }                                                                                                                       \
+  int fus_facet_source_array_dev_##SUF(T* y, const T* cA1, const T* cA2, const T* detJA, const int32_t* dmA,                \
+                                       const int32_t* element_of_facet, int64_t nentA, const double* amplitude,            \
+                                       const double* phase, const double* delay, int64_t nelem, const T* xB, const T* cB,  \
+                                       const T* detJB, const int32_t* dmB, int64_t nentB, int N, const double* stage_dev,   \
+                                       void* s) {                                                                         \
+    return facet_source_array<T>(y, cA1, cA2, detJA, dmA, element_of_facet, nentA, amplitude, phase, delay, nelem, xB, cB, \
+                                 detJB, dmB, nentB, N, stage_dev, true, s);                                               \
+  }
+FUS_SOURCE_ARRAY(double, f64)
+FUS_SOURCE_ARRAY(float, f32)
+#undef FUS_SOURCE_ARRAY
 
 #define FUS_VEC(T, SUF)                                                                                       \
   int fus_axpy_##SUF(T alpha, const T* x, T* y, int64_t n, void* s) {                                         \

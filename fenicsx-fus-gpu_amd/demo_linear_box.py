@@ -6,6 +6,7 @@ stage sequence :487-566, final-plane sampling :128-141) on the synthetic structu
 replaces dolfinx's ``create_box``.
 
     python fenicsx-fus-gpu_amd/demo_linear_box.py [--cells N] [--degree P] [--reference-sequence] [--out file.npz]
+    python fenicsx-fus-gpu_amd/demo_linear_box.py --array 8,8 --focus 0.06,0.05,0.06     # phased array focused on a point
     python -m torch.distributed.run --nproc-per-node 8 fenicsx-fus-gpu_amd/demo_linear_box.py   # one rank per GPU
 
 Prints the reference's progress / timing lines (cuda/demo_linear_box.py:125,183,569-581) and
@@ -36,7 +37,13 @@ def main():
                          "'x,y,value' to DIR/pressure_field_nproc<N>.txt, rank after rank (cuda/demo_linear_box.py:128-141,587-605)")
     ap.add_argument("--device-eval", action="store_true",
                     help="--eval-out evaluates on the device (sensors.PointSensors.evaluate) instead of the host's eval_function; same rows")
+    ap.add_argument("--array", default=None, metavar="NY,NZ",
+                    help="split the source face x = 0 into NY x NZ elements (sources.SourceArray) with delays that focus on --focus, and "
+                         "report the peak pressure at the focus and along the x axis through it, recorded on the device every step")
+    ap.add_argument("--focus", default=None, metavar="X,Y,Z", help="focal point of --array in m (default: the centre of the box)")
     a = ap.parse_args()
+    if a.focus and not a.array:
+        ap.error("--focus needs --array")
 
     import torch
     import torch.distributed as dist
@@ -69,20 +76,42 @@ def main():
     if rank == 0:
         print(f"Number of steps: {nstep}", flush=True)
         print(f"Number of degrees-of-freedom: {mesh.ndofs_global}", flush=True)
+    source, probes = None, None
+    if a.array:
+        src, sens = fusgpu_loader.submodule("sources"), fusgpu_loader.submodule("sensors")
+        ny, nz = (int(v) for v in a.array.split(","))
+        L = domain_length
+        focus = np.array([float(v) for v in a.focus.split(",")] if a.focus else [0.5 * L] * 3)
+        centres = src.grid_centres(ny, nz, 0.0, (0.0, L), (0.0, L))  # the global layout: every rank assigns its facets by centroid
+        source = src.SourceArray(src.grid_elements(ny, nz, (0.0, L), (0.0, L)), delay=src.focus_delays(centres, focus, speed_of_sound),
+                                 n_elements=ny * nz)
+        # the focus and 64 points along the x axis through it: running peaks on the device (sensors.PointSensors)
+        axis = np.stack([np.linspace(0.0, L, 64), np.full(64, focus[1]), np.full(64, focus[2])], axis=1)
+        pts = np.concatenate([focus[None, :], axis])
+        probes = (pts, sens.PointSensors(mesh, pts, float_type, peak=True))
     solver = ls.LinearSpectral3D(mesh, float_type, speed_of_sound, density, source_frequency, source_amplitude,
-                                 comm=comm, fused=not a.reference_sequence)
+                                 comm=comm, fused=not a.reference_sequence, source=source)
     solver.init()
     if rank == 0:
         print("Solve!", flush=True)
     torch.cuda.synchronize()
     t0 = time.perf_counter()
-    t, steps = solver.rk4(0.0, tf, dt, max_steps=a.max_steps)
+    t, steps = solver.rk4(0.0, tf, dt, max_steps=a.max_steps, sensors=probes[1] if probes else None)
     torch.cuda.synchronize()
     el = time.perf_counter() - t0
     if rank == 0:
         print(f"t: {t:5.5},\t Steps: {steps}/{nstep}", flush=True)
         print(f"Solve time: {el}")
         print(f"Solve time per step: {el / max(steps, 1)}")
+    if probes is not None:
+        pts, s = probes
+        pmax = s.peak()[0][None, :]
+        peak = (s.gather(comm, pmax) if world > 1 else fusgpu_loader.submodule("sensors").merge([(s.point_ids, pmax)], pts.shape[0]))[0]
+        if rank == 0:
+            k = int(np.nanargmax(peak[1:])) + 1
+            print(f"Array elements: {a.array.replace(',', ' x ')}, focus: {tuple(float(v) for v in pts[0])}")
+            print(f"Peak pressure at the focus: {peak[0]}")
+            print(f"Peak pressure on the axis: {peak[k]} at x = {pts[k, 0]}")
     if a.out:
         lex = mesh.global_lexicographic_ids()[: mesh.nlocal]
         gd = mesh.global_dof_dims

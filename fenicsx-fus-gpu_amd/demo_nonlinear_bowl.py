@@ -11,6 +11,7 @@ cells (G varies per quadrature point; P1 geometry, cuda/demo_nonlinear_bowl.py:3
 
     python fenicsx-fus-gpu_amd/demo_nonlinear_bowl.py [--degree 6] [--cells N] [--out-dir DIR] [--max-steps K]
     python fenicsx-fus-gpu_amd/demo_nonlinear_bowl.py --sensor-plane 141,241 --out-dir DIR [--peak-out FILE]   # recorded on the device
+    python fenicsx-fus-gpu_amd/demo_nonlinear_bowl.py --sensor-plane 61,61 --peak-out FILE --array 6,6 --focus 0.008,0.006,0.006
     python -m torch.distributed.run --nproc-per-node 8 fenicsx-fus-gpu_amd/demo_nonlinear_bowl.py
 
 Dumps: ``DIR/pressure_field_<k>.txt`` for k = 0 .. steps_per_period-1, rows ``x,y,p`` on the mid-z plane of the dof grid
@@ -46,7 +47,14 @@ def main():
                          "reference's own point grid, cuda/demo_linear_piston.py) and record the last period in ONE rk4 call")
     ap.add_argument("--peak-out", default=None, metavar="FILE",
                     help="with --sensor-plane: write rows 'x,y,max,min,|H1|,|H2|' over the last period to FILE")
+    ap.add_argument("--array", default=None, metavar="NY,NZ",
+                    help="with --sensor-plane: split the source face into NY x NZ elements (sources.SourceArray) with delays that focus on --focus")
+    ap.add_argument("--focus", default=None, metavar="X,Y,Z", help="focal point of --array in m (default: the centre of the box)")
     a = ap.parse_args()
+    if a.array and not a.sensor_plane:
+        ap.error("--array needs --sensor-plane")
+    if a.focus and not a.array:
+        ap.error("--focus needs --array")
     if a.peak_out and not a.sensor_plane:
         ap.error("--peak-out needs --sensor-plane")
 
@@ -101,8 +109,19 @@ def main():
         print(f"Number of steps: {nstep}", flush=True)
         print(f"Number of steps per period: {step_per_period}", flush=True)
         print(f"Number of degrees-of-freedom: {mesh.ndofs_global}", flush=True)
+    source = None
+    if a.array:
+        src = fusgpu_loader.submodule("sources")
+        ny, nz = (int(v) for v in a.array.split(","))
+        focus = np.array([float(v) for v in a.focus.split(",")] if a.focus else [0.5 * L] * 3)
+        # the elements split the face by the (y, z) of the facet centroids; their centres lie on the bowl
+        centres = bowl(src.grid_centres(ny, nz, 0.0, (0.0, L), (0.0, L)))
+        source = src.SourceArray(src.grid_elements(ny, nz, (0.0, L), (0.0, L)), delay=src.focus_delays(centres, focus, speed_of_sound),
+                                 n_elements=ny * nz)
+        if rank == 0:
+            print(f"Array elements: {ny} x {nz}, focus: {tuple(float(v) for v in focus)}", flush=True)
     solver = nls.WesterveltSpectral3D(mesh, float_type, speed_of_sound, density, source_frequency, source_amplitude,
-                                      nonlinear_coefficient, attenuation_coefficient_dB, comm=comm, fused=not a.reference_sequence,
+                                      nonlinear_coefficient, attenuation_coefficient_dB, comm=comm, fused=not a.reference_sequence, source=source,
                                       in_kernel_geometry=True if (a.in_kernel_geometry or a.geometry == "kernel") else ("auto" if a.geometry == "auto" else False))
     solver.init()
 

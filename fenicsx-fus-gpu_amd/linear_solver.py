@@ -108,7 +108,7 @@ class LinearSpectral3D(StepGraphMixin):
     def __init__(self, mesh, float_type=np.float64, speed_of_sound=1500.0, density=1000.0,
                  source_frequency=0.5e6, source_amplitude=60000.0, comm=None, fused=True,
                  source_time="tn", overlap=True, halo_kernels=None, affine="auto", in_kernel_geometry="auto",
-                 halo_plan=None, defer_setup_exchange=False, reference_speed_of_sound=None, keep_G=False):
+                 halo_plan=None, defer_setup_exchange=False, reference_speed_of_sound=None, keep_G=False, source=None):
         """``speed_of_sound`` / ``density``: scalars, or one value per cell (heterogeneous medium: the DG0 material arrays of
         the reference's drivers, in the caller's cell order).  ``reference_speed_of_sound``: the c of the source term
         ``p0 w0 / c cos(w0 t)`` (cuda/demo_linear_box.py:515-530 uses the scalar of its homogeneous medium); default: the
@@ -117,7 +117,9 @@ class LinearSpectral3D(StepGraphMixin):
         from the 8 vertices of each cell (the reference's geometry is P1 everywhere, cuda/demo_nonlinear_bowl.py:317): -18 % per
         step and no 6 n^3-value-per-cell G array at config 3; ``False`` keeps the reference's G stream
         (numba-cpu/precompute.py:115-163), ``True`` forces the kernel form for any degree.  ``keep_G``: keep the G array on the
-        device although the apply does not read it (``solver.G_array``)."""
+        device although the apply does not read it (``solver.G_array``).  ``source``: a ``sources.SourceArray`` (phased array:
+        per-element amplitude, phase and delay, optionally a burst) in place of the one scalar waveform of ``source_value``;
+        bound to this rank's source facets here (``self.source``), ``None`` keeps every launch as it is."""
         self.mesh, self.P = mesh, mesh.P
         self.dt_np = np.dtype(float_type)
         self.tdt = _lib.torch_dtype(float_type)
@@ -162,6 +164,9 @@ class LinearSpectral3D(StepGraphMixin):
         self.detJ_f1, self.detJ_f2 = dF1_d, dF2_d
         self.fdm1, self.fdm2 = td(mesh.facet_dofmap(bd1)), td(mesh.facet_dofmap(bd2))
         self.nlocal, self.ndofs = mesh.nlocal, mesh.ndofs
+        # phased-array source (sources.py): the source-facet term through fus_facet_source_array_* with g = p0 w0 / c0 per element
+        self.source = None if source is None else source.bind(mesh, bd1, ft, dev, frequency=self.f0, scale=self.p0 * self.w0 / self.c0,
+                                                              coeff1=self.facet_coeff1, detJ=self.detJ_f1, dofmap=self.fdm1)
 
         # ---- operators --------------------------------------------------------------------------
         # affine cells (every box mesh of the reference's demos): opt into the constant-G fast path
@@ -254,13 +259,18 @@ class LinearSpectral3D(StepGraphMixin):
         axpy(A_RUNGE[i] * dt, self.kv, self.vn)
         tn = t + C_RUNGE[i] * dt
         copy(self.vn, self.ku)  # f0
-        fill(self.source_value(tn if self.source_time == "tn" else t), self.g)
+        ts = tn if self.source_time == "tn" else t
+        if self.source is None:
+            fill(self.source_value(ts), self.g)
         copy(self.un, self.u_n)
         copy(self.vn, self.v_n)
         fill(0.0, self.b)
 
         def facets():
-            self._mass_facet_stage(self.g, self.facet_coeff1, self.b, self.detJ_f1, self.fdm1)
+            if self.source is None:
+                self._mass_facet_stage(self.g, self.facet_coeff1, self.b, self.detJ_f1, self.fdm1)
+            else:  # the array's source facets alone (no set B): replaces filling g and its facet mass apply
+                ops.facet_source_terms(self.b, self.source, None, stage=self.source.stage_scalars(ts))
             self._mass_facet_stage(self.v_n, self.facet_coeff2, self.b, self.detJ_f2, self.fdm2)
 
         if self.halo is None:
@@ -283,17 +293,25 @@ class LinearSpectral3D(StepGraphMixin):
             "fus_rk4_stage",
         )
 
-    def _operator_fused(self, tn_or_t, u_n=None, v_n=None, scalars=None):
+    def _operator_fused(self, tn_or_t, u_n=None, v_n=None, scalars=None, stage_dev=None):
         """b += K(c2) u_n + facet terms; (u_n, v_n) default to the stage buffers (un, ku == v_n); the
         first stage of a step passes (u0, v0) themselves.  ``scalars``: device tensor the source value is read
-        from instead of being evaluated at ``tn_or_t`` (graph capture)."""
+        from instead of being evaluated at ``tn_or_t`` (graph capture); ``stage_dev``: the same for a phased-array source
+        (its fp64 stage block)."""
         u_n = self.un if u_n is None else u_n
         v_n = self.ku if v_n is None else v_n
-        gval = 0.0 if scalars is not None else self.source_value(tn_or_t)
+        if self.source is not None:
+            stage = None if stage_dev is not None else self.source.stage_scalars(tn_or_t)
 
-        def facets():  # M_f1(g c1) 1 + M_f2(c2) v_n in one launch (the reference fills g into a vector)
-            ops.facet_terms(self.b, (self.facet_coeff1, gval, None, 0.0, self.detJ_f1, self.fdm1),
-                            (v_n, self.facet_coeff2, self.detJ_f2, self.fdm2), scalars=scalars)
+            def facets():  # M_f1(g_e c1) 1 per element + M_f2(c2) v_n in one launch
+                ops.facet_source_terms(self.b, self.source, (v_n, self.facet_coeff2, self.detJ_f2, self.fdm2), stage=stage,
+                                       stage_dev=stage_dev)
+        else:
+            gval = 0.0 if scalars is not None else self.source_value(tn_or_t)
+
+            def facets():  # M_f1(g c1) 1 + M_f2(c2) v_n in one launch (the reference fills g into a vector)
+                ops.facet_terms(self.b, (self.facet_coeff1, gval, None, 0.0, self.detJ_f1, self.fdm1),
+                                (v_n, self.facet_coeff2, self.detJ_f2, self.fdm2), scalars=scalars)
 
         if self.halo is None:
             self.stiff(u_n, self.cell_coeff2, self.b, self.G, self.dofmap)
@@ -395,7 +413,8 @@ class LinearSpectral3D(StepGraphMixin):
         source values are read from ``self._scal[i]``."""
         for i in range(4):
             first, last = i == 0, i == 3
-            for _ in self._operator_fused(None, self.u0 if first else None, self.v0 if first else None, scalars=self._scal[i]):
+            for _ in self._operator_fused(None, self.u0 if first else None, self.v0 if first else None, scalars=self._scal[i],
+                                          stage_dev=self._sstage[i] if self.source is not None else None):
                 pass
             self._rk4_stage_kernel(*self._stage_args(i, dt))
 

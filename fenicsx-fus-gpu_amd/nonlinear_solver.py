@@ -37,7 +37,7 @@ class WesterveltSpectral3D(StepGraphMixin):
                  source_frequency=1.1e6, source_amplitude=None, nonlinear_coefficient=3.5,
                  attenuation_coefficient_dB=0.2, comm=None, source_time="tn", overlap=True, fused=False,
                  in_kernel_geometry="auto", uniform_ratio="auto", halo_plan=None, defer_setup_exchange=False,
-                 reference_speed_of_sound=None, reference_density=None, keep_G=False):
+                 reference_speed_of_sound=None, reference_density=None, keep_G=False, source=None):
         """``speed_of_sound``, ``density``, ``nonlinear_coefficient``, ``attenuation_coefficient_dB``: scalars, or one value per
         cell in the caller's cell order (the DG0 material arrays of cuda/demo_nonlinear_bowl.py:166-178 -- water / skull / ...).
         ``reference_speed_of_sound`` / ``reference_density``: the scalars of the source term and of the default source amplitude
@@ -46,7 +46,8 @@ class WesterveltSpectral3D(StepGraphMixin):
         medium); the default is the two-gather pass for every medium (faster since round 5, and what a heterogeneous medium needs anyway).
         ``in_kernel_geometry``: ``"auto"`` (default) -- the fused stage of degree >= 3 forms G in the cell kernel from the 8
         vertices of each (trilinear) cell and the G array is dropped unless ``keep_G``; ``False``: the reference's G stream;
-        the reference launch sequence (``fused=False``) always reads G."""
+        the reference launch sequence (``fused=False``) always reads G.  ``source``: a ``sources.SourceArray`` (phased array) in
+        place of the one waveform of ``source_values``, as ``LinearSpectral3D``; ``None`` keeps every launch as it is."""
         from .linear_solver import per_cell
 
         if comm is not None:  # an MPI.Comm (the reference's comm = MPI.COMM_WORLD) becomes the bootstrap of a NativeComm
@@ -101,6 +102,9 @@ class WesterveltSpectral3D(StepGraphMixin):
         self.fdm1 = torch.from_numpy(mesh.facet_dofmap(bd1)).to(dev)
         self.fdm2 = torch.from_numpy(mesh.facet_dofmap(bd2)).to(dev)
         self.nlocal, self.ndofs = mesh.nlocal, mesh.ndofs
+        # phased-array source (sources.py): g = 2 p0 w0 / c0 per element and its derivative through fus_facet_source_array_*
+        self.source = None if source is None else source.bind(mesh, bd1, ft, dev, frequency=self.f0, scale=2.0 * self.p0 * self.w0 / self.c0,
+                                                              coeff1=self.fc1_1, coeff2=self.fc2_1, detJ=self.dF1, dofmap=self.fdm1)
         self.stiff = ops.stiffness_operator(P, D.flatten(), ft)
         # detJ never changes in the life of a solver: the reference-sequence stage applies the cell mass operator twice per stage
         # with it (cuda/demo_nonlinear_bowl.py:612-616, 630-632) -- streamed from a row-ordered copy instead of gathered
@@ -216,10 +220,13 @@ class WesterveltSpectral3D(StepGraphMixin):
             "fus_rk4_stage_nl2",
         )
 
-    def _operator_fused(self, ts, u_n=None, v_n=None, scalars=None):
+    def _operator_fused(self, ts, u_n=None, v_n=None, scalars=None, stage_dev=None):
         u_n = self.un if u_n is None else u_n
         v_n = self.ku if v_n is None else v_n  # ku == v_n
-        gv, dgv = (0.0, 0.0) if scalars is not None else self.source_values(ts)  # scalars: (g, dg) in device memory
+        if self.source is None:
+            gv, dgv = (0.0, 0.0) if scalars is not None else self.source_values(ts)  # scalars: (g, dg) in device memory
+        else:
+            stage = None if stage_dev is not None else self.source.stage_scalars(ts)  # stage_dev: the array's block in device memory
 
         single = self.kappa is not None  # one gather: the cell pass is K(c3) w, w = u_n + kappa v_n
         w_n = self.w
@@ -231,6 +238,9 @@ class WesterveltSpectral3D(StepGraphMixin):
                 self.cell_fused.stiffness_only(u_n, v_n, c3, c4, self.b, G_, dm_)
 
         def facets():  # M_f1(fc1_1 g + fc2_1 dg) 1 + M_f2(fc2_2) v_n in one launch
+            if self.source is not None:  # g, dg per element
+                ops.facet_source_terms(self.b, self.source, (v_n, self.fc2_2, self.dF2, self.fdm2), stage=stage, stage_dev=stage_dev)
+                return
             ops.facet_terms(self.b, (self.fc1_1, gv, self.fc2_1, dgv, self.dF1, self.fdm1), (v_n, self.fc2_2, self.dF2, self.fdm2),
                             scalars=scalars)
 
@@ -271,9 +281,11 @@ class WesterveltSpectral3D(StepGraphMixin):
         axpy(A_RUNGE[i] * dt, self.kv, self.vn)
         tn = t + C_RUNGE[i] * dt
         copy(self.vn, self.ku)
-        gv, dgv = self.source_values(tn if self.source_time == "tn" else t)
-        fill(gv, self.g)
-        fill(dgv, self.dg)
+        ts = tn if self.source_time == "tn" else t
+        if self.source is None:
+            gv, dgv = self.source_values(ts)
+            fill(gv, self.g)
+            fill(dgv, self.dg)
         copy(self.un, self.u_n)
         copy(self.vn, self.v_n)
         ops.square(self.vn, self.w_n)
@@ -292,8 +304,11 @@ class WesterveltSpectral3D(StepGraphMixin):
         self.stiff(self.u_n, self.cc3, self.b, self.G, self.dofmap)
         self.stiff(self.v_n, self.cc4, self.b, self.G, self.dofmap)
         self.mass_cell(self.w_n, self.cc5, self.b, self.detJ, self.dofmap)
-        self.mass_facet(self.g, self.fc1_1, self.b, self.dF1, self.fdm1)
-        self.mass_facet(self.dg, self.fc2_1, self.b, self.dF1, self.fdm1)
+        if self.source is None:
+            self.mass_facet(self.g, self.fc1_1, self.b, self.dF1, self.fdm1)
+            self.mass_facet(self.dg, self.fc2_1, self.b, self.dF1, self.fdm1)
+        else:  # the array's g and dg terms in one launch (no set B)
+            ops.facet_source_terms(self.b, self.source, None, stage=self.source.stage_scalars(ts))
         self.mass_facet(self.v_n, self.fc2_2, self.b, self.dF2, self.fdm2)
         if self.halo is not None:
             self.halo.rev(self.b)
@@ -324,7 +339,8 @@ class WesterveltSpectral3D(StepGraphMixin):
     def _graph_step_body(self, dt):
         for i in range(4):
             first, last = i == 0, i == 3
-            for _ in self._operator_fused(None, self.u0 if first else None, self.v0 if first else None, scalars=self._scal[i]):
+            for _ in self._operator_fused(None, self.u0 if first else None, self.v0 if first else None, scalars=self._scal[i],
+                                          stage_dev=self._sstage[i] if self.source is not None else None):
                 pass
             self._stage_vector_kernel(*self._stage_args(i, dt))
 

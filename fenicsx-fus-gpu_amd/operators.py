@@ -618,6 +618,69 @@ def facet_terms(y, source, field, scalars=None):
     )
 
 
+def facet_source_terms(y, bound_array, field, stage=None, stage_dev=None):
+    """``facet_terms`` with a phased-array source (csrc/source_array.hpp, ``fus_facet_source_array_*``):
+
+        bound_array  a ``sources.BoundSourceArray``: per source facet its element and the set-A tensors (c1, c2, detJ, dofmap)
+                     y += M_f(g_e c1 + dg_e c2) 1,  g_e / dg_e the value of each facet's element at the stage time
+        field        (x, c, detJ_f, facet_dofmap) or None      y += M_f(c) x  (the absorbing term; None: no set B)
+
+    The stage block ``{t, w0, A, f0, alpha, D}`` (fp64) is ``stage`` (host, ``bound_array.stage_scalars(t)``: copied into
+    the launch) or ``stage_dev`` (a float64 device tensor read by the kernel, ``fus_facet_source_array_dev_*``: a captured
+    hipGraph replays with new stage times).  Exactly one of them is given."""
+    ba = bound_array
+    dt = y.dtype if isinstance(y, torch.Tensor) else None
+    _req(y, dt, "y")
+    if ba.dtype != dt:
+        raise TypeError(f"the source array was bound for {ba.dtype}, y is {dt}")
+    nA = ba.nfacets
+    if nA:
+        for name, t in (("coeff1", ba.coeff1), ("detJ_source", ba.detJ)):
+            _req(t, dt, name)
+        if ba.coeff2 is not None:
+            _req(ba.coeff2, dt, "coeff2")
+        _req(ba.dofmap, torch.int32, "source dofmap")
+        _req(ba.element_of_facet, torch.int32, "element_of_facet")
+        for name, t in (("amplitude", ba.amplitude), ("phase", ba.phase), ("delay", ba.delay)):
+            _req(t, torch.float64, name)
+        if ba.detJ.shape != ba.dofmap.shape or ba.coeff1.numel() != nA or ba.dofmap.shape[0] != nA:
+            raise ValueError("source facet arrays: detJ must have the dofmap's shape, one constant and one element id per facet")
+    nB = 0
+    if field is not None:
+        xB, cB, dB, dmB = field
+        for name, t in (("x", xB), ("c", cB), ("detJ_field", dB)):
+            _req(t, dt, name)
+        _req(dmB, torch.int32, "field dofmap")
+        nB = dmB.shape[0]
+        if nB and (dB.shape != dmB.shape or cB.numel() != nB):
+            raise ValueError("facet arrays: detJ must have the dofmap's shape, one constant per facet")
+        if nA and nB and ba.dofmap.shape[1] != dmB.shape[1]:
+            raise ValueError("both facet sets must have the same number of dofs per facet")
+    if nA + nB == 0:
+        return
+    if (stage is None) == (stage_dev is None):
+        raise ValueError("facet_source_terms: give exactly one of stage (host) and stage_dev (device)")
+    N = ba.dofmap.shape[1] if nA else dmB.shape[1]
+    pA = lambda t: t.data_ptr() if (nA and t is not None) else None  # noqa: E731
+    pB = lambda t: t.data_ptr() if nB else None  # noqa: E731
+    args = [y.data_ptr(), pA(ba.coeff1), pA(ba.coeff2), pA(ba.detJ), pA(ba.dofmap), pA(ba.element_of_facet), int(nA),
+            pA(ba.amplitude), pA(ba.phase), pA(ba.delay), int(ba.n_elements)]
+    args += [pB(xB), pB(cB), pB(dB), pB(dmB)] if nB else [None] * 4
+    args += [int(nB), int(N)]
+    if stage_dev is not None:
+        _req(stage_dev, torch.float64, "stage_dev")
+        if stage_dev.numel() < 6:
+            raise ValueError("stage_dev must hold {t, w0, A, f0, alpha, D}")
+        fn = getattr(_lib.load(), f"fus_facet_source_array_dev_{_lib.suffix(dt)}")
+        _lib.check(fn(*args, stage_dev.data_ptr(), _lib.stream_ptr()), "fus_facet_source_array_dev")
+        return
+    st = np.ascontiguousarray(np.asarray(stage, dtype=np.float64).reshape(-1))
+    if st.size < 6:
+        raise ValueError("stage must hold {t, w0, A, f0, alpha, D}")
+    fn = getattr(_lib.load(), f"fus_facet_source_array_{_lib.suffix(dt)}")
+    _lib.check(fn(*args, st.ctypes.data, _lib.stream_ptr()), "fus_facet_source_array")
+
+
 # ---------------------------------------------------------------------- stiffness
 class _StiffnessOperator(_Launchable):
     """Returned by ``stiffness_operator``; callable both ways."""

@@ -1,0 +1,270 @@
+"""
+Phased-array sources: every source facet belongs to an element with its own amplitude factor, phase and delay, and the
+array may fire a tone burst instead of a continuous wave (csrc/source_array.hpp, ``fus_facet_source_array_*``).
+
+The solvers drive the source facets with one waveform, ``g(t) = A W(t) cos(w0 t)`` (``LinearSpectral3D.source_value``,
+``WesterveltSpectral3D.source_values``).  A ``SourceArray`` assigns each source facet an element id ``e`` in ``[0, E)``
+(or -1: inactive) and, with ``s = t - tau_e``,
+
+    g_e(t) = a_e A Env(s) cos(w0 s + phi_e)          Env = W(s) (continuous wave)  or  W(s) W(D - s) (burst of duration D)
+
+with the solvers' ramp ``W`` (4 periods).  A one-element array with ``a = 1, phi = 0, tau = 0, D = None`` is the scalar
+source.  Electronic focusing, steering, phase correction through a skull and apodisation are choices of ``phi`` / ``tau`` / ``a``:
+
+    arr = SourceArray(element_of_facet=ring_id, delay=focus_delays(centres, focus, 1500.0))
+    solver = LinearSpectral3D(mesh, source=arr)          # or WesterveltSpectral3D(..., source=arr)
+
+``element_of_facet`` is a callable from facet centroids ``[m, 3]`` to ids (what a partitioned run needs: each rank binds
+its own facets and the assignment by position agrees across ranks) or an int array aligned with the rows of
+``mesh.boundary_facets([source_tag])``.
+"""
+
+from __future__ import annotations
+
+from dataclasses import dataclass
+
+import numpy as np
+
+ALPHA = 4.0  # ramp length in periods (linear_solver.source_value, nonlinear_solver.source_values)
+STAGE_WORDS = 6  # t, w0, A, f0, alpha, D  (csrc/source_array.hpp SourceStage)
+
+
+def _window(s, f0, alpha=ALPHA):
+    """W(s) and W'(s) (arrays), the expressions of the solvers' source terms; 0 for s <= 0."""
+    s = np.asarray(s, dtype=np.float64)
+    T = 1.0 / f0
+    ramp = (s > 0.0) & (s < T * alpha)
+    w = np.where(s >= T * alpha, 1.0, 0.0)
+    dw = np.zeros_like(s)
+    if ramp.any():
+        sr = s[ramp]
+        w[ramp] = 0.5 * (1.0 - np.cos(f0 * np.pi * sr / alpha))
+        dw[ramp] = 0.5 * np.pi * f0 / alpha * np.sin(f0 * np.pi * sr / alpha)
+    return w, dw
+
+
+def facet_centroids(mesh, facets):
+    """``[m, 3]`` centroids of the boundary facets ``facets`` (``(cell, local facet)`` rows): the mean of the facet's four
+    vertices, from ``x_dofs`` / ``x_g`` (any mesh the solvers take: ``BoxMesh``, ``dolfinx_adaptor.ArrayMesh``)."""
+    from .precompute import HEX_FACET_AXIS_SIDE
+
+    bd = np.asarray(facets).reshape(-1, 2)
+    if bd.shape[0] == 0:
+        return np.zeros((0, 3))
+    # vertex v = vx + 2 vy + 4 vz (precompute.tabulate_hex_p1_gradients): facet (axis, side) holds the four with bit ``axis`` = side
+    verts = np.array([[v for v in range(8) if (v >> axis) & 1 == side] for axis, side in HEX_FACET_AXIS_SIDE])
+    xg = np.asarray(mesh.x_g, dtype=np.float64)
+    xd = np.asarray(mesh.x_dofs)
+    return xg[xd[bd[:, 0][:, None], verts[bd[:, 1]]]].mean(axis=1)
+
+
+def _per_element(value, E, name):
+    a = np.asarray(value, dtype=np.float64)
+    if a.ndim == 0:
+        return np.full(E, float(a))
+    if a.shape != (E,):
+        raise ValueError(f"{name}: a scalar or one value per element ({E}), got shape {a.shape}")
+    if not np.all(np.isfinite(a)):
+        raise ValueError(f"{name}: values must be finite")
+    return np.ascontiguousarray(a)
+
+
+class SourceArray:
+    """The elements of a phased array and what each facet of the source set belongs to (see the module docstring).
+
+    ``amplitude`` / ``phase`` (radians) / ``delay`` (seconds): scalars or one value per element; ``duration``: the burst
+    length ``D`` in seconds (at least two ramps, ``2 alpha / f0``, checked when bound) or ``None`` (continuous wave);
+    ``n_elements``: ``E`` (default: the length of an array parameter, else the largest id + 1)."""
+
+    def __init__(self, element_of_facet, amplitude=1.0, phase=0.0, delay=0.0, duration=None, n_elements=None):
+        self.element_of_facet = element_of_facet
+        if not callable(element_of_facet):
+            ids = np.asarray(element_of_facet)
+            if ids.ndim != 1 or (ids.size and not np.issubdtype(ids.dtype, np.integer)):
+                raise ValueError("element_of_facet: a callable of the facet centroids or a 1-D int array")
+            self.element_of_facet = ids.astype(np.int64)
+        E = n_elements
+        if E is None:
+            lens = {np.size(v) for v in (amplitude, phase, delay) if np.ndim(v) > 0}
+            if len(lens) > 1:
+                raise ValueError(f"per-element parameters of different lengths {sorted(lens)}")
+            if lens:
+                E = lens.pop()
+            elif not callable(self.element_of_facet):
+                E = int(self.element_of_facet.max()) + 1 if self.element_of_facet.size else 1
+            else:
+                E = 1
+        E = int(E)
+        if E < 1:
+            raise ValueError(f"n_elements must be >= 1, got {E}")
+        self.n_elements = E
+        self.amplitude = _per_element(amplitude, E, "amplitude")
+        self.phase = _per_element(phase, E, "phase")
+        self.delay = _per_element(delay, E, "delay")
+        if duration is not None:
+            duration = float(duration)
+            if not (np.isfinite(duration) and duration > 0.0):
+                raise ValueError(f"duration must be a positive number of seconds or None, got {duration}")
+        self.duration = duration
+
+    # -- host evaluation -----------------------------------------------------------------------
+    def check_duration(self, frequency, alpha=ALPHA):
+        if self.duration is not None and self.duration < 2.0 * alpha / float(frequency):
+            raise ValueError(f"duration {self.duration} s is shorter than the two ramps of the burst ({2.0 * alpha / float(frequency)} s)")
+
+    def values(self, t, frequency, scale, alpha=ALPHA):
+        """Host ``(g_e(t), dg_e/dt)``, ``[E]`` each, for carrier ``frequency`` and source constant ``scale`` (``A``)."""
+        f0 = float(frequency)
+        w0 = 2.0 * np.pi * f0
+        s = float(t) - self.delay
+        env, denv = _window(s, f0, alpha)
+        if self.duration is not None:
+            w2, dw2 = _window(self.duration - s, f0, alpha)
+            env, denv = env * w2, denv * w2 - env * dw2
+        a = self.amplitude * float(scale)
+        cs, sn = np.cos(w0 * s + self.phase), np.sin(w0 * s + self.phase)
+        return env * a * cs, denv * a * cs - env * a * w0 * sn
+
+    def stage_scalars(self, t, frequency, scale, alpha=ALPHA):
+        """The fp64 stage block ``{t, w0, A, f0, alpha, D}`` of the kernel (``D = 0``: continuous wave)."""
+        f0 = float(frequency)
+        return np.array([float(t), 2.0 * np.pi * f0, float(scale), f0, float(alpha), self.duration or 0.0], dtype=np.float64)
+
+    def assign(self, mesh, facets):
+        """Element id of every row of ``facets`` (int32), validated against ``[-1, E)``."""
+        bd = np.asarray(facets).reshape(-1, 2)
+        if callable(self.element_of_facet):
+            ids = np.asarray(self.element_of_facet(facet_centroids(mesh, bd))).reshape(-1)
+            if ids.size and not np.issubdtype(ids.dtype, np.integer):
+                raise ValueError("element_of_facet(centroids) must return integer ids")
+        else:
+            ids = self.element_of_facet
+        if ids.shape != (bd.shape[0],):
+            raise ValueError(f"element_of_facet: {ids.shape[0]} ids for {bd.shape[0]} source facets")
+        if ids.size and (ids.min() < -1 or ids.max() >= self.n_elements):
+            raise ValueError(f"element ids must lie in [-1, {self.n_elements}), got [{ids.min()}, {ids.max()}]")
+        return np.ascontiguousarray(ids.astype(np.int32))
+
+    def bind(self, mesh, facets, dtype, device, frequency=None, scale=None, coeff1=None, coeff2=None, detJ=None, dofmap=None):
+        """Upload the element table for this rank's source facets ``facets`` (``mesh.boundary_facets([source_tag])``).
+        ``frequency`` / ``scale``: the carrier and the source constant ``A`` of the solver; ``coeff1`` / ``coeff2`` / ``detJ``
+        / ``dofmap``: the set-A tensors of the facet launch (``dofmap`` default: ``mesh.facet_dofmap(facets)``)."""
+        import torch
+
+        from . import _lib
+
+        ids = self.assign(mesh, facets)
+        if frequency is not None:
+            self.check_duration(frequency)
+        td = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(device)  # noqa: E731
+        if dofmap is None:
+            dofmap = td(np.asarray(mesh.facet_dofmap(np.asarray(facets).reshape(-1, 2)), dtype=np.int32))
+        return BoundSourceArray(self, _lib.torch_dtype(dtype), td(ids), td(self.amplitude), td(self.phase), td(self.delay),
+                                None if frequency is None else float(frequency), None if scale is None else float(scale),
+                                coeff1, coeff2, detJ, dofmap, ids)
+
+
+@dataclass
+class BoundSourceArray:
+    """A ``SourceArray`` on the device for one rank's source facets: what ``operators.facet_source_terms`` launches with."""
+
+    array: SourceArray
+    dtype: object  # torch dtype of the field
+    element_of_facet: object  # int32 [m]
+    amplitude: object  # float64 [E]
+    phase: object
+    delay: object
+    frequency: float | None
+    scale: float | None
+    coeff1: object = None  # T [m]: cA1 (facet_coeff1 / fc1_1)
+    coeff2: object = None  # T [m] or None: cA2 (fc2_1 of the Westervelt solver)
+    detJ: object = None  # T [m, n^2]
+    dofmap: object = None  # int32 [m, n^2]
+    ids: np.ndarray = None  # host copy of element_of_facet
+
+    @property
+    def n_elements(self):
+        return self.array.n_elements
+
+    @property
+    def nfacets(self):
+        return int(self.element_of_facet.shape[0])
+
+    def values(self, t):
+        return self.array.values(t, self.frequency, self.scale)
+
+    def stage_scalars(self, t):
+        return self.array.stage_scalars(t, self.frequency, self.scale)
+
+
+# -- geometry helpers --------------------------------------------------------------------------
+def _points(a, name):
+    p = np.asarray(a, dtype=np.float64)
+    if p.ndim == 1 and p.size == 3:
+        p = p[None, :]
+    if p.ndim != 2 or p.shape[1] != 3:
+        raise ValueError(f"{name}: [E, 3] points, got shape {p.shape}")
+    return p
+
+
+def focus_delays(centres, focus, c):
+    """Delays that focus the elements at ``centres`` [E, 3] on ``focus`` through a medium of speed ``c``: the farthest element
+    fires first (delay 0) and every wavefront reaches the focus at the same time, ``tau_e = (max_j d_j - d_e) / c``."""
+    d = np.linalg.norm(_points(centres, "centres") - np.asarray(focus, dtype=np.float64).reshape(1, 3), axis=1)
+    return (d.max() - d) / float(c)
+
+
+def focus_phases(centres, focus, c, f):
+    """The continuous-wave equivalent of ``focus_delays`` at frequency ``f``: ``phi_e = -2 pi f tau_e``, wrapped to (-pi, pi]."""
+    phi = -2.0 * np.pi * float(f) * focus_delays(centres, focus, c)
+    return np.pi - np.mod(np.pi - phi, 2.0 * np.pi)
+
+
+def steer_delays(centres, direction, c):
+    """Delays that steer a plane wave along ``direction``: ``tau_e = (x_e . k - min_j x_j . k) / c``, k the unit direction."""
+    k = np.asarray(direction, dtype=np.float64).reshape(3)
+    nk = np.linalg.norm(k)
+    if nk == 0.0:
+        raise ValueError("direction must be non-zero")
+    proj = _points(centres, "centres") @ (k / nk)
+    return (proj - proj.min()) / float(c)
+
+
+def element_centres(mesh, facets, ids):
+    """``[E, 3]`` centre of each element on ONE rank: the mean of its facets' centroids (E = largest id + 1; NaN for an element
+    without facets).  A partitioned run computes the centres from the global layout instead."""
+    ids = np.asarray(ids).reshape(-1)
+    cen = facet_centroids(mesh, facets)
+    if cen.shape[0] != ids.size:
+        raise ValueError(f"{ids.size} ids for {cen.shape[0]} facets")
+    E = int(ids.max()) + 1 if ids.size else 0
+    out = np.full((E, 3), np.nan)
+    act = ids >= 0
+    cnt = np.bincount(ids[act], minlength=E).astype(np.float64)
+    for a in range(3):
+        s = np.bincount(ids[act], weights=cen[act, a], minlength=E)
+        with np.errstate(invalid="ignore", divide="ignore"):
+            out[:, a] = np.where(cnt > 0, s / np.maximum(cnt, 1), np.nan)
+    return out
+
+
+def grid_elements(ny, nz, y_range, z_range):
+    """``element_of_facet`` callable of a rectangular ``ny x nz`` split of a face normal to x: element ``j nz + k`` holds the
+    facets whose centroid lies in cell (j, k) of the ``y_range`` x ``z_range`` grid."""
+    (y0, y1), (z0, z1) = y_range, z_range
+
+    def ids(cen):
+        j = np.clip(np.floor((cen[:, 1] - y0) / (y1 - y0) * ny), 0, ny - 1).astype(np.int64)
+        k = np.clip(np.floor((cen[:, 2] - z0) / (z1 - z0) * nz), 0, nz - 1).astype(np.int64)
+        return j * nz + k
+
+    return ids
+
+
+def grid_centres(ny, nz, x, y_range, z_range):
+    """``[ny nz, 3]`` centres of the elements of ``grid_elements`` on the plane ``x``."""
+    (y0, y1), (z0, z1) = y_range, z_range
+    yc = y0 + (np.arange(ny) + 0.5) * (y1 - y0) / ny
+    zc = z0 + (np.arange(nz) + 0.5) * (z1 - z0) / nz
+    Y, Z = np.meshgrid(yc, zc, indexing="ij")
+    return np.stack([np.full(Y.size, float(x)), Y.reshape(-1), Z.reshape(-1)], axis=1)

@@ -7,7 +7,9 @@ overlap their tails and graph nodes do not).
 Every launch of a fused step takes fixed device pointers and constants except the source values g(t),
 dg/dt of the boundary-facet terms; with ``fus_facet_terms_dev_*`` those are read from device memory, so
 the step is captured once (``torch.cuda.CUDAGraph`` = hipStreamBeginCapture / hipGraphLaunch) and
-replayed with one 16-byte-per-stage device copy of the step's source values.
+replayed with one 16-byte-per-stage device copy of the step's source values.  A solver with a phased-array source
+(``self.source``, sources.py) reads a fp64 stage block per stage instead (``fus_facet_source_array_dev_*``): ``_sstage``
+[4, 6] beside ``_scal``, rewritten before each replay in its place.
 
 The reference drives every launch from Python (cuda/demo_linear_box.py:487-566: 12 launches + 5 host
 syncs per stage); this is its launch-bound regime taken to one graph launch per step.
@@ -27,7 +29,8 @@ class StepGraphMixin:
     """Adds ``rk4_graph`` to a solver that provides
 
     ``_graph_state()``        the tensors a step mutates (saved / restored around the warm-up step)
-    ``_graph_step_body(dt)``  the launches of one fused step, source values read from ``self._scal[i]``
+    ``_graph_step_body(dt)``  the launches of one fused step, source values read from ``self._scal[i]`` (a phased-array
+                              source: its stage blocks from ``self._sstage[i]``)
     ``_graph_scalars(t)``     ``(s1, s2)`` of a stage evaluated at time ``t``
     ``_graph_enter()`` / ``_graph_exit()``   what ``rk4`` does before / after its step loop
     """
@@ -73,19 +76,26 @@ class StepGraphMixin:
         rows, ends = [], []
         if sensors is not None:
             sensors.expect_steps(t, tf, dt, max_steps, record_from)
+        src = getattr(self, "source", None)
         while t < tf and (max_steps is None or len(rows) < max_steps) and min(dt, tf - t) == dt:
-            rows.append([self._graph_scalars(t + C_RUNGE[i] * dt if self.source_time == "tn" else t) for i in range(4)])
+            ts = [t + C_RUNGE[i] * dt if self.source_time == "tn" else t for i in range(4)]
+            rows.append([self._graph_scalars(x) for x in ts] if src is None else [src.stage_scalars(x) for x in ts])
             t += dt
             ends.append(t)
         if rows:
             if not hasattr(self, "_graphs"):
                 self._graphs = {}
                 self._scal = torch.zeros((4, 2), dtype=self.tdt, device=self.dev)
-            table = torch.from_numpy(np.asarray(rows, dtype=np.float64).astype(self.tdt_np)).to(self.dev)
+                if src is not None:
+                    self._sstage = torch.zeros((4, len(rows[0][0])), dtype=torch.float64, device=self.dev)
+            if src is None:
+                table, slot = torch.from_numpy(np.asarray(rows, dtype=np.float64).astype(self.tdt_np)).to(self.dev), self._scal
+            else:  # the stage blocks stay fp64 for fp32 fields too
+                table, slot = torch.from_numpy(np.asarray(rows, dtype=np.float64)).to(self.dev), self._sstage
             graph = self._step_graph(dt)
             self._graph_enter()
             for k in range(len(rows)):
-                self._scal.copy_(table[k])
+                slot.copy_(table[k])
                 graph.replay()
                 if sensors is not None and ends[k] > rf and not sensors.full:
                     sensors.record(self.u0, ends[k])

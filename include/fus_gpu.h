@@ -54,7 +54,7 @@ extern "C" {
  *      fus_comm_health; the PEER blob identifies the exporting process by a random token and its device by PCI bus id.
  *      Added since without a bump (new symbols only): fus_mass_gather_plan_bytes / _build / _info, fus_mass_apply_gather_*,
  *      fus_mass_gather_plan_build_rows, fus_mass_gather_static_bytes / _build_* , fus_mass_apply_gather_static_*,
- *      fus_probe_eval_*.
+ *      fus_probe_eval_*, fus_facet_source_array_* / fus_facet_source_array_dev_*.
  * There are deliberately NO fus_cpu_* twins of the entry points (SURVEY.md 8b proposed them): a CPU path inside the
  * product would be a silent fallback; the CPU restatement of the reference is test infrastructure and lives outside the product tree.
  */
@@ -146,6 +146,40 @@ int fus_facet_terms_dev_f64(double* y, const double* cA1, const double* cA2, con
 int fus_facet_terms_dev_f32(float* y, const float* cA1, const float* cA2, const float* scalars, const float* detJA,
                             const int32_t* dmA, int64_t nentA, const float* xB, const float* cB, const float* detJB,
                             const int32_t* dmB, int64_t nentB, int ndof_per_entity, void* stream);
+
+/*
+ * Phased-array source facets (csrc/source_array.hpp): fus_facet_terms_* with a per-element source value instead of one
+ * scalar for the whole source set.  Source facet f belongs to element e = element_of_facet[f] in [0, nelem), or -1
+ * (inactive; the ids are NOT checked here, as dofmaps are not: sources.SourceArray validates them when it binds).  With
+ * the stage block {t, w0, A, f0, alpha, D} (fp64) and s = t - delay[e]:
+ *   g_e     = amplitude[e] A Env(s) cos(w0 s + phase[e])            dg_e = d g_e / dt (analytic)
+ *   W(s)    = 0 (s <= 0), 0.5 (1 - cos(pi f0 s / alpha)) (0 < s < alpha / f0), 1 (s >= alpha / f0)
+ *   Env(s)  = W(s) for D = 0 (continuous wave), W(s) W(D - s) for a burst of duration D > 0
+ *   set A:  y[dmA[f][i]] += (g_e cA1[f] + dg_e cA2[f]) detJA[f][i]      cA2 may be NULL; evaluated in fp64, rounded to T once
+ *   set B:  y[dmB[f][i]] += xB[dmB[f][i]] cB[f] detJB[f][i]          (as fus_facet_terms_*)
+ *   amplitude / phase / delay   double[nelem]  (device)       element_of_facet   int32[nentA]  (device)
+ *   stage   double[6]  HOST memory, copied into the launch (fus_facet_source_array_*), or DEVICE memory read by the kernel
+ *           (fus_facet_source_array_dev_*: a captured hipGraph replays with new stage times)
+ * The adds are float atomics (the launch may run next to a stiffness apply into the same y).  nentA = nentB = 0 is a no-op;
+ * nentA > 0 needs nelem >= 1; the plain variant also checks f0 > 0, alpha > 0, D >= 0.
+ * A one-element array with amplitude 1, phase 0, delay 0, D = 0 is the scalar source of fus_facet_terms_* for t >= 0.
+ */
+int fus_facet_source_array_f64(double* y, const double* cA1, const double* cA2, const double* detJA, const int32_t* dmA,
+                               const int32_t* element_of_facet, int64_t nentA, const double* amplitude, const double* phase,
+                               const double* delay, int64_t nelem, const double* xB, const double* cB, const double* detJB,
+                               const int32_t* dmB, int64_t nentB, int ndof_per_entity, const double* stage, void* stream);
+int fus_facet_source_array_f32(float* y, const float* cA1, const float* cA2, const float* detJA, const int32_t* dmA,
+                               const int32_t* element_of_facet, int64_t nentA, const double* amplitude, const double* phase,
+                               const double* delay, int64_t nelem, const float* xB, const float* cB, const float* detJB,
+                               const int32_t* dmB, int64_t nentB, int ndof_per_entity, const double* stage, void* stream);
+int fus_facet_source_array_dev_f64(double* y, const double* cA1, const double* cA2, const double* detJA, const int32_t* dmA,
+                                   const int32_t* element_of_facet, int64_t nentA, const double* amplitude, const double* phase,
+                                   const double* delay, int64_t nelem, const double* xB, const double* cB, const double* detJB,
+                                   const int32_t* dmB, int64_t nentB, int ndof_per_entity, const double* stage_dev, void* stream);
+int fus_facet_source_array_dev_f32(float* y, const float* cA1, const float* cA2, const float* detJA, const int32_t* dmA,
+                                   const int32_t* element_of_facet, int64_t nentA, const double* amplitude, const double* phase,
+                                   const double* delay, int64_t nelem, const float* xB, const float* cB, const float* detJB,
+                                   const int32_t* dmB, int64_t nentB, int ndof_per_entity, const double* stage_dev, void* stream);
 
 /*
  * Point sensors (csrc/probe.hpp) -- replaces the reference's per-step host evaluation of its collection window,

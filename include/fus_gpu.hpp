@@ -80,6 +80,12 @@ struct Abi<double> {
                    int64_t cap, int slot, double* pmax, double* pmin, double* hre, double* him, const double* coef, int H, void* s) {
     return fus_probe_eval_f64(u, cells, m, dm, nc, w, P, rec, cap, slot, pmax, pmin, hre, him, coef, H, s);
   }
+  static int source_array(double* y, const double* c1, const double* c2, const double* dA, const int32_t* dmA, const int32_t* eid, int64_t nA,
+                          const double* a, const double* ph, const double* tau, int64_t E, const double* xB, const double* cB, const double* dB,
+                          const int32_t* dmB, int64_t nB, int N, const double* stage, bool dev, void* s) {
+    return dev ? fus_facet_source_array_dev_f64(y, c1, c2, dA, dmA, eid, nA, a, ph, tau, E, xB, cB, dB, dmB, nB, N, stage, s)
+               : fus_facet_source_array_f64(y, c1, c2, dA, dmA, eid, nA, a, ph, tau, E, xB, cB, dB, dmB, nB, N, stage, s);
+  }
 };
 template <>
 struct Abi<float> {
@@ -106,6 +112,12 @@ struct Abi<float> {
   static int probe(const float* u, const int32_t* cells, int64_t m, const int32_t* dm, int64_t nc, const float* w, int P, float* rec,
                    int64_t cap, int slot, double* pmax, double* pmin, double* hre, double* him, const double* coef, int H, void* s) {
     return fus_probe_eval_f32(u, cells, m, dm, nc, w, P, rec, cap, slot, pmax, pmin, hre, him, coef, H, s);
+  }
+  static int source_array(float* y, const float* c1, const float* c2, const float* dA, const int32_t* dmA, const int32_t* eid, int64_t nA,
+                          const double* a, const double* ph, const double* tau, int64_t E, const float* xB, const float* cB, const float* dB,
+                          const int32_t* dmB, int64_t nB, int N, const double* stage, bool dev, void* s) {
+    return dev ? fus_facet_source_array_dev_f32(y, c1, c2, dA, dmA, eid, nA, a, ph, tau, E, xB, cB, dB, dmB, nB, N, stage, s)
+               : fus_facet_source_array_f32(y, c1, c2, dA, dmA, eid, nA, a, ph, tau, E, xB, cB, dB, dmB, nB, N, stage, s);
   }
 };
 
@@ -349,6 +361,44 @@ class PointProbe {
   const int32_t* dofmap_;
   int64_t ncells_;
   const T* weights_;
+};
+
+// Phased-array source facets (fus_facet_source_array_*): the source-facet term of one RK4 stage with a per-element amplitude,
+// phase and delay, and the absorbing term in the same launch.  Set A: ``eid`` [nA] (element of each facet, -1 = inactive,
+// validated by the caller), ``amplitude`` / ``phase`` / ``delay`` [E] (fp64), ``c1`` / ``c2`` [nA] (c2 may be null), ``detJ`` /
+// ``dofmap`` [nA][N].  Set B (optional): ``cB``, ``detJB``, ``dmB`` of nB facets.  All device arrays, caller-owned.
+template <typename T>
+class FacetSourceArray {
+ public:
+  FacetSourceArray(const T* c1, const T* c2, const T* detJ, const int32_t* dofmap, const int32_t* eid, int64_t nA, const double* amplitude,
+                   const double* phase, const double* delay, int64_t E, int N, const T* cB = nullptr, const T* detJB = nullptr,
+                   const int32_t* dmB = nullptr, int64_t nB = 0)
+      : c1_(c1), c2_(c2), detJ_(detJ), dm_(dofmap), eid_(eid), nA_(nA), a_(amplitude), ph_(phase), tau_(delay), E_(E), N_(N), cB_(cB),
+        detJB_(detJB), dmB_(dmB), nB_(nB) {
+    check_abi();
+  }
+  // y += set A at the stage block {t, w0, A, f0, alpha, D} (host memory) + set B applied to xB (ignored when nB == 0)
+  void operator()(T* y, const double* stage, const T* xB = nullptr, void* stream = nullptr) const { launch(y, stage, false, xB, stream); }
+  // the same with the stage block read from device memory by the kernel (hipGraph replay with new times)
+  void device_stage(T* y, const double* stage_dev, const T* xB = nullptr, void* stream = nullptr) const {
+    launch(y, stage_dev, true, xB, stream);
+  }
+
+ private:
+  void launch(T* y, const double* stage, bool dev, const T* xB, void* stream) const {
+    check(detail::Abi<T>::source_array(y, c1_, c2_, detJ_, dm_, eid_, nA_, a_, ph_, tau_, E_, xB, cB_, detJB_, dmB_, xB ? nB_ : 0, N_, stage,
+                                       dev, stream),
+          "fus_facet_source_array");
+  }
+  const T *c1_, *c2_, *detJ_;
+  const int32_t *dm_, *eid_;
+  int64_t nA_;
+  const double *a_, *ph_, *tau_;
+  int64_t E_;
+  int N_;
+  const T *cB_, *detJB_;
+  const int32_t* dmB_;
+  int64_t nB_;
 };
 
 }  // namespace fus_gpu
