@@ -13,17 +13,13 @@ The stage follows the reference's launch sequence through the reference-compatib
 
 from __future__ import annotations
 
-import os
-
 import numpy as np
 import torch
 
 from . import _lib
 from . import operators as ops
-from .linear_solver import A_RUNGE, B_RUNGE, C_RUNGE
-from .linear_solver import device_geometry
-from .sensors import record_schedule
-from .step_graph import StepGraphMixin
+from .gll import tabulate_1d
+from .solver_base import A_RUNGE, B_RUNGE, SpectralSolver3D, per_cell
 
 
 def compute_diffusivity_of_sound(frequency, speed, attenuationdB):
@@ -32,7 +28,7 @@ def compute_diffusivity_of_sound(frequency, speed, attenuationdB):
     return 2 * attenuationNp * speed**3 / frequency / frequency
 
 
-class WesterveltSpectral3D(StepGraphMixin):
+class WesterveltSpectral3D(SpectralSolver3D):
     def __init__(self, mesh, float_type=np.float64, speed_of_sound=1480.0, density=1000.0,
                  source_frequency=1.1e6, source_amplitude=None, nonlinear_coefficient=3.5,
                  attenuation_coefficient_dB=0.2, comm=None, source_time="tn", overlap=True, fused=False,
@@ -48,23 +44,13 @@ class WesterveltSpectral3D(StepGraphMixin):
         vertices of each (trilinear) cell and the G array is dropped unless ``keep_G``; ``False``: the reference's G stream;
         the reference launch sequence (``fused=False``) always reads G.  ``source``: a ``sources.SourceArray`` (phased array) in
         place of the one waveform of ``source_values``, as ``LinearSpectral3D``; ``None`` keeps every launch as it is."""
-        from .linear_solver import per_cell
-
-        if comm is not None:  # an MPI.Comm (the reference's comm = MPI.COMM_WORLD) becomes the bootstrap of a NativeComm
-            from .scatterer import as_comm
-
-            comm = as_comm(comm)
-        self.mesh, self.P = mesh, mesh.P
-        ft = np.dtype(float_type)
-        self.tdt_np = ft
-        self.tdt = _lib.torch_dtype(ft)
         c_cells, rho_cells = per_cell(speed_of_sound, mesh, "speed_of_sound"), per_cell(density, mesh, "density")
         beta_cells = per_cell(nonlinear_coefficient, mesh, "nonlinear_coefficient")
         att_cells = per_cell(attenuation_coefficient_dB, mesh, "attenuation_coefficient_dB")
+        bd1, bd2, D, G_d, detJ_d, (dF1_d, dF2_d) = self._init_common(mesh, float_type, comm, fused, source_time)
         self.f0 = float(source_frequency)
         self.w0 = 2 * np.pi * self.f0
-        src = mesh.boundary_facets([getattr(mesh, "source_tag", 2)])
-        pick = (lambda a: float(a[src[:, 0]].mean())) if src.shape[0] else (lambda a: float(a.mean()))
+        pick = (lambda a: float(a[bd1[:, 0]].mean())) if bd1.shape[0] else (lambda a: float(a.mean()))
         self.c0 = float(reference_speed_of_sound) if reference_speed_of_sound is not None else (
             float(speed_of_sound) if np.ndim(speed_of_sound) == 0 else pick(c_cells))
         self.rho0 = float(reference_density) if reference_density is not None else (
@@ -73,16 +59,7 @@ class WesterveltSpectral3D(StepGraphMixin):
         self.beta = float(beta_cells.mean())
         delta_cells = compute_diffusivity_of_sound(self.w0, c_cells, att_cells)
         self.delta = float(delta_cells.mean())
-        self.source_time = source_time
-        self.fused = bool(fused)
-        self.lean_stages = os.environ.get("FUS_RK4_LEAN", "1") != "0"  # the fused stage's vector pass: kinds 4-7 of csrc/rk4.hpp (_stage_args)
-        P, n = self.P, self.P + 1
-        dev = torch.device("cuda", torch.cuda.current_device())
-        self.dev = dev
-        nc = mesh.ncells
-        # tagged facet sets: source / absorbing (a structured box: its x = 0 / x = L faces; dolfinx_adaptor.ArrayMesh: facet tags)
-        bd1, bd2 = mesh.boundary_facets([getattr(mesh, "source_tag", 2)]), mesh.boundary_facets([getattr(mesh, "absorbing_tag", 3)])
-        D, G_d, detJ_d, (dF1_d, dF2_d) = device_geometry(mesh, P, ft, dev, (bd1, bd2))
+        P, n, dev, ft = self.P, self.P + 1, self.dev, self.tdt_np
         rho, c, beta, delta = rho_cells, c_cells, beta_cells, delta_cells
         td = lambda a: torch.from_numpy(np.ascontiguousarray(np.asarray(a, dtype=ft))).to(dev)  # noqa: E731
         # cuda/demo_nonlinear_bowl.py:357-374
@@ -102,25 +79,26 @@ class WesterveltSpectral3D(StepGraphMixin):
         self.fdm1 = torch.from_numpy(mesh.facet_dofmap(bd1)).to(dev)
         self.fdm2 = torch.from_numpy(mesh.facet_dofmap(bd2)).to(dev)
         self.nlocal, self.ndofs = mesh.nlocal, mesh.ndofs
+        # the fused stage's facet sets: M_f1(fc1_1 g + fc2_1 dg) 1 with (g, dg) = source_values(t), M_f2(fc2_2) v_n
+        self._source_set = (self.fc1_1, self.fc2_1, self.dF1, self.fdm1)
+        self._absorbing_set = (self.fc2_2, self.dF2, self.fdm2)
         # phased-array source (sources.py): g = 2 p0 w0 / c0 per element and its derivative through fus_facet_source_array_*
         self.source = None if source is None else source.bind(mesh, bd1, ft, dev, frequency=self.f0, scale=2.0 * self.p0 * self.w0 / self.c0,
                                                               coeff1=self.fc1_1, coeff2=self.fc2_1, detJ=self.dF1, dofmap=self.fdm1)
         self.stiff = ops.stiffness_operator(P, D.flatten(), ft)
         # detJ never changes in the life of a solver: the reference-sequence stage applies the cell mass operator twice per stage
         # with it (cuda/demo_nonlinear_bowl.py:612-616, 630-632) -- streamed from a row-ordered copy instead of gathered
-        self.mass_cell = ops.mass_operator(n**3, ft, static_detJ=not bool(fused))
+        self.mass_cell = ops.mass_operator(n**3, ft, static_detJ=not self.fused)
         self.mass_facet = ops.mass_operator(n * n, ft)
         self.axpy = ops.axpy(self.ndofs)
         self.halo = None
-        if comm is not None and comm.size > 1:
-            from .scatterer import HaloApply, scatter_forward
+        if self.comm is not None and self.comm.size > 1:
+            from .scatterer import HaloApply, scatter_forward, scatter_reverse
 
-            self.halo = HaloApply(mesh, self.stiff, comm, ft, overlap=overlap, plan=halo_plan)
-            mk = lambda: scatter_forward(comm, self.halo.owners_data, self.halo.ghosts_data, mesh.nlocal, ft)  # noqa: E731
+            self.halo = HaloApply(mesh, self.stiff, self.comm, ft, overlap=overlap, plan=halo_plan)
+            mk = lambda: scatter_forward(self.comm, self.halo.owners_data, self.halo.ghosts_data, mesh.nlocal, ft)  # noqa: E731
             self.fwd_u, self.fwd_v, self.fwd_w = self.halo.fwd, mk(), mk()
-            from .scatterer import scatter_reverse
-
-            self.rev_m = scatter_reverse(comm, self.halo.owners_data, self.halo.ghosts_data, mesh.nlocal, ft)
+            self.rev_m = scatter_reverse(self.comm, self.halo.owners_data, self.halo.ghosts_data, mesh.nlocal, ft)
         z = lambda: torch.zeros(self.ndofs, dtype=self.tdt, device=dev)  # noqa: E731
         (self.u, self.v, self.u0, self.v0, self.un, self.vn, self.ku, self.kv, self.u_n, self.v_n, self.w_n,
          self.g, self.dg, self.b, self.m, self.m0) = (z() for _ in range(16))
@@ -146,13 +124,8 @@ class WesterveltSpectral3D(StepGraphMixin):
         # any of them exchanges
         self._rev_w5 = None
         if self.halo is not None:
-            from .scatterer import scatter_reverse
-
             self._rev_w5 = scatter_reverse(self.halo.comm, self.halo.owners_data, self.halo.ghosts_data, self.nlocal, self.tdt_np)
-        self._setup = self.setup_schedule()
-        if not defer_setup_exchange:
-            for _ in self._setup:
-                pass
+        self._start_setup(defer_setup_exchange)
         # uniform ratio c4 / c3 (= delta / c^2: every homogeneous medium): K(c3) u + K(c4) v = K(c3)(u + kappa v),
         # so the cell pass CAN be one plain stiffness apply on w = u_n + kappa v_n, which the vector kernel writes (uniform_ratio=True)
         ratio = self.cc4 / self.cc3
@@ -160,11 +133,11 @@ class WesterveltSpectral3D(StepGraphMixin):
         # the decision (and kappa itself) must be the SAME on every rank -- a rank in single-gather mode forward-scatters
         # w where a neighbour in two-gather mode expects u_n, with matching counts, so nothing would hang and the result
         # would be silently wrong: min / max over all ranks.  cc3 / cc4 must not be edited after construction.
-        if comm is not None and getattr(comm, "size", 1) > 1 and getattr(comm, "_world_id", None) is None:
+        if self.comm is not None and getattr(self.comm, "size", 1) > 1 and getattr(self.comm, "_world_id", None) is None:
             import torch.distributed as dist
 
-            if hasattr(comm, "allgather_floats"):  # NativeComm: over its bootstrap (torch.distributed or MPI)
-                every = comm.allgather_floats([kmin, kmax])
+            if hasattr(self.comm, "allgather_floats"):  # NativeComm: over its bootstrap (torch.distributed or MPI)
+                every = self.comm.allgather_floats([kmin, kmax])
                 kmin, kmax = float(every[:, 0].min()), float(every[:, 1].max())
             elif dist.is_available() and dist.is_initialized():
                 on_gpu = dist.get_backend() == "nccl"
@@ -186,14 +159,20 @@ class WesterveltSpectral3D(StepGraphMixin):
         self.in_kernel_geometry = bool(in_kernel_geometry)
         if self.in_kernel_geometry and self.fused and not keep_G:
             self.G = None  # the fused stage does not read it (P = 6, 36^3 cells: 768 MB)
+        stiff, pair = self.stiff, self.cell_fused
         if self.in_kernel_geometry:
-            from .gll import tabulate_1d
-
             pts, wts, _ = tabulate_1d(P, ft)
             self.x_dofs = torch.from_numpy(np.ascontiguousarray(mesh.x_dofs)).to(dev)
             self.cell_fused_geom = ops.westervelt_cell_operator(P, D.flatten(), ft, geometry=(mesh.x_g, pts, wts))
             self.stiff_geom = ops.stiffness_operator(P, D.flatten(), ft, geometry=(self.x_dofs, mesh.x_g, pts, wts))
-        self.fc_src = torch.zeros_like(self.fc1_1)  # per-stage source-facet constants (fused mode)
+            stiff, pair = self.stiff_geom, self.cell_fused_geom
+        # the fused stage's cell pass, one of four: single gather (K(c3) w, w = u_n + kappa v_n) or two (K(c3) u_n + K(c4) v_n),
+        # each with the G array or G formed in the kernel (x_dofs rows travel in the G position)
+        self._percell = (self.cc3, self.cc4, self.x_dofs if self.in_kernel_geometry else self.G, self.dofmap)
+        if self.kappa is not None:
+            self._cell_pass = lambda u_n, v_n, c3, c4, G_, dm_: stiff(self.w, c3, self.b, G_, dm_)
+        else:
+            self._cell_pass = lambda u_n, v_n, c3, c4, G_, dm_: pair.stiffness_only(u_n, v_n, c3, c4, self.b, G_, dm_)
 
     def setup_schedule(self):
         if self.halo is not None:
@@ -204,61 +183,6 @@ class WesterveltSpectral3D(StepGraphMixin):
             yield "reverse"
             for sc, vec, wk in pending:
                 sc.end(vec, wk)
-
-    def init(self):
-        for t in (self.u, self.v, self.ku, self.kv):
-            ops.fill(0.0, t)
-
-    # -- fused stage: one cell pass + one vector pass ------------------------------------------------
-    def _stage_vector_kernel(self, bw, aw, new_step):
-        fn = getattr(_lib.load(), f"fus_rk4_stage_nl2_{_lib.suffix(self.tdt)}")
-        _lib.check(
-            fn(float(bw), float(aw), int(new_step), self.m0.data_ptr(), self.w2.data_ptr(), self.w5.data_ptr(),
-               self.b.data_ptr(), self.u.data_ptr(), self.v.data_ptr(), self.u0.data_ptr(), self.v0.data_ptr(),
-               self.ku.data_ptr(), self.un.data_ptr(), float(self.kappa or 0.0),
-               self.w.data_ptr() if self.w is not None else None, self.nlocal, self.ndofs, _lib.stream_ptr()),
-            "fus_rk4_stage_nl2",
-        )
-
-    def _operator_fused(self, ts, u_n=None, v_n=None, scalars=None, stage_dev=None):
-        u_n = self.un if u_n is None else u_n
-        v_n = self.ku if v_n is None else v_n  # ku == v_n
-        if self.source is None:
-            gv, dgv = (0.0, 0.0) if scalars is not None else self.source_values(ts)  # scalars: (g, dg) in device memory
-        else:
-            stage = None if stage_dev is not None else self.source.stage_scalars(ts)  # stage_dev: the array's block in device memory
-
-        single = self.kappa is not None  # one gather: the cell pass is K(c3) w, w = u_n + kappa v_n
-        w_n = self.w
-
-        def cells(c3, c4, G_, dm_):
-            if single:
-                self.stiff(w_n, c3, self.b, G_, dm_)
-            else:
-                self.cell_fused.stiffness_only(u_n, v_n, c3, c4, self.b, G_, dm_)
-
-        def facets():  # M_f1(fc1_1 g + fc2_1 dg) 1 + M_f2(fc2_2) v_n in one launch
-            if self.source is not None:  # g, dg per element
-                ops.facet_source_terms(self.b, self.source, (v_n, self.fc2_2, self.dF2, self.fdm2), stage=stage, stage_dev=stage_dev)
-                return
-            ops.facet_terms(self.b, (self.fc1_1, gv, self.fc2_1, dgv, self.dF1, self.fdm1), (v_n, self.fc2_2, self.dF2, self.fdm2),
-                            scalars=scalars)
-
-        percell = (self.cc3, self.cc4, self.G, self.dofmap)
-        if self.in_kernel_geometry:
-            def cells(c3, c4, xd_, dm_):  # noqa: F811
-                if single:
-                    self.stiff_geom(w_n, c3, self.b, xd_, dm_)  # x_dofs rows travel in the G position
-                else:
-                    self.cell_fused_geom.stiffness_only(u_n, v_n, c3, c4, self.b, xd_, dm_)
-
-            percell = (self.cc3, self.cc4, self.x_dofs, self.dofmap)
-        if self.halo is None:
-            cells(*percell)
-            facets()
-        else:
-            yield from self.halo.schedule(cells, percell, [(self.fwd_u, w_n if single else u_n), (self.fwd_v, v_n)],
-                                          [(self.halo.rev, self.b)], facets)
 
     def source_values(self, t):
         """g and dg/dt (cuda/demo_nonlinear_bowl.py:560-595)."""
@@ -273,15 +197,50 @@ class WesterveltSpectral3D(StepGraphMixin):
         dg = dwindow * a * np.cos(self.w0 * t) - window * a * self.w0 * np.sin(self.w0 * t)
         return g, dg
 
-    def _stage(self, i, t, dt):
+    def _source_scalars(self, t):
+        return self.source_values(t)
+
+    # -- fused stage: one cell pass + one vector pass ------------------------------------------------
+    def _cell_terms(self, u_n, v_n, facets):
+        """The cell pass chosen at construction into b, then ``facets()``; next to a halo the interior cells overlap the
+        exchange of (w or u_n, v_n) and the reverse scatter of b follows."""
+        cells = lambda *percell: self._cell_pass(u_n, v_n, *percell)  # noqa: E731
+        if self.halo is None:
+            cells(*self._percell)
+            facets()
+        else:
+            yield from self.halo.schedule(cells, self._percell, [(self.fwd_u, self.w if self.kappa is not None else u_n), (self.fwd_v, v_n)],
+                                          [(self.halo.rev, self.b)], facets)
+
+    def _vector_pass(self, bw, aw, new_step):
+        fn = getattr(_lib.load(), f"fus_rk4_stage_nl2_{_lib.suffix(self.tdt)}")
+        _lib.check(
+            fn(float(bw), float(aw), int(new_step), self.m0.data_ptr(), self.w2.data_ptr(), self.w5.data_ptr(),
+               self.b.data_ptr(), self.u.data_ptr(), self.v.data_ptr(), self.u0.data_ptr(), self.v0.data_ptr(),
+               self.ku.data_ptr(), self.un.data_ptr(), float(self.kappa or 0.0),
+               self.w.data_ptr() if self.w is not None else None, self.nlocal, self.ndofs, _lib.stream_ptr()),
+            "fus_rk4_stage_nl2",
+        )
+
+    def _fused_enter(self):
+        ops.fill(1.0, self.g)  # source enters through scaled facet constants
+        super()._fused_enter()
+        if self.kappa is not None:
+            ops.copy(self.u0, self.w)
+            self.axpy(self.kappa, self.v0, self.w)
+
+    def _graph_state(self):
+        return super()._graph_state() + ((self.w,) if self.w is not None else ())
+
+    # -- reference launch sequence (blocking scatters: never yields) ---------------------------------
+    def _stage_reference(self, i, t, dt):
         copy, fill, axpy = ops.copy, ops.fill, self.axpy
         copy(self.u0, self.un)
         copy(self.v0, self.vn)
         axpy(A_RUNGE[i] * dt, self.ku, self.un)
         axpy(A_RUNGE[i] * dt, self.kv, self.vn)
-        tn = t + C_RUNGE[i] * dt
         copy(self.vn, self.ku)
-        ts = tn if self.source_time == "tn" else t
+        ts = self._stage_time(t, i, dt)
         if self.source is None:
             gv, dgv = self.source_values(ts)
             fill(gv, self.g)
@@ -315,102 +274,4 @@ class WesterveltSpectral3D(StepGraphMixin):
         ops.pointwise_divide(self.b, self.m, self.kv)
         axpy(B_RUNGE[i] * dt, self.ku, self.u)
         axpy(B_RUNGE[i] * dt, self.kv, self.v)
-
-    # -- hipGraph replay (launch-bound meshes): step_graph.StepGraphMixin.rk4_graph ---------------------
-    def _graph_state(self):
-        return (self.u, self.v, self.u0, self.v0, self.ku, self.un, self.b) + ((self.w,) if self.w is not None else ())
-
-    def _graph_scalars(self, t):
-        return self.source_values(t)
-
-    def _graph_enter(self):
-        ops.fill(1.0, self.g)
-        ops.fill(0.0, self.b)
-        ops.copy(self.u, self.u0)
-        ops.copy(self.v, self.v0)
-        if self.kappa is not None:
-            ops.copy(self.u0, self.w)
-            self.axpy(self.kappa, self.v0, self.w)
-
-    def _graph_exit(self):
-        ops.copy(self.u0, self.u)
-        ops.copy(self.v0, self.v)
-
-    def _graph_step_body(self, dt):
-        for i in range(4):
-            first, last = i == 0, i == 3
-            for _ in self._operator_fused(None, self.u0 if first else None, self.v0 if first else None, scalars=self._scal[i],
-                                          stage_dev=self._sstage[i] if self.source is not None else None):
-                pass
-            self._stage_vector_kernel(*self._stage_args(i, dt))
-
-    def _stage_args(self, i, dt):
-        """``(bw, aw, kind)`` of the vector pass after stage ``i`` (csrc/rk4.hpp).  Default: the LEAN set 4, 5, 6, 7 with bw = b_runge[0] dt,
-        aw = a_runge[1] dt in all four passes (u's accumulator runs one pass ahead, 34 instead of 41 vector touches per linear step, 46
-        instead of 52 per Westervelt step; v differs from the reference's sequence in the rounding of one term); ``lean_stages = False``
-        (FUS_RK4_LEAN=0): kinds 2, 0, 0, 3, the reference's arithmetic operation for operation."""
-        if self.lean_stages:
-            return B_RUNGE[0] * dt, A_RUNGE[1] * dt, 4 + i
-        last = i == 3
-        return B_RUNGE[i] * dt, 0.0 if last else A_RUNGE[i + 1] * dt, 3 if last else (2 if i == 0 else 0)
-
-    def rk4(self, start_time, final_time, dt, max_steps=None, sensors=None, record_from=None):
-        """Advance from ``start_time`` to ``final_time``; returns ``(t, steps)``.  ``sensors`` / ``record_from``: as
-        ``LinearSpectral3D.rk4``."""
-        gen = self.rk4_schedule(start_time, final_time, dt, max_steps, sensors, record_from)
-        while True:
-            try:
-                next(gen)
-            except StopIteration as done:
-                self.check_halo_health("WesterveltSpectral3D.rk4")  # a failed exchange is an error, not a field (see LinearSpectral3D.rk4)
-                return done.value
-
-    def check_halo_health(self, what="halo exchange"):
-        if self.halo is not None:
-            self.halo.check_health(what)
-
-    def rk4_schedule(self, start_time, final_time, dt, max_steps=None, sensors=None, record_from=None):
-        """``rk4`` as a generator that yields whenever this rank has posted halo exchanges; returns ``(t, steps)``.  ``u`` /
-        ``v`` are valid only once it is exhausted; ``sensors`` observe the field mid-run (``LinearSpectral3D.rk4_schedule``)."""
-        t, step, tf = float(start_time), 0, float(final_time)
-        rf = -np.inf if record_from is None else float(record_from)
-        if sensors is not None:
-            sensors.expect_steps(t, tf, dt, max_steps, record_from)
-        if self.fused:
-            ops.fill(1.0, self.g)  # source enters through scaled facet constants
-            ops.fill(0.0, self.b)
-            ops.copy(self.u, self.u0)  # between steps the solution lives in (u0, v0): stage kinds 2, 0, 0, 3
-            ops.copy(self.v, self.v0)
-            if self.kappa is not None:
-                ops.copy(self.u0, self.w)
-                self.axpy(self.kappa, self.v0, self.w)
-        while t < tf and (max_steps is None or step < max_steps):
-            dt = min(dt, tf - t)
-            if self.fused:
-                for i in range(4):
-                    tn = t + C_RUNGE[i] * dt
-                    if i == 0:
-                        yield from self._operator_fused(tn if self.source_time == "tn" else t, self.u0, self.v0)
-                    else:
-                        yield from self._operator_fused(tn if self.source_time == "tn" else t)
-                    self._stage_vector_kernel(*self._stage_args(i, dt))
-            else:
-                ops.copy(self.u, self.u0)
-                ops.copy(self.v, self.v0)
-                for i in range(4):
-                    self._stage(i, t, dt)
-            t += dt
-            step += 1
-            if sensors is not None and t > rf and not sensors.full:
-                yield from record_schedule(sensors, self.u0 if self.fused else self.u, t, self.halo)
-        if self.fused:
-            ops.copy(self.u0, self.u)
-            ops.copy(self.v0, self.v)
-        return t, step
-
-    def u_sol(self):
-        """Owned part of the pressure field on the host, valid once ``rk4()`` has returned (mid-run: ``sensors``)."""
-        return self.u[: self.nlocal].detach().cpu().numpy()
-
-    def v_sol(self):
-        return self.v[: self.nlocal].detach().cpu().numpy()
+        yield from ()  # the base class's stage protocol is a generator; this sequence has nothing to post

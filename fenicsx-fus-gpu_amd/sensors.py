@@ -202,22 +202,23 @@ class PointSensors:
 
     def expect_steps(self, start_time, final_time, dt, max_steps=None, record_from=None):
         """Upload, in one copy, the harmonic factors of every step an ``rk4(start_time, final_time, dt, max_steps)`` call
-        will record (its step loop: ``t += min(dt, final_time - t)``; steps that end after ``record_from``, while the series
-        has room).  ``record`` then reads them from this table instead of copying each step's factors (the solvers call this
-        at the start of ``rk4``; a per-step copy ordered between the launches of a step costs more than the sensor launch)."""
+        will record (its steps: ``solver_base.rk4_steps``; those that end after ``record_from``, while the series has room).
+        ``record`` then reads them from this table instead of copying each step's factors (the solvers call this at the
+        start of ``rk4``; a per-step copy ordered between the launches of a step costs more than the sensor launch)."""
         import torch
+
+        from .solver_base import rk4_steps
 
         if not self.harmonics:
             return
-        t, tf, step = float(start_time), float(final_time), 0
         rf = -np.inf if record_from is None else float(record_from)
         room = self.capacity - self.nrec if self.capacity else 1 << 16
         ends = []
-        while t < tf and (max_steps is None or step < max_steps) and len(ends) < room:
-            t += min(dt, tf - t)
-            step += 1
-            if t > rf:
-                ends.append(t)
+        for t, h in rk4_steps(start_time, final_time, dt, max_steps):
+            if len(ends) >= room:
+                break
+            if t + h > rf:
+                ends.append(t + h)
         if self._table_ev is not None:
             self._table_ev.synchronize()  # the previous table's host rows: copied long ago, normally
         self._plan_t, self._plan_i = np.asarray(ends), 0

@@ -1,0 +1,332 @@
+"""
+The explicit RK4 time loop both wave solvers share (``LinearSpectral3D``, ``WesterveltSpectral3D``): their common set-up,
+the step loop of ``rk4`` / ``rk4_schedule``, the fused step and its hipGraph replay (``rk4_graph``).  A solver supplies its
+physics through hooks:
+
+  ``setup_schedule()``                  generator: the set-up exchange (reverse scatters of the assembled mass)
+  ``_stage_reference(i, t, dt)``        generator: stage ``i`` as the reference's launch sequence
+  ``_cell_terms(u_n, v_n, facets)``     generator: the cell part of a fused stage into ``b``, then ``facets()``
+  ``_vector_pass(bw, aw, kind)``        the fused stage's vector kernel (csrc/rk4.hpp)
+  ``_source_scalars(t)``                ``(s1, s2)`` of the source facet term at time ``t``
+  ``_source_set`` / ``_absorbing_set``  ``(c1, c2 or None, detJ, dofmap)`` / ``(c, detJ, dofmap)`` of the two facet sets
+
+hipGraph replay of the fused step (single rank) is for meshes small enough that the launches, not the kernels, bound the
+step -- below roughly 0.5 M dofs when driven from Python (tools/time_rk4_graph.py: 1.7x at 50 k dofs, 1.4x at 118 k,
+nothing to gain from 1 M dofs up, where consecutive stream launches overlap their tails and graph nodes do not).  Every
+launch of a fused step takes fixed device pointers and constants except the source values g(t), dg/dt of the boundary-facet
+terms; with ``fus_facet_terms_dev_*`` those are read from device memory, so the step is captured once
+(``torch.cuda.CUDAGraph`` = hipStreamBeginCapture / hipGraphLaunch) and replayed with one 16-byte-per-stage device copy of
+the step's source values.  A solver with a phased-array source (``self.source``, sources.py) reads a fp64 stage block per
+stage instead (``fus_facet_source_array_dev_*``): ``_sstage`` [4, 6] beside ``_scal``, rewritten before each replay in its
+place.  The reference drives every launch from Python (cuda/demo_linear_box.py:487-566: 12 launches + 5 host syncs per
+stage); this is its launch-bound regime taken to one graph launch per step.
+"""
+
+from __future__ import annotations
+
+import os
+
+import numpy as np
+import torch
+
+from . import _lib
+from . import operators as ops
+from .gll import tabulate_1d, tensor_points_3d, tensor_weights_2d, tensor_weights_3d
+from .precompute import (
+    compute_boundary_facets_scaled_jacobian_determinant_device,
+    compute_scaled_geometrical_factor_device,
+    tabulate_facet_gradients,
+    tabulate_hex_p1_gradients,
+)
+from .sensors import record_schedule
+
+A_RUNGE = (0.0, 0.5, 0.5, 1.0)
+B_RUNGE = (1.0 / 6.0, 1.0 / 3.0, 1.0 / 3.0, 1.0 / 6.0)
+C_RUNGE = (0.0, 0.5, 0.5, 1.0)
+
+
+def per_cell(value, mesh, name):
+    """A material parameter as a per-cell array in the MESH's cell order: a scalar (homogeneous medium, the reference's box
+    demos) or one value per cell in the caller's cell order (the DG0 arrays ``c0.x.array`` ... of the reference's production
+    drivers, cuda/demo_nonlinear_bowl.py:166-178; a mesh that re-ordered its cells -- ``ArrayMesh`` -- permutes them)."""
+    a = np.asarray(value, dtype=np.float64)
+    if a.ndim == 0:
+        return np.full(mesh.ncells, float(a))
+    if a.shape != (mesh.ncells,):
+        raise ValueError(f"{name}: a scalar or one value per cell ({mesh.ncells}), got shape {a.shape}")
+    return np.ascontiguousarray(mesh.permute_cells(a) if hasattr(mesh, "permute_cells") else a)
+
+
+def device_geometry(mesh, P, ft, dev, facet_sets):
+    """G, detJ and the facet detJ of the given boundary_data sets, computed on the device
+    (csrc/geometry.hpp; the reference does this with numba on the host,
+    cuda/demo_linear_box.py:245-317)."""
+    n = P + 1
+    pts, wts, D = tabulate_1d(P, ft)
+    td = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)  # noqa: E731
+    tdt = torch.float64 if np.dtype(ft) == np.float64 else torch.float32
+    w3, w2 = td(tensor_weights_3d(wts).astype(ft)), td(tensor_weights_2d(wts).astype(ft))
+    dphi_g = td(tabulate_hex_p1_gradients(tensor_points_3d(pts), ft))
+    dphi_f = td(tabulate_facet_gradients(pts, ft))
+    gm = (td(mesh.x_dofs), td(mesh.x_g))
+    G = torch.empty((mesh.ncells, n**3, 6), dtype=tdt, device=dev)
+    detJ = torch.empty((mesh.ncells, n**3), dtype=tdt, device=dev)
+    compute_scaled_geometrical_factor_device(G, gm, mesh.ncells, dphi_g, w3, detJ=detJ)
+    out = []
+    for bd in facet_sets:
+        dF = torch.zeros((bd.shape[0], n * n), dtype=tdt, device=dev)
+        if bd.shape[0]:
+            compute_boundary_facets_scaled_jacobian_determinant_device(dF, gm, td(bd.astype(np.int32)), dphi_f, w2)
+        out.append(dF)
+    return D, G, detJ, out
+
+
+def rk4_steps(start_time, final_time, dt, max_steps=None):
+    """``(t, dt)`` of every step of ``rk4(start_time, final_time, dt, max_steps)``: its start and its length, the last step
+    shortened to end at ``final_time``.  A step ends at ``t + dt``: ``sensors.PointSensors.expect_steps`` matches the
+    recording times against those sums bitwise."""
+    t, tf, step = float(start_time), float(final_time), 0
+    while t < tf and (max_steps is None or step < max_steps):
+        dt = min(dt, tf - t)
+        yield t, dt
+        t += dt
+        step += 1
+
+
+class SpectralSolver3D:
+    """The time loop of an explicit RK4 solver for u' = v, M v' = r(u, v, t) (see the module docstring for its hooks)."""
+
+    def _init_common(self, mesh, float_type, comm, fused, source_time):
+        """The attributes both solvers set first; returns the source and absorbing facet sets and the device geometry:
+        ``bd1, bd2, D, G, detJ, (dF1, dF2)``."""
+        if comm is not None:  # an MPI.Comm (the reference's comm = MPI.COMM_WORLD) becomes the bootstrap of a NativeComm
+            from .scatterer import as_comm
+
+            comm = as_comm(comm)
+        self.comm = comm
+        self.mesh, self.P = mesh, mesh.P
+        self.tdt_np = np.dtype(float_type)
+        self.tdt = _lib.torch_dtype(float_type)
+        self.dev = torch.device("cuda", torch.cuda.current_device())
+        self.fused, self.source_time = bool(fused), source_time
+        self.lean_stages = os.environ.get("FUS_RK4_LEAN", "1") != "0"  # the fused stage's vector pass: kinds 4-7 of csrc/rk4.hpp (_stage_args)
+        # the two tagged facet sets (cuda/demo_linear_box.py:230-243, cuda/utils.py:81-114): a structured box names them by its
+        # faces (x = 0: source, x = L: absorbing), a mesh handed over as arrays (dolfinx_adaptor.ArrayMesh) by its facet tags
+        bd1 = mesh.boundary_facets([getattr(mesh, "source_tag", 2)])
+        bd2 = mesh.boundary_facets([getattr(mesh, "absorbing_tag", 3)])
+        # geometry precompute (reference: numba on the host, cuda/demo_linear_box.py:245-317)
+        return (bd1, bd2) + device_geometry(mesh, self.P, self.tdt_np, self.dev, (bd1, bd2))
+
+    def _start_setup(self, defer_setup_exchange):
+        """The set-up exchange (``setup_schedule``): now, or -- several ranks driven from one process, every rank must have
+        posted before any completes -- by the driver through ``self._setup``."""
+        self._setup = self.setup_schedule()
+        if not defer_setup_exchange:
+            for _ in self._setup:
+                pass
+
+    def init(self):
+        """u = v = 0 (cuda/demo_linear_box.py:434-435)."""
+        for t in (self.u, self.v, self.ku, self.kv):
+            ops.fill(0.0, t)
+
+    def _stage_time(self, t, i, dt):
+        """The time stage ``i`` of the step from ``t`` evaluates its source at: the stage time (``source_time="tn"``) or,
+        as the CUDA demos do, the step's start."""
+        return t + C_RUNGE[i] * dt if self.source_time == "tn" else t
+
+    def _stage_args(self, i, dt):
+        """``(bw, aw, kind)`` of the vector pass after stage ``i`` (csrc/rk4.hpp).  Default: the LEAN set 4, 5, 6, 7 with bw = b_runge[0] dt,
+        aw = a_runge[1] dt in all four passes (u's accumulator runs one pass ahead, 34 instead of 41 vector touches per linear step, 46
+        instead of 52 per Westervelt step; v differs from the reference's sequence in the rounding of one term); ``lean_stages = False``
+        (FUS_RK4_LEAN=0): kinds 2, 0, 0, 3, the reference's arithmetic operation for operation."""
+        if self.lean_stages:
+            return B_RUNGE[0] * dt, A_RUNGE[1] * dt, 4 + i
+        last = i == 3
+        return B_RUNGE[i] * dt, 0.0 if last else A_RUNGE[i + 1] * dt, 3 if last else (2 if i == 0 else 0)
+
+    # -- fused stage: the cell pass with the facet terms in one launch, then one vector pass -------------------------------
+    def _operator_fused(self, t, u_n, v_n, scalars=None, stage_dev=None):
+        """b += the cell terms of (u_n, v_n) + the facet terms of the source at time ``t`` and M_f2(c) v_n, in one facet
+        launch.  ``scalars``: device tensor the source values are read from instead of being evaluated at ``t`` (graph
+        capture); ``stage_dev``: the same for a phased-array source (its fp64 stage block)."""
+        field = (v_n,) + self._absorbing_set
+        if self.source is not None:  # M_f1(g_e c1 [+ dg_e c2]) 1 per element + M_f2(c) v_n
+            stage = None if stage_dev is not None else self.source.stage_scalars(t)
+
+            def facets():
+                ops.facet_source_terms(self.b, self.source, field, stage=stage, stage_dev=stage_dev)
+        else:  # M_f1(s1 c1 [+ s2 c2]) 1 + M_f2(c) v_n (the reference fills g into a vector)
+            c1, c2, detJ, dofmap = self._source_set
+            s1, s2 = (0.0, 0.0) if scalars is not None else self._source_scalars(t)
+
+            def facets():
+                ops.facet_terms(self.b, (c1, s1, c2, s2, detJ, dofmap), field, scalars=scalars)
+
+        yield from self._cell_terms(u_n, v_n, facets)
+
+    def _fused_step(self, t, dt):
+        """The 8 launches of one fused RK4 step from ``t``: the first stage reads (u0, v0) themselves, the others the stage
+        buffers (un, ku == v_n).  ``t=None`` (graph capture): every argument is a fixed pointer or a constant, the source
+        values of stage ``i`` are read from ``self._scal[i]`` (a phased-array source: its stage block from ``self._sstage[i]``)."""
+        for i in range(4):
+            u_n, v_n = (self.u0, self.v0) if i == 0 else (self.un, self.ku)
+            if t is None:
+                yield from self._operator_fused(None, u_n, v_n, scalars=self._scal[i],
+                                                stage_dev=self._sstage[i] if self.source is not None else None)
+            else:
+                yield from self._operator_fused(self._stage_time(t, i, dt), u_n, v_n)
+            self._vector_pass(*self._stage_args(i, dt))
+
+    def _fused_enter(self):
+        """Before a fused step loop: between steps the solution lives in (u0, v0), the first stage's inputs as they stand;
+        the last stage writes the new solution straight into them."""
+        ops.fill(0.0, self.b)
+        ops.copy(self.u, self.u0)
+        ops.copy(self.v, self.v0)
+
+    def _fused_exit(self):
+        ops.copy(self.u0, self.u)
+        ops.copy(self.v0, self.v)
+
+    # -- the time loop -----------------------------------------------------------------------------------------------------
+    def rk4(self, start_time, final_time, dt, max_steps=None, sensors=None, record_from=None):
+        """Advance from ``start_time`` to ``final_time`` (cuda/demo_linear_box.py:487-566).
+        Returns ``(t, steps)``.  ``sensors``: a ``sensors.PointSensors`` recorded after every step that ends after
+        ``record_from`` (default: every step) while its series has room -- the supported way to observe the field mid-run."""
+        gen = self.rk4_schedule(start_time, final_time, dt, max_steps, sensors, record_from)
+        while True:
+            try:
+                next(gen)
+            except StopIteration as done:
+                # N > 1: every device-side wait of the exchange is bounded, so a late or dead neighbour cannot hang this
+                # rank -- it must not hand back a field computed from stale ghosts either (the reference would block in
+                # MPI Waitall, cuda/scatterer.py:175): raise.  One synchronisation per rk4() call.
+                self.check_halo_health(f"{type(self).__name__}.rk4")
+                return done.value
+
+    def check_halo_health(self, what="halo exchange"):
+        if self.halo is not None:
+            self.halo.check_health(what)
+
+    def rk4_schedule(self, start_time, final_time, dt, max_steps=None, sensors=None, record_from=None):
+        """``rk4`` as a generator that yields whenever this rank has posted halo exchanges (see
+        ``HaloApply.schedule``); its return value is ``(t, steps)``.  A driver that advances several ranks' generators
+        itself calls ``check_halo_health()`` when they are exhausted (``rk4`` does).  ``u`` / ``v`` are valid only once
+        the generator is exhausted (the fused path keeps the solution in ``u0`` / ``v0`` between steps): observe the field
+        mid-run through ``sensors`` (see ``rk4``; on a partitioned mesh a recording step posts a forward exchange of the
+        field first, with a yield)."""
+        t, step = float(start_time), 0
+        rf = -np.inf if record_from is None else float(record_from)
+        if sensors is not None:
+            sensors.expect_steps(t, final_time, dt, max_steps, record_from)
+        if self.fused:
+            self._fused_enter()
+        for t0, h in rk4_steps(t, final_time, dt, max_steps):
+            if self.fused:
+                yield from self._fused_step(t0, h)
+            else:
+                ops.copy(self.u, self.u0)
+                ops.copy(self.v, self.v0)
+                for i in range(4):
+                    yield from self._stage_reference(i, t0, h)
+            t, step = t0 + h, step + 1
+            if sensors is not None and t > rf and not sensors.full:
+                yield from record_schedule(sensors, self.u0 if self.fused else self.u, t, self.halo)
+        if self.fused:
+            self._fused_exit()
+        return t, step
+
+    # -- hipGraph replay (launch-bound meshes) -----------------------------------------------------------------------------
+    def _graph_state(self):
+        """The tensors a fused step mutates (saved / restored around the warm-up step of a capture)."""
+        return (self.u, self.v, self.u0, self.v0, self.ku, self.un, self.b)
+
+    def _step_graph(self, dt):
+        g = self._graphs.get(dt)
+        if g is None:
+            state = self._graph_state()
+            saved = [t.clone() for t in state]
+            # every kernel of the step once outside the capture (code objects load on first launch, batch
+            # plans are built on first use), on state that is put back afterwards
+            for _ in self._fused_step(None, dt):
+                pass
+            torch.cuda.synchronize()
+            for t, s_ in zip(state, saved):
+                t.copy_(s_)
+            # the captured nodes hold the RAW device pointers of the batch-plan workspaces the operators looked up:
+            # keep those workspaces (and the dofmaps they belong to) alive for as long as the graph lives -- the plan
+            # cache is bounded and evicts oldest-first, and an evicted workspace that nothing else references would be
+            # freed under the graph's feet (replay does not go through the plan registry)
+            g = torch.cuda.CUDAGraph()
+            ops._PLANS.start_recording()
+            try:
+                with torch.cuda.graph(g):
+                    for _ in self._fused_step(None, dt):
+                        pass
+            finally:
+                held = ops._PLANS.stop_recording()
+            self._graphs[dt] = g
+            self._graph_plans = getattr(self, "_graph_plans", {})
+            self._graph_plans[dt] = held
+        return g
+
+    def rk4_graph(self, start_time, final_time, dt, max_steps=None, sensors=None, record_from=None):
+        """``rk4`` with the full-size steps replayed from ONE captured hipGraph.  Same kernels in the same
+        order on the same data as ``rk4``.  One rank, fused path; a last shorter step runs through ``rk4``.
+        ``sensors`` / ``record_from`` as in ``rk4``: the sensor launch follows a replay on the same stream, outside the
+        captured graph.  Returns ``(t, steps)``."""
+        if not self.fused or self.halo is not None:
+            raise _lib.FusGpuError("rk4_graph: single-rank fused path only")
+        t, tf = float(start_time), float(final_time)
+        rf = -np.inf if record_from is None else float(record_from)
+        rows, ends = [], []
+        if sensors is not None:
+            sensors.expect_steps(t, tf, dt, max_steps, record_from)
+        src = self.source
+        for t0, h in rk4_steps(t, tf, dt, max_steps):
+            if h != dt:
+                break
+            ts = [self._stage_time(t0, i, dt) for i in range(4)]
+            rows.append([self._source_scalars(x) for x in ts] if src is None else [src.stage_scalars(x) for x in ts])
+            t = t0 + h
+            ends.append(t)
+        if rows:
+            if not hasattr(self, "_graphs"):
+                self._graphs = {}
+                self._scal = torch.zeros((4, 2), dtype=self.tdt, device=self.dev)
+                if src is not None:
+                    self._sstage = torch.zeros((4, len(rows[0][0])), dtype=torch.float64, device=self.dev)
+            if src is None:
+                table, slot = torch.from_numpy(np.asarray(rows, dtype=np.float64).astype(self.tdt_np)).to(self.dev), self._scal
+            else:  # the stage blocks stay fp64 for fp32 fields too
+                table, slot = torch.from_numpy(np.asarray(rows, dtype=np.float64)).to(self.dev), self._sstage
+            graph = self._step_graph(dt)
+            self._fused_enter()
+            for k in range(len(rows)):
+                slot.copy_(table[k])
+                graph.replay()
+                if sensors is not None and ends[k] > rf and not sensors.full:
+                    sensors.record(self.u0, ends[k])
+            self._fused_exit()
+        steps = len(rows)
+        if t < tf and (max_steps is None or steps < max_steps):
+            t, more = self.rk4(t, tf, dt, None if max_steps is None else max_steps - steps, sensors, record_from)
+            steps += more
+        return t, steps
+
+    # -- the solution on the host ------------------------------------------------------------------------------------------
+    def u_sol(self, with_ghosts=False):
+        """Owned part of the pressure field on the host; ``with_ghosts``: the whole local vector after a forward scatter
+        (``scatter_fwd(u_n_d); u_n_d.copy_to_host(u_n)``, cuda/demo_linear_box.py:568-570 -- what point evaluation needs).
+        Valid once ``rk4()`` has returned; mid-run, ``rk4(..., sensors=...)`` observes the field on the device."""
+        if not with_ghosts:
+            return self.u[: self.nlocal].detach().cpu().numpy()
+        if self.halo is not None:
+            self.halo.fwd(self.u)
+            torch.cuda.synchronize()
+            self.check_halo_health(f"{type(self).__name__}.u_sol(with_ghosts=True)")
+        return self.u.detach().cpu().numpy()
+
+    def v_sol(self):
+        return self.v[: self.nlocal].detach().cpu().numpy()
