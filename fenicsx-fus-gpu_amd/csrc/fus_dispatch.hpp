@@ -76,26 +76,48 @@ inline int hip_rc(hipError_t e) { return e == hipSuccess ? FUS_OK : FUS_ERR_HIP_
 
 inline bool misaligned(const void* p, size_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) != 0; }
 
-inline int cells_per_batch(int P) {
-  const int n2 = (P + 1) * (P + 1);
-  return 256 / n2 > 0 ? 256 / n2 : 1;
-}
-
-template <int P>
-int64_t plan_bytes_p(int64_t ncell) {
-  return fus::plan_view(nullptr, P, fus::plan_cells_per_batch<P>(), ncell).bytes;
+// The one switch from the runtime degree to code compiled per degree: K is a generic lambda taking std::integral_constant<int, P>
+// (as plan_dispatch, plan.hpp, takes its two booleans).  false, and K not called, for a degree outside the supported range.
+static_assert(FUS_MIN_DEGREE == 1 && FUS_MAX_DEGREE == 10, "degree_dispatch lists the supported degrees");
+template <typename K>
+inline bool degree_dispatch(int P, K&& k) {
+  switch (P) {
+    case 1: k(std::integral_constant<int, 1>{}); return true;
+    case 2: k(std::integral_constant<int, 2>{}); return true;
+    case 3: k(std::integral_constant<int, 3>{}); return true;
+    case 4: k(std::integral_constant<int, 4>{}); return true;
+    case 5: k(std::integral_constant<int, 5>{}); return true;
+    case 6: k(std::integral_constant<int, 6>{}); return true;
+    case 7: k(std::integral_constant<int, 7>{}); return true;
+    case 8: k(std::integral_constant<int, 8>{}); return true;
+    case 9: k(std::integral_constant<int, 9>{}); return true;
+    case 10: k(std::integral_constant<int, 10>{}); return true;
+  }
+  return false;
 }
 
 inline int64_t plan_bytes(int P, int64_t ncell) {
-  switch (P) {
-#define FUS_CASE(PP) \
-  case PP:           \
-    return plan_bytes_p<PP>(ncell);
-    FUS_CASE(1) FUS_CASE(2) FUS_CASE(3) FUS_CASE(4) FUS_CASE(5) FUS_CASE(6) FUS_CASE(7) FUS_CASE(8) FUS_CASE(9)
-    FUS_CASE(10)
-#undef FUS_CASE
-  }
-  return FUS_ERR_UNSUPPORTED_DEGREE;
+  if (P < FUS_MIN_DEGREE || P > FUS_MAX_DEGREE) return FUS_ERR_UNSUPPORTED_DEGREE;
+  return fus::plan_view(nullptr, P, fus::cells_per_batch(P), ncell).bytes;
+}
+
+// What the entry points of the planned cell operators check and decide in common, in the order of their error codes: negative cell count,
+// degree, the empty mesh (FUS_OK before any pointer is looked at), the entry's own arguments (``args_ok``: its null pointers and the
+// alignment of its G) and the workspace, the plan of the workspace; then which list encoding the launch reads (plan_use_runs) and the
+// degree.  ``launch`` is a generic lambda (std::integral_constant<int, P>, bool ordered, bool use_runs) -> hipError_t.
+template <typename T, typename L>
+int planned_cell_entry(bool args_ok, const void* ws, int P, int64_t ncell, L&& launch) {
+  if (ncell < 0) return FUS_ERR_INVALID_ARGUMENT;
+  if (P < FUS_MIN_DEGREE || P > FUS_MAX_DEGREE) return FUS_ERR_UNSUPPORTED_DEGREE;
+  if (ncell == 0) return FUS_OK;
+  if (!args_ok || !ws || misaligned(ws, 256)) return FUS_ERR_INVALID_ARGUMENT;
+  const int Nd = (P + 1) * (P + 1) * (P + 1);
+  bool ord = false, rp = true;
+  if (!plan_check(ws, Nd, fus::cells_per_batch(P), ncell, &ord, nullptr, &rp)) return FUS_ERR_PLAN_MISMATCH;
+  const bool use_runs = plan_use_runs<T>(Nd, rp);
+  hipError_t e = hipErrorInvalidValue;
+  degree_dispatch(P, [&](auto p) { e = launch(p, ord, use_runs); });
+  return hip_rc(e);
 }
 
 

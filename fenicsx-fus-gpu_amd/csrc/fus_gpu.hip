@@ -36,8 +36,8 @@ hipError_t stiffness_dispatch_variant(const T* x, const T* cc, T* y, const T* G,
                                       const T* dphi, int64_t ncell, hipStream_t s) {
   const int variant = g_stiffness_variant.load(std::memory_order_relaxed);
   const int remap = g_xcd_remap.load(std::memory_order_relaxed);
-  constexpr int CPB256 = fus::default_cells_per_block<P>(256);
-  constexpr int CPB128 = fus::default_cells_per_block<P>(128);
+  constexpr int CPB256 = fus::default_cells_per_block(P, 256);
+  constexpr int CPB128 = fus::default_cells_per_block(P, 128);
   switch (variant) {
     case 1:  // ~128-thread workgroups
       return fus::launch_stiffness_col<T, P, CPB128>(x, cc, y, G, dofmap, dphi, ncell, remap, s);
@@ -58,15 +58,7 @@ int stiffness_apply(const T* x, const T* cc, T* y, const T* G, const int32_t* do
     return FUS_ERR_INVALID_ARGUMENT;
   hipStream_t s = static_cast<hipStream_t>(stream);
   hipError_t e = hipErrorInvalidValue;
-  switch (P) {
-#define FUS_CASE(PP) \
-  case PP:           \
-    e = stiffness_dispatch_variant<T, PP>(x, cc, y, G, dofmap, dphi, ncell, s); \
-    break;
-    FUS_CASE(1) FUS_CASE(2) FUS_CASE(3) FUS_CASE(4) FUS_CASE(5) FUS_CASE(6) FUS_CASE(7) FUS_CASE(8) FUS_CASE(9)
-    FUS_CASE(10)
-#undef FUS_CASE
-  }
+  degree_dispatch(P, [&](auto p) { e = stiffness_dispatch_variant<T, decltype(p)::value>(x, cc, y, G, dofmap, dphi, ncell, s); });
   return hip_rc(e);
 }
 
@@ -185,14 +177,9 @@ int probe_eval(const T* u, const int32_t* cells, int64_t npts, const int32_t* do
   T* row = rec ? rec + (int64_t)slot * npts : nullptr;
   hipStream_t s = static_cast<hipStream_t>(stream);
   hipError_t e = hipErrorInvalidValue;
-  switch (P) {
-#define FUS_CASE(PP)                                                                                                        \
-  case PP:                                                                                                                  \
-    e = fus::launch_probe_eval<T, PP>(u, cells, dofmap, weights, npts, ncells, row, pmax, pmin, hre, him, coef, H, s); \
-    break;
-    FUS_CASE(1) FUS_CASE(2) FUS_CASE(3) FUS_CASE(4) FUS_CASE(5) FUS_CASE(6) FUS_CASE(7) FUS_CASE(8) FUS_CASE(9) FUS_CASE(10)
-#undef FUS_CASE
-  }
+  degree_dispatch(P, [&](auto p) {
+    e = fus::launch_probe_eval<T, decltype(p)::value>(u, cells, dofmap, weights, npts, ncells, row, pmax, pmin, hre, him, coef, H, s);
+  });
   return hip_rc(e);
 }
 
@@ -305,7 +292,7 @@ int64_t fus_stiffness_plan_bytes(int P, int64_t ncell) {
 int fus_stiffness_plan_build(const int32_t* dofmap, int P, int64_t ncell, void* workspace, int64_t workspace_bytes,
                              void* stream) {
   if (P < FUS_MIN_DEGREE || P > FUS_MAX_DEGREE) return FUS_ERR_UNSUPPORTED_DEGREE;
-  return fus_plan_build_ordered(dofmap, nullptr, (P + 1) * (P + 1) * (P + 1), cells_per_batch(P), ncell, workspace,
+  return fus_plan_build_ordered(dofmap, nullptr, (P + 1) * (P + 1) * (P + 1), fus::cells_per_batch(P), ncell, workspace,
                                 workspace_bytes, stream);
 }
 
@@ -322,9 +309,7 @@ int fus_plan_entities_per_batch(int N) {
   if (N < 1 || N > fus::kPlanMaxEntries) return FUS_ERR_UNSUPPORTED_ENTITY;
   // cells (N = n^3): the stiffness kernel's batch size, so one plan serves both operators
   for (int P = FUS_MIN_DEGREE; P <= FUS_MAX_DEGREE; ++P)
-    if ((P + 1) * (P + 1) * (P + 1) == N) {
-      return 256 / ((P + 1) * (P + 1)) > 0 ? 256 / ((P + 1) * (P + 1)) : 1;
-    }
+    if ((P + 1) * (P + 1) * (P + 1) == N) return fus::cells_per_batch(P);
   const int epb = 1280 / N;  // ~5 entries per thread of a 256-thread workgroup
   return epb > 0 ? epb : 1;
 }

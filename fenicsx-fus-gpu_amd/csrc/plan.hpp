@@ -139,9 +139,11 @@ __host__ __device__ constexpr int next_pow2(int v) {
 }
 __host__ __device__ constexpr int64_t align256(int64_t v) { return (v + 255) / 256 * 256; }
 
+// cells per batch of a plan of degree P: the one rule behind the kernels' CPB, the C ABI's checks and fus_plan_entities_per_batch
+__host__ __device__ constexpr int cells_per_batch(int P) { return default_cells_per_block(P, 256); }
 template <int P>
 __host__ __device__ constexpr int plan_cells_per_batch() {
-  return default_cells_per_block<P>(256);
+  return cells_per_batch(P);
 }
 
 struct PlanView {
@@ -324,6 +326,17 @@ inline void plan_dispatch(bool ordered, bool runs, K&& k) {
     if (runs) k(std::false_type{}, std::true_type{});
     else k(std::false_type{}, std::false_type{});
   }
+}
+
+// One launch of a planned cell kernel: the batch view of the workspace, the fork signal waiting on the stream, the (ORDERED, RUNS)
+// build.  K is a generic lambda (tag_o, tag_r, const PlanView&, LaunchSignal) that holds the hipLaunchKernelGGL line of its kernel.
+template <typename K>
+inline hipError_t plan_launch(const void* workspace, int P, int cpb, int64_t ncell, hipStream_t stream, bool ordered, bool runs, K&& k) {
+  if (ncell <= 0) return hipSuccess;
+  const PlanView v = plan_view(const_cast<void*>(workspace), P, cpb, ncell);
+  const LaunchSignal sig = take_launch_signal(stream);
+  plan_dispatch(ordered, runs, [&](auto o, auto r) { k(o, r, v, sig); });
+  return settle_launch_signal(stream, sig, hipGetLastError());
 }
 
 template <typename T>

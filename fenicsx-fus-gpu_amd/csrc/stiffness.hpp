@@ -66,6 +66,16 @@ __device__ __forceinline__ void load_g6(const T* __restrict__ p, T (&g)[6]) {
   g[5] = c.y;
 }
 
+// Flux of one quadrature point: scale * G (vx, vy, vz) with the symmetric G as its six values (xx, xy, xz, yy, yz, zz), written
+// straight to the destinations (a flux register, the two flux cubes in LDS) in this order.  scale = 1 folds away.  No __restrict__ on
+// gq: its alias scope lands on the caller's LDS stores and reschedules kernels (the P = 10 whole-slab builds: + 11 v_mov_b64).
+template <typename T>
+__device__ __forceinline__ void apply_g6(const T* gq, T vx, T vy, T vz, T& fx, T& fy, T& fz, T scale = T(1)) {
+  fx = scale * (gq[0] * vx + gq[1] * vy + gq[2] * vz);
+  fy = scale * (gq[1] * vx + gq[3] * vy + gq[4] * vz);
+  fz = scale * (gq[2] * vx + gq[4] * vy + gq[5] * vz);
+}
+
 __host__ __device__ constexpr int round_up(int a, int b) { return (a + b - 1) / b * b; }
 
 // LDS stride between the cubes of consecutive cells: padded so that the few distinct addresses a
@@ -79,9 +89,9 @@ __host__ __device__ constexpr int lds_cell_stride() {
   return s;
 }
 
-template <int P>
-__host__ __device__ constexpr int default_cells_per_block(int target_threads) {
-  constexpr int n2 = (P + 1) * (P + 1);
+// cells of n^2 threads each in a workgroup of about ``target_threads`` (at least one); 256 for every plan (plan.hpp: cells_per_batch)
+__host__ __device__ constexpr int default_cells_per_block(int P, int target_threads) {
+  const int n2 = (P + 1) * (P + 1);
   return target_threads / n2 > 0 ? target_threads / n2 : 1;
 }
 
@@ -168,10 +178,7 @@ __global__ void __launch_bounds__((col_block_threads<P, CPB>()))
         vy += dy[i] * cu_y[qx * n2 + i * n];
         vz += dz[i] * cu_z[qx * n2 + i];
       }
-      const T* gq = g[qx];
-      fx[qx] = coeff * (gq[0] * vx + gq[1] * vy + gq[2] * vz);
-      cfy[qx * n2] = coeff * (gq[1] * vx + gq[3] * vy + gq[4] * vz);
-      cfz[qx * n2] = coeff * (gq[2] * vx + gq[4] * vy + gq[5] * vz);
+      apply_g6<T>(g[qx], vx, vy, vz, fx[qx], cfy[qx * n2], cfz[qx * n2], coeff);
     }
   }
   __syncthreads();

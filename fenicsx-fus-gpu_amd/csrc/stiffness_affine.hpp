@@ -84,10 +84,7 @@ __global__ void __launch_bounds__((col_block_threads<P, CPB>()), MINW)
     for (int qx = 0; qx < n; ++qx) {
       T vx, vy, vz;
       plan_grad_at<T, n, n2>(qx, dphi, u, dy, dz, cu_y, cu_z, vx, vy, vz);
-      const T cw = coeff * wr[qx];
-      fx[qx] = cw * (g0[0] * vx + g0[1] * vy + g0[2] * vz);
-      cfy[qx * n2] = cw * (g0[1] * vx + g0[3] * vy + g0[4] * vz);
-      cfz[qx * n2] = cw * (g0[2] * vx + g0[4] * vy + g0[5] * vz);
+      apply_g6<T>(g0, vx, vy, vz, fx[qx], cfy[qx * n2], cfz[qx * n2], coeff * wr[qx]);
     }
   }
   __syncthreads();
@@ -105,16 +102,11 @@ inline hipError_t launch_stiffness_plan_affine(const T* x, const T* cc, T* y, co
                                                const void* workspace, const T* dphi, int64_t ncell,
                                                hipStream_t stream, bool ordered = false, bool use_runs = false) {
   constexpr int CPB = plan_cells_per_batch<P>();
-  if (ncell <= 0) return hipSuccess;
-  PlanView v = plan_view(const_cast<void*>(workspace), P, CPB, ncell);
-  constexpr int threads = col_block_threads<P, CPB>();
-  const LaunchSignal sig = take_launch_signal(stream);
-  plan_dispatch(ordered, use_runs, [&](auto o, auto r) {
+  return plan_launch(workspace, P, CPB, ncell, stream, ordered, use_runs, [&](auto o, auto r, const PlanView& v, LaunchSignal sig) {
     hipLaunchKernelGGL((stiffness_plan_affine_kernel<T, P, CPB, ALIAS, PADLDS, MINW, decltype(o)::value, decltype(r)::value>),
-                       dim3((unsigned)v.nbatch), dim3(threads), 0, stream, x, cc, y, G, v.nu, v.udofs, v.slot, dphi, ncell, wratio,
-                       v.order, v.runs, sig);
+                       dim3((unsigned)v.nbatch), dim3(col_block_threads<P, CPB>()), 0, stream, x, cc, y, G, v.nu, v.udofs, v.slot, dphi,
+                       ncell, wratio, v.order, v.runs, sig);
   });
-  return settle_launch_signal(stream, sig, hipGetLastError());
 }
 
 }  // namespace fus

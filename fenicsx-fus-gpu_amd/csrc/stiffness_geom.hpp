@@ -345,10 +345,7 @@ __global__ void __launch_bounds__((col_block_threads<P, CPB>()), MINW)
       } else {
         T gl[6];
         if constexpr (!PREG) column_g_at<T>(pts[qx], wts[qx] * s0, J0, Ja, Jba, Jc, Jdc, gl);
-        const T* gq = PREG ? g[PREG ? qx : 0] : gl;
-        fx[qx] = gq[0] * vx + gq[1] * vy + gq[2] * vz;
-        cfy[qx * n2] = gq[1] * vx + gq[3] * vy + gq[4] * vz;
-        cfz[qx * n2] = gq[2] * vx + gq[4] * vy + gq[5] * vz;
+        apply_g6<T>(PREG ? g[PREG ? qx : 0] : gl, vx, vy, vz, fx[qx], cfy[qx * n2], cfz[qx * n2]);
       }
     }
   }
@@ -367,16 +364,11 @@ template <typename T, int P, bool ALIAS, bool PADLDS, int MINW, bool PREG, int C
 inline hipError_t launch_stiffness_plan_geom(const T* x, const T* cc, T* y, const T* x_g, const int32_t* x_dofs,
                                              const T* pts, const T* wts, const void* workspace, const T* dphi,
                                              int64_t ncell, hipStream_t stream, bool ordered = false, bool use_runs = false) {
-  if (ncell <= 0) return hipSuccess;
-  PlanView v = plan_view(const_cast<void*>(workspace), P, CPB, ncell);
-  constexpr int threads = col_block_threads<P, CPB>();
-  const LaunchSignal sig = take_launch_signal(stream);
-  plan_dispatch(ordered, use_runs, [&](auto o, auto r) {
+  return plan_launch(workspace, P, CPB, ncell, stream, ordered, use_runs, [&](auto o, auto r, const PlanView& v, LaunchSignal sig) {
     hipLaunchKernelGGL((stiffness_plan_geom_kernel<T, P, CPB, ALIAS, PADLDS, MINW, PREG, decltype(o)::value, decltype(r)::value>),
-                       dim3((unsigned)v.nbatch), dim3(threads), 0, stream, x, cc, y, x_g, x_dofs, pts, wts, v.nu, v.udofs, v.slot,
-                       dphi, ncell, v.order, v.runs, sig);
+                       dim3((unsigned)v.nbatch), dim3(col_block_threads<P, CPB>()), 0, stream, x, cc, y, x_g, x_dofs, pts, wts, v.nu,
+                       v.udofs, v.slot, dphi, ncell, v.order, v.runs, sig);
   });
-  return settle_launch_signal(stream, sig, hipGetLastError());
 }
 
 }  // namespace fus

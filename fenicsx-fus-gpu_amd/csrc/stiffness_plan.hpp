@@ -1,13 +1,23 @@
 // Planned stiffness apply (the shipped default): same column-per-thread contraction structure as
 // stiffness_col_kernel (stiffness.hpp), gather / scatter through the batch plan (plan.hpp).
 //
-// This header holds ONLY product kernels.  Three kernels share the gather / contraction / flush
-// phases below as force-inlined device functions and differ in where the geometric factor comes from:
+// This header holds ONLY product kernels.  The planned cell kernels differ in where the geometric factor comes from:
 //   stiffness_plan_kernel         general per-quadrature-point G[ncell][n^3][6] (the headline path)
 //   stiffness_plan_affine_kernel  affine cells: one 6-value record per cell (stiffness_affine.hpp)
 //   stiffness_plan_geom_kernel    G formed in registers from the cell's 8 vertices (stiffness_geom.hpp)
-// Each is its own __global__ template so that an edit to one cannot change the register allocation
-// of another; tests/test_resource_usage.py pins VGPR / occupancy / scratch of the default builds.
+// (and the two Westervelt cell passes, westervelt.hpp / westervelt_geom.hpp).  Each is its own __global__ template so that an
+// edit to one cannot change the register allocation of another; tests/test_resource_usage.py pins VGPR / occupancy / scratch
+// of the default builds.  What they share, as force-inlined device functions:
+//   all five          the preamble helpers of plan.hpp, plan_grad_at, apply_g6 (stiffness.hpp: also the plan-free kernel),
+//                     plan_zero, plan_flush
+//   general, affine   plan_gather_x           the three stiffness kernels   plan_backward
+//   both in-kernel-geometry kernels           the vertex staging and the column geometry (stiffness_geom.hpp)
+// and on the host one launch path (plan_launch, plan.hpp) and one argument check + degree switch (fus_dispatch.hpp).
+// What stays written out in each kernel, because every shared form tried compiled to other code (a helper is optimised as a
+// function of its own before it is inlined, and the order it gives its loads, address arithmetic and LDS atomics survives;
+// per kernel: profiles/planned_cells_refactor.log): the header of the flux loop (the dy / dz rows and the four cube pointers),
+// the backward loop and the lumped-mass early flush of the two Westervelt kernels, the gather next to the vertex staging and the
+// three table stores of the two in-kernel-geometry kernels, the thread-index arithmetic.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -238,10 +248,7 @@ __global__ void __launch_bounds__((col_block_threads<P, CPB>()), MINW)
     for (int qx = 0; qx < n; ++qx) {
       T vx, vy, vz;
       plan_grad_at<T, n, n2>(qx, dphi, u, dy, dz, cu_y, cu_z, vx, vy, vz);
-      const T* gq = g[qx % GPRE];
-      fx[qx] = gq[0] * vx + gq[1] * vy + gq[2] * vz;
-      cfy[qx * n2] = gq[1] * vx + gq[3] * vy + gq[4] * vz;
-      cfz[qx * n2] = gq[2] * vx + gq[4] * vy + gq[5] * vz;
+      apply_g6<T>(g[qx % GPRE], vx, vy, vz, fx[qx], cfy[qx * n2], cfz[qx * n2]);
       if constexpr (GPRE < n) {
         if (qx + GPRE < n) load_g6<T>(Gc + (int64_t)(qx + GPRE) * n2 * 6, g[qx % GPRE]);
       }
@@ -262,16 +269,11 @@ inline hipError_t launch_stiffness_plan(const T* x, const T* cc, T* y, const T* 
                                         const T* dphi, int64_t ncell, int xcd_remap, hipStream_t stream,
                                         bool ordered = false, bool use_runs = false) {
   constexpr int CPB = plan_cells_per_batch<P>();
-  if (ncell <= 0) return hipSuccess;
-  PlanView v = plan_view(const_cast<void*>(workspace), P, CPB, ncell);
-  constexpr int threads = col_block_threads<P, CPB>();
-  const LaunchSignal sig = take_launch_signal(stream);
-  plan_dispatch(ordered, use_runs, [&](auto o, auto r) {
+  return plan_launch(workspace, P, CPB, ncell, stream, ordered, use_runs, [&](auto o, auto r, const PlanView& v, LaunchSignal sig) {
     hipLaunchKernelGGL((stiffness_plan_kernel<T, P, CPB, ALIAS, PADLDS, MINW, GPRE, decltype(o)::value, decltype(r)::value>),
-                       dim3((unsigned)v.nbatch), dim3(threads), 0, stream, x, cc, y, G, v.nu, v.udofs, v.slot, dphi, ncell,
-                       xcd_remap, v.order, v.runs, sig);
+                       dim3((unsigned)v.nbatch), dim3(col_block_threads<P, CPB>()), 0, stream, x, cc, y, G, v.nu, v.udofs, v.slot, dphi,
+                       ncell, xcd_remap, v.order, v.runs, sig);
   });
-  return settle_launch_signal(stream, sig, hipGetLastError());
 }
 
 }  // namespace fus

@@ -174,10 +174,7 @@ __global__ void __launch_bounds__((col_block_threads<P, CPB>()), MINW)
     for (int qx = 0; qx < n; ++qx) {
       T vx, vy, vz;
       plan_grad_at<T, n, n2>(qx, dphi, w, dy, dz, cu_y, cu_z, vx, vy, vz);
-      const T* gq = g[qx % GPRE];
-      fx[qx] = gq[0] * vx + gq[1] * vy + gq[2] * vz;
-      cfy[qx * n2] = gq[1] * vx + gq[3] * vy + gq[4] * vz;
-      cfz[qx * n2] = gq[2] * vx + gq[4] * vy + gq[5] * vz;
+      apply_g6<T>(g[qx % GPRE], vx, vy, vz, fx[qx], cfy[qx * n2], cfz[qx * n2]);
       if constexpr (GPRE < n) {
         if (qx + GPRE < n) load_g6<T>(Gc + (int64_t)(qx + GPRE) * n2 * 6, g[qx % GPRE]);
       }
@@ -224,19 +221,14 @@ inline hipError_t launch_westervelt_cell(const T* u, const T* v, const T* c2, co
                                          T* b, T* m, const T* G, const T* detJ, const void* workspace, const T* dphi,
                                          int64_t ncell, hipStream_t stream, bool ordered = false, bool use_runs = false) {
   constexpr int CPB = plan_cells_per_batch<P>();
-  if (ncell <= 0) return hipSuccess;
-  PlanView pv = plan_view(const_cast<void*>(workspace), P, CPB, ncell);
-  constexpr int threads = col_block_threads<P, CPB>();
   constexpr int MINW = 1;
   // stiffness-only: the ring sizes of the stiffness kernel (its register profile + one more gather)
   constexpr int RING = MASS ? westervelt_g_ring<P>() : (P >= 6 ? plan_g_ring<P>() : P + 1);
-  const LaunchSignal sig = take_launch_signal(stream);
-  plan_dispatch(ordered, use_runs, [&](auto o, auto r) {
+  return plan_launch(workspace, P, CPB, ncell, stream, ordered, use_runs, [&](auto o, auto r, const PlanView& pv, LaunchSignal sig) {
     hipLaunchKernelGGL((westervelt_cell_kernel<T, P, CPB, MINW, RING, MASS, decltype(o)::value, decltype(r)::value>),
-                       dim3((unsigned)pv.nbatch), dim3(threads), 0, stream, u, v, c2, c3, c4, c5, b, m, G, detJ, pv.nu, pv.udofs,
-                       pv.slot, dphi, ncell, pv.order, pv.runs, sig);
+                       dim3((unsigned)pv.nbatch), dim3(col_block_threads<P, CPB>()), 0, stream, u, v, c2, c3, c4, c5, b, m, G, detJ,
+                       pv.nu, pv.udofs, pv.slot, dphi, ncell, pv.order, pv.runs, sig);
   });
-  return settle_launch_signal(stream, sig, hipGetLastError());
 }
 
 // Fused RK4 stage vector kernel of the Westervelt solver: as rk4_stage_kernel (rk4.hpp) but the

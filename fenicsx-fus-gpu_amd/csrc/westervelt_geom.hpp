@@ -169,9 +169,7 @@ __global__ void __launch_bounds__((col_block_threads<P, CPB>()), MINW)
       } else {
         T gq[6];
         column_g_at<T>(pts[qx], wts[qx] * wyz, J0, Ja, Jba, Jc, Jdc, gq);
-        fx[qx] = gq[0] * vx + gq[1] * vy + gq[2] * vz;
-        cfy[qx * n2] = gq[1] * vx + gq[3] * vy + gq[4] * vz;
-        cfz[qx * n2] = gq[2] * vx + gq[4] * vy + gq[5] * vz;
+        apply_g6<T>(gq, vx, vy, vz, fx[qx], cfy[qx * n2], cfz[qx * n2]);
       }
     }
   }
@@ -211,16 +209,11 @@ inline hipError_t launch_westervelt_cell_geom(const T* u, const T* v, const T* c
                                               const T* pts, const T* wts, const void* workspace, const T* dphi,
                                               int64_t ncell, hipStream_t stream, bool ordered = false, bool use_runs = false) {
   constexpr int CPB = plan_cells_per_batch<P>();
-  if (ncell <= 0) return hipSuccess;
-  PlanView pv = plan_view(const_cast<void*>(workspace), P, CPB, ncell);
-  constexpr int threads = col_block_threads<P, CPB>();
-  const LaunchSignal sig = take_launch_signal(stream);
-  plan_dispatch(ordered, use_runs, [&](auto o, auto r) {
+  return plan_launch(workspace, P, CPB, ncell, stream, ordered, use_runs, [&](auto o, auto r, const PlanView& pv, LaunchSignal sig) {
     hipLaunchKernelGGL((westervelt_cell_geom_kernel<T, P, CPB, 1, MASS, decltype(o)::value, decltype(r)::value>),
-                       dim3((unsigned)pv.nbatch), dim3(threads), 0, stream, u, v, c2, c3, c4, c5, b, m, x_g, x_dofs, pts, wts, pv.nu,
-                       pv.udofs, pv.slot, dphi, ncell, pv.order, pv.runs, sig);
+                       dim3((unsigned)pv.nbatch), dim3(col_block_threads<P, CPB>()), 0, stream, u, v, c2, c3, c4, c5, b, m, x_g, x_dofs, pts,
+                       wts, pv.nu, pv.udofs, pv.slot, dphi, ncell, pv.order, pv.runs, sig);
   });
-  return settle_launch_signal(stream, sig, hipGetLastError());
 }
 
 }  // namespace fus
