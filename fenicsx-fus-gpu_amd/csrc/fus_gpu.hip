@@ -10,6 +10,7 @@
 #include <mutex>
 #include <unordered_map>
 
+#include "field_monitor.hpp"
 #include "fus_dispatch.hpp"
 #include "geometry.hpp"
 #include "halo.hpp"
@@ -181,6 +182,23 @@ int probe_eval(const T* u, const int32_t* cells, int64_t npts, const int32_t* do
     e = fus::launch_probe_eval<T, decltype(p)::value>(u, cells, dofmap, weights, npts, ncells, row, pmax, pmin, hre, him, coef, H, s);
   });
   return hip_rc(e);
+}
+
+// full-field monitors (csrc/field_monitor.hpp): every check before any device work; n == 0 or no output requested is a no-op
+template <typename T>
+int field_accumulate(const T* u, const T* v, int64_t n, T* pmax, T* pmin, double* usq, double* vsq, double* hre, double* him,
+                     int64_t hstride, const double* coef, int H, int init, void* stream) {
+  if (n < 0 || H < 0 || H > 4) return FUS_ERR_INVALID_ARGUMENT;
+  if (H > 0 && (!hre || !him || !coef || hstride < n)) return FUS_ERR_INVALID_ARGUMENT;
+  if ((vsq && !v) || (!pmax != !pmin)) return FUS_ERR_INVALID_ARGUMENT;
+  if (n == 0 || (!pmax && !usq && !vsq && H == 0)) return FUS_OK;
+  if (!u) return FUS_ERR_INVALID_ARGUMENT;
+  if (misaligned(u, sizeof(T)) || misaligned(v, sizeof(T)) || misaligned(pmax, sizeof(T)) || misaligned(pmin, sizeof(T)) ||
+      misaligned(usq, sizeof(double)) || misaligned(vsq, sizeof(double)) || misaligned(hre, sizeof(double)) ||
+      misaligned(him, sizeof(double)) || misaligned(coef, sizeof(double)))
+    return FUS_ERR_INVALID_ARGUMENT;
+  return hip_rc(fus::launch_field_accumulate<T>(u, v, n, pmax, pmin, usq, vsq, hre, him, hstride, coef, H, init != 0,
+                                                static_cast<hipStream_t>(stream)));
 }
 
 // phased-array source facets (csrc/source_array.hpp): every check before any device work; nA + nB == 0 is a no-op.
@@ -589,6 +607,14 @@ FUS_GEOM(double, f64)
 FUS_GEOM(float, f32)
 #undef FUS_GEOM
 
+int fus_field_accumulate_f64(const double* u, const double* v, int64_t n, double* pmax, double* pmin, double* usq, double* vsq,
+                             double* hre, double* him, int64_t hstride, const double* coef, int H, int init, void* stream) {
+  return field_accumulate<double>(u, v, n, pmax, pmin, usq, vsq, hre, him, hstride, coef, H, init, stream);
+}
+int fus_field_accumulate_f32(const float* u, const float* v, int64_t n, float* pmax, float* pmin, double* usq, double* vsq,
+                             double* hre, double* him, int64_t hstride, const double* coef, int H, int init, void* stream) {
+  return field_accumulate<float>(u, v, n, pmax, pmin, usq, vsq, hre, him, hstride, coef, H, init, stream);
+}
 int fus_probe_eval_f64(const double* u, const int32_t* cells, int64_t npts, const int32_t* dofmap, int64_t ncells,
                        const double* weights, int P, double* rec, int64_t capacity, int slot, double* pmax, double* pmin, double* hre,
                        double* him, const double* coef, int H, void* stream) {

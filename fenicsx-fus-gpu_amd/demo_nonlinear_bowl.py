@@ -12,6 +12,7 @@ cells (G varies per quadrature point; P1 geometry, cuda/demo_nonlinear_bowl.py:3
     python fenicsx-fus-gpu_amd/demo_nonlinear_bowl.py [--degree 6] [--cells N] [--out-dir DIR] [--max-steps K]
     python fenicsx-fus-gpu_amd/demo_nonlinear_bowl.py --sensor-plane 141,241 --out-dir DIR [--peak-out FILE]   # recorded on the device
     python fenicsx-fus-gpu_amd/demo_nonlinear_bowl.py --sensor-plane 61,61 --peak-out FILE --array 6,6 --focus 0.008,0.006,0.006
+    python fenicsx-fus-gpu_amd/demo_nonlinear_bowl.py --field-stats maps.npz     # last-period maps of every dof, accumulated on the device
     python -m torch.distributed.run --nproc-per-node 8 fenicsx-fus-gpu_amd/demo_nonlinear_bowl.py
 
 Dumps: ``DIR/pressure_field_<k>.txt`` for k = 0 .. steps_per_period-1, rows ``x,y,p`` on the mid-z plane of the dof grid
@@ -50,7 +51,13 @@ def main():
     ap.add_argument("--array", default=None, metavar="NY,NZ",
                     help="with --sensor-plane: split the source face into NY x NZ elements (sources.SourceArray) with delays that focus on --focus")
     ap.add_argument("--focus", default=None, metavar="X,Y,Z", help="focal point of --array in m (default: the centre of the box)")
+    ap.add_argument("--field-stats", default=None, metavar="FILE.npz",
+                    help="accumulate the last period of EVERY owned dof on the device in ONE rk4 call (field_monitor.FieldMonitor) and "
+                         "write pmax, pmin, |H1|, |H2|, the heat deposition q and the focus of |H1| to FILE.npz (several ranks: "
+                         "FILE.rank<r>.npz each, the focus reduced over the ranks)")
     a = ap.parse_args()
+    if a.field_stats and a.sensor_plane:
+        ap.error("--field-stats and --sensor-plane are separate runs")
     if a.array and not a.sensor_plane:
         ap.error("--array needs --sensor-plane")
     if a.focus and not a.array:
@@ -147,6 +154,10 @@ def main():
         run_with_sensors(a, solver, mesh, comm, rank, world, L, float_type, t0, tf, dt, nstep, budget, t_collect, step_per_period,
                          source_frequency)
         return
+    if a.field_stats:
+        run_with_monitor(a, solver, mesh, comm, rank, world, float_type, t0, tf, dt, nstep, budget, t_collect, step_per_period,
+                         source_frequency)
+        return
     # up to the collection window in one go (no host round trip per step), then step by step with one dump per step
     n_before = min(budget, max(0, int(np.floor(t_collect / dt)) - 1))  # t stays <= the threshold: no dump is skipped
     t, steps = solver.rk4(0.0, tf, dt, max_steps=n_before) if n_before > 0 else (0.0, 0)
@@ -215,6 +226,43 @@ def run_with_sensors(a, solver, mesh, comm, rank, world, L, float_type, t0, tf, 
             keep = np.nonzero(~np.isnan(allc[0]))[0]
             rows = np.column_stack([points[keep, 0], points[keep, 1], allc[:, keep].T])
             np.savetxt(a.peak_out, rows, fmt="%.8f", delimiter=",")
+    if world > 1:
+        dist.destroy_process_group()
+
+
+def run_with_monitor(a, solver, mesh, comm, rank, world, float_type, t0, tf, dt, nstep, budget, t_collect, step_per_period, f0):
+    """The whole run in ONE rk4 call with a full-field monitor accumulating the last period on the device: the maps the reference
+    post-processes from its per-step dumps (cuda/demo_nonlinear_bowl.py:662-680), without a field copy per step."""
+    import torch
+    import torch.distributed as dist
+
+    import fusgpu_loader
+
+    fm = fusgpu_loader.submodule("field_monitor")
+    m = fm.FieldMonitor(mesh.nlocal, float_type, peak=True, mean_square=("u", "v"), harmonics=(1, 2), frequency=f0)
+    # one period and no more: the run stops steps_per_period steps after the first one that ends after t_collect
+    ends = [e for e in fm.record_times(0.0, tf, dt, budget) if not e > t_collect]
+    t, steps = solver.rk4(0.0, tf, dt, max_steps=min(budget, len(ends) + step_per_period), monitor=m, record_from=t_collect)
+    torch.cuda.synchronize()
+    el = time.perf_counter() - t0
+    out = {"nacc": m.nacc, "steps_per_period": step_per_period, "lexicographic_ids": mesh.global_lexicographic_ids()[: mesh.nlocal]}
+    if m.nacc:
+        h1 = m.harmonic_amplitude(1)
+        foc = fm.focus(h1, solver, 0.5, comm if world > 1 else None)
+        host = lambda x: x.cpu().numpy()  # noqa: E731
+        out.update(pmax=host(m.peak()[0]), pmin=host(m.peak()[1]), H1=host(h1), H2=host(m.harmonic_amplitude(2)),
+                   u_mean_square=host(m.mean_square("u")), q=host(m.heat_deposition(solver)), focus_max=foc["max"], focus_dof=foc["dof"],
+                   focus_rank=foc["rank"], focus_position=np.asarray(foc["position"] if foc["position"] is not None else [np.nan] * 3),
+                   focus_volume=foc["volume"], focus_level=foc["level"])
+    name = a.field_stats if world == 1 else f"{os.path.splitext(a.field_stats)[0]}.rank{rank}.npz"
+    np.savez(name, **out)
+    if rank == 0:
+        print(f"t: {t:5.5},\t Steps: {steps}/{nstep}", flush=True)
+        print(f"Fields accumulated over the last period: {m.nacc}/{step_per_period}")
+        if m.nacc:
+            print(f"Focus of |H1|: {out['focus_max']:.6g} Pa at {tuple(out['focus_position'])}, -6 dB volume {out['focus_volume']:.6g} m^3")
+        print(f"Solve time: {el}")
+        print(f"Solve time per step: {el / max(steps, 1)}")
     if world > 1:
         dist.destroy_process_group()
 

@@ -59,6 +59,8 @@ class WesterveltSpectral3D(SpectralSolver3D):
         self.beta = float(beta_cells.mean())
         delta_cells = compute_diffusivity_of_sound(self.w0, c_cells, att_cells)
         self.delta = float(delta_cells.mean())
+        # per cell, in the mesh's cell order: what field_monitor.heat_deposition forms kappa = delta / (rho c^4) from
+        self.delta_cells, self.rho_cells, self.c_cells = delta_cells, rho_cells, c_cells
         P, n, dev, ft = self.P, self.P + 1, self.dev, self.tdt_np
         rho, c, beta, delta = rho_cells, c_cells, beta_cells, delta_cells
         td = lambda a: torch.from_numpy(np.ascontiguousarray(np.asarray(a, dtype=ft))).to(dev)  # noqa: E731

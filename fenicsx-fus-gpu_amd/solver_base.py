@@ -190,11 +190,13 @@ class SpectralSolver3D:
         ops.copy(self.v0, self.v)
 
     # -- the time loop -----------------------------------------------------------------------------------------------------
-    def rk4(self, start_time, final_time, dt, max_steps=None, sensors=None, record_from=None):
+    def rk4(self, start_time, final_time, dt, max_steps=None, sensors=None, record_from=None, monitor=None):
         """Advance from ``start_time`` to ``final_time`` (cuda/demo_linear_box.py:487-566).
         Returns ``(t, steps)``.  ``sensors``: a ``sensors.PointSensors`` recorded after every step that ends after
-        ``record_from`` (default: every step) while its series has room -- the supported way to observe the field mid-run."""
-        gen = self.rk4_schedule(start_time, final_time, dt, max_steps, sensors, record_from)
+        ``record_from`` (default: every step) while its series has room -- the supported way to observe the field mid-run.
+        ``monitor``: a ``field_monitor.FieldMonitor`` that accumulates (u, v) over the owned dofs after the same steps (one
+        launch, no exchange); it may be given together with ``sensors``."""
+        gen = self.rk4_schedule(start_time, final_time, dt, max_steps, sensors, record_from, monitor)
         while True:
             try:
                 next(gen)
@@ -209,17 +211,19 @@ class SpectralSolver3D:
         if self.halo is not None:
             self.halo.check_health(what)
 
-    def rk4_schedule(self, start_time, final_time, dt, max_steps=None, sensors=None, record_from=None):
+    def rk4_schedule(self, start_time, final_time, dt, max_steps=None, sensors=None, record_from=None, monitor=None):
         """``rk4`` as a generator that yields whenever this rank has posted halo exchanges (see
         ``HaloApply.schedule``); its return value is ``(t, steps)``.  A driver that advances several ranks' generators
         itself calls ``check_halo_health()`` when they are exhausted (``rk4`` does).  ``u`` / ``v`` are valid only once
         the generator is exhausted (the fused path keeps the solution in ``u0`` / ``v0`` between steps): observe the field
         mid-run through ``sensors`` (see ``rk4``; on a partitioned mesh a recording step posts a forward exchange of the
-        field first, with a yield)."""
+        field first, with a yield) or, over every owned dof, through ``monitor`` (no exchange, no yield)."""
         t, step = float(start_time), 0
         rf = -np.inf if record_from is None else float(record_from)
         if sensors is not None:
             sensors.expect_steps(t, final_time, dt, max_steps, record_from)
+        if monitor is not None:
+            monitor.expect_steps(t, final_time, dt, max_steps, record_from)
         if self.fused:
             self._fused_enter()
         for t0, h in rk4_steps(t, final_time, dt, max_steps):
@@ -233,6 +237,8 @@ class SpectralSolver3D:
             t, step = t0 + h, step + 1
             if sensors is not None and t > rf and not sensors.full:
                 yield from record_schedule(sensors, self.u0 if self.fused else self.u, t, self.halo)
+            if monitor is not None and t > rf:
+                monitor.record(*((self.u0, self.v0) if self.fused else (self.u, self.v)), t)
         if self.fused:
             self._fused_exit()
         return t, step
@@ -271,11 +277,11 @@ class SpectralSolver3D:
             self._graph_plans[dt] = held
         return g
 
-    def rk4_graph(self, start_time, final_time, dt, max_steps=None, sensors=None, record_from=None):
+    def rk4_graph(self, start_time, final_time, dt, max_steps=None, sensors=None, record_from=None, monitor=None):
         """``rk4`` with the full-size steps replayed from ONE captured hipGraph.  Same kernels in the same
         order on the same data as ``rk4``.  One rank, fused path; a last shorter step runs through ``rk4``.
-        ``sensors`` / ``record_from`` as in ``rk4``: the sensor launch follows a replay on the same stream, outside the
-        captured graph.  Returns ``(t, steps)``."""
+        ``sensors`` / ``monitor`` / ``record_from`` as in ``rk4``: their launches follow a replay on the same stream, outside
+        the captured graph.  Returns ``(t, steps)``."""
         if not self.fused or self.halo is not None:
             raise _lib.FusGpuError("rk4_graph: single-rank fused path only")
         t, tf = float(start_time), float(final_time)
@@ -283,6 +289,8 @@ class SpectralSolver3D:
         rows, ends = [], []
         if sensors is not None:
             sensors.expect_steps(t, tf, dt, max_steps, record_from)
+        if monitor is not None:
+            monitor.expect_steps(t, tf, dt, max_steps, record_from)
         src = self.source
         for t0, h in rk4_steps(t, tf, dt, max_steps):
             if h != dt:
@@ -308,10 +316,12 @@ class SpectralSolver3D:
                 graph.replay()
                 if sensors is not None and ends[k] > rf and not sensors.full:
                     sensors.record(self.u0, ends[k])
+                if monitor is not None and ends[k] > rf:
+                    monitor.record(self.u0, self.v0, ends[k])
             self._fused_exit()
         steps = len(rows)
         if t < tf and (max_steps is None or steps < max_steps):
-            t, more = self.rk4(t, tf, dt, None if max_steps is None else max_steps - steps, sensors, record_from)
+            t, more = self.rk4(t, tf, dt, None if max_steps is None else max_steps - steps, sensors, record_from, monitor)
             steps += more
         return t, steps
 

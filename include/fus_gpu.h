@@ -54,7 +54,7 @@ extern "C" {
  *      fus_comm_health; the PEER blob identifies the exporting process by a random token and its device by PCI bus id.
  *      Added since without a bump (new symbols only): fus_mass_gather_plan_bytes / _build / _info, fus_mass_apply_gather_*,
  *      fus_mass_gather_plan_build_rows, fus_mass_gather_static_bytes / _build_* , fus_mass_apply_gather_static_*,
- *      fus_probe_eval_*, fus_facet_source_array_* / fus_facet_source_array_dev_*.
+ *      fus_probe_eval_*, fus_facet_source_array_* / fus_facet_source_array_dev_*, fus_field_accumulate_*.
  * There are deliberately NO fus_cpu_* twins of the entry points (SURVEY.md 8b proposed them): a CPU path inside the
  * product would be a silent fallback; the CPU restatement of the reference is test infrastructure and lives outside the product tree.
  */
@@ -201,6 +201,23 @@ int fus_probe_eval_f64(const double* u, const int32_t* cells, int64_t npts, cons
 int fus_probe_eval_f32(const float* u, const int32_t* cells, int64_t npts, const int32_t* dofmap, int64_t ncells,
                        const float* weights, int P, float* rec, int64_t capacity, int slot, double* pmax, double* pmin,
                        double* hre, double* him, const double* coef, int H, void* stream);
+
+/*
+ * Full-field monitors (csrc/field_monitor.hpp) -- replaces the reference's dump of the whole field at every step of its
+ * collection window and the host post-processing of those dumps (cuda/demo_nonlinear_bowl.py:662-680,
+ * cuda/demo_linear_piston.py).  One elementwise launch over the owned dofs [0, n) after a recorded step applies every output
+ * whose pointer is non-null:
+ *   pmax / pmin  T[n]               running maximum / minimum of u (both or neither; comparisons only)
+ *   usq / vsq    double[n]          += u^2 / += v^2   (vsq needs v: the fused time loop keeps dp/dt in its v0 between steps)
+ *   hre / him    double[H][hstride] row h: += u * coef[2h] / += u * coef[2h + 1]; coef double[2H] in DEVICE memory; 0 <= H <= 4,
+ *                                   hstride >= n (even, with 16-byte aligned pointers, for the 16-byte access path)
+ * ``init`` != 0 WRITES the outputs (pmax = pmin = u, usq = u^2, ...) instead of updating them: the first record of a window.
+ * Each dof's outputs are written by one thread: no atomics.  n == 0, or no output requested, is a no-op.
+ */
+int fus_field_accumulate_f64(const double* u, const double* v, int64_t n, double* pmax, double* pmin, double* usq, double* vsq,
+                             double* hre, double* him, int64_t hstride, const double* coef, int H, int init, void* stream);
+int fus_field_accumulate_f32(const float* u, const float* v, int64_t n, float* pmax, float* pmin, double* usq, double* vsq,
+                             double* hre, double* him, int64_t hstride, const double* coef, int H, int init, void* stream);
 
 /*
  * Opt-in fast path for AFFINE cells (reported separately from the headline, whose

@@ -80,6 +80,10 @@ struct Abi<double> {
                    int64_t cap, int slot, double* pmax, double* pmin, double* hre, double* him, const double* coef, int H, void* s) {
     return fus_probe_eval_f64(u, cells, m, dm, nc, w, P, rec, cap, slot, pmax, pmin, hre, him, coef, H, s);
   }
+  static int field(const double* u, const double* v, int64_t n, double* pmax, double* pmin, double* usq, double* vsq, double* hre, double* him,
+                   int64_t hstride, const double* coef, int H, int init, void* s) {
+    return fus_field_accumulate_f64(u, v, n, pmax, pmin, usq, vsq, hre, him, hstride, coef, H, init, s);
+  }
   static int source_array(double* y, const double* c1, const double* c2, const double* dA, const int32_t* dmA, const int32_t* eid, int64_t nA,
                           const double* a, const double* ph, const double* tau, int64_t E, const double* xB, const double* cB, const double* dB,
                           const int32_t* dmB, int64_t nB, int N, const double* stage, bool dev, void* s) {
@@ -112,6 +116,10 @@ struct Abi<float> {
   static int probe(const float* u, const int32_t* cells, int64_t m, const int32_t* dm, int64_t nc, const float* w, int P, float* rec,
                    int64_t cap, int slot, double* pmax, double* pmin, double* hre, double* him, const double* coef, int H, void* s) {
     return fus_probe_eval_f32(u, cells, m, dm, nc, w, P, rec, cap, slot, pmax, pmin, hre, him, coef, H, s);
+  }
+  static int field(const float* u, const float* v, int64_t n, float* pmax, float* pmin, double* usq, double* vsq, double* hre, double* him,
+                   int64_t hstride, const double* coef, int H, int init, void* s) {
+    return fus_field_accumulate_f32(u, v, n, pmax, pmin, usq, vsq, hre, him, hstride, coef, H, init, s);
   }
   static int source_array(float* y, const float* c1, const float* c2, const float* dA, const int32_t* dmA, const int32_t* eid, int64_t nA,
                           const double* a, const double* ph, const double* tau, int64_t E, const float* xB, const float* cB, const float* dB,
@@ -361,6 +369,31 @@ class PointProbe {
   const int32_t* dofmap_;
   int64_t ncells_;
   const T* weights_;
+};
+
+// Full-field monitors (fus_field_accumulate_*): running extrema, mean squares and harmonic sums of the owned dofs after every
+// recorded step, in place of the reference's per-step dump of the whole field (cuda/demo_nonlinear_bowl.py:662-680).  The output
+// arrays are device memory, caller-owned; a null pointer switches an output off.  ``hre`` / ``him``: [H][hstride], H <= 4.
+template <typename T>
+class FieldAccumulator {
+ public:
+  FieldAccumulator(int64_t n, T* pmax, T* pmin, double* usq, double* vsq, double* hre = nullptr, double* him = nullptr,
+                   int64_t hstride = 0, int H = 0)
+      : n_(n), pmax_(pmax), pmin_(pmin), usq_(usq), vsq_(vsq), hre_(hre), him_(him), hstride_(hstride), H_(H) {
+    check_abi();
+  }
+  // one record of (u, v); ``coef``: the 2H factors of this step in device memory; ``init``: the first record of a window
+  void operator()(const T* u, const T* v, const double* coef, bool init, void* stream = nullptr) const {
+    check(detail::Abi<T>::field(u, v, n_, pmax_, pmin_, usq_, vsq_, hre_, him_, hstride_, coef, H_, init ? 1 : 0, stream),
+          "fus_field_accumulate");
+  }
+
+ private:
+  int64_t n_;
+  T *pmax_, *pmin_;
+  double *usq_, *vsq_, *hre_, *him_;
+  int64_t hstride_;
+  int H_;
 };
 
 // Phased-array source facets (fus_facet_source_array_*): the source-facet term of one RK4 stage with a per-element amplitude,
