@@ -110,6 +110,7 @@ def _signatures():
         sig[f"fus_facet_source_array_dev_{suf}"] = [_vp] * 6 + [_i64] + [_vp] * 3 + [_i64] + [_vp] * 4 + [_i64, _int, _vp, _vp]
         sig[f"fus_probe_eval_{suf}"] = [_vp, _vp, _i64, _vp, _i64, _vp, _int, _vp, _i64, _int] + [_vp] * 5 + [_int, _vp]
         sig[f"fus_field_accumulate_{suf}"] = [_vp, _vp, _i64] + [_vp] * 6 + [_i64, _vp, _int, _int, _vp]
+        sig[f"fus_bioheat_stage_{suf}"] = [ct, ct, _int, ct, ct, C.c_double] + [_vp] * 9 + [_int, _i64, _i64, _vp]
         sig[f"fus_pack_fwd_{suf}"] = [_vp, _vp, _vp, _i64, _vp]
         sig[f"fus_unpack_fwd_{suf}"] = [_vp, _vp, _vp, _i64, _i64, _vp]
         sig[f"fus_pack_rev_{suf}"] = [_vp, _vp, _vp, _i64, _i64, _vp]

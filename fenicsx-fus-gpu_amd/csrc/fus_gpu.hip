@@ -10,6 +10,7 @@
 #include <mutex>
 #include <unordered_map>
 
+#include "bioheat.hpp"
 #include "field_monitor.hpp"
 #include "fus_dispatch.hpp"
 #include "geometry.hpp"
@@ -699,6 +700,26 @@ FUS_WESTG(float, f32)
 FUS_RK4(double, f64)
 FUS_RK4(float, f32)
 #undef FUS_RK4
+
+// Pennes bioheat stage (csrc/bioheat.hpp): every check before any device work; ntotal == 0 is a no-op
+#define FUS_BIOHEAT(T, SUF)                                                                                                   \
+  int fus_bioheat_stage_##SUF(T bw, T aw, int kind, T gate, T t_a, double dt, const T* minv, const T* pr, const T* s, T* b,   \
+                              T* T0, T* Tn, T* acc, double* cem43, T* tmax, int init, int64_t nlocal, int64_t ntotal,         \
+                              void* stream) {                                                                                 \
+    if (nlocal < 0 || ntotal < nlocal) return FUS_ERR_INVALID_ARGUMENT;                                                       \
+    if (kind < 0 || kind > 2) return FUS_ERR_INVALID_ARGUMENT;                                                                \
+    if (ntotal == 0) return FUS_OK;                                                                                           \
+    if (!minv || !b || !T0 || !Tn || !acc) return FUS_ERR_INVALID_ARGUMENT;                                                   \
+    if (misaligned(minv, sizeof(T)) || misaligned(pr, sizeof(T)) || misaligned(s, sizeof(T)) || misaligned(b, sizeof(T)) ||   \
+        misaligned(T0, sizeof(T)) || misaligned(Tn, sizeof(T)) || misaligned(acc, sizeof(T)) ||                               \
+        misaligned(cem43, sizeof(double)) || misaligned(tmax, sizeof(T)))                                                     \
+      return FUS_ERR_INVALID_ARGUMENT;                                                                                        \
+    return hip_rc(fus::launch_bioheat_stage<T>(bw, aw, kind, gate, t_a, dt, minv, pr, s, b, T0, Tn, acc, cem43, tmax,         \
+                                               init != 0, nlocal, ntotal, static_cast<hipStream_t>(stream)));                 \
+  }
+FUS_BIOHEAT(double, f64)
+FUS_BIOHEAT(float, f32)
+#undef FUS_BIOHEAT
 #undef FUS_VEC
 
 // ------------------------------------------------------------------ communicator + halo exchange

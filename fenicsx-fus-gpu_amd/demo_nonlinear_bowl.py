@@ -13,6 +13,7 @@ cells (G varies per quadrature point; P1 geometry, cuda/demo_nonlinear_bowl.py:3
     python fenicsx-fus-gpu_amd/demo_nonlinear_bowl.py --sensor-plane 141,241 --out-dir DIR [--peak-out FILE]   # recorded on the device
     python fenicsx-fus-gpu_amd/demo_nonlinear_bowl.py --sensor-plane 61,61 --peak-out FILE --array 6,6 --focus 0.008,0.006,0.006
     python fenicsx-fus-gpu_amd/demo_nonlinear_bowl.py --field-stats maps.npz     # last-period maps of every dof, accumulated on the device
+    python fenicsx-fus-gpu_amd/demo_nonlinear_bowl.py --thermal 10 20            # then heat for 10 s and cool for 20 s with the last period's q (bioheat.py)
     python -m torch.distributed.run --nproc-per-node 8 fenicsx-fus-gpu_amd/demo_nonlinear_bowl.py
 
 Dumps: ``DIR/pressure_field_<k>.txt`` for k = 0 .. steps_per_period-1, rows ``x,y,p`` on the mid-z plane of the dof grid
@@ -55,8 +56,14 @@ def main():
                     help="accumulate the last period of EVERY owned dof on the device in ONE rk4 call (field_monitor.FieldMonitor) and "
                          "write pmax, pmin, |H1|, |H2|, the heat deposition q and the focus of |H1| to FILE.npz (several ranks: "
                          "FILE.rank<r>.npz each, the focus reduced over the ranks)")
+    ap.add_argument("--thermal", default=None, nargs="+", type=float, metavar=("SECONDS_ON", "SECONDS_OFF"),
+                    help="implies --field-stats (without a FILE.npz nothing is written): after the acoustic run, heat soft tissue for SECONDS_ON "
+                         "with the heat deposition q of the last period and cool it for SECONDS_OFF (bioheat.BioheatSpectral3D: Pennes' equation, "
+                         "CEM43 thermal dose); prints the peak temperature, the focus of the dose and the volume above 240 CEM43")
     a = ap.parse_args()
-    if a.field_stats and a.sensor_plane:
+    if a.thermal is not None and (len(a.thermal) > 2 or min(a.thermal) < 0.0):
+        ap.error("--thermal SECONDS_ON [SECONDS_OFF], both >= 0")
+    if (a.field_stats or a.thermal) and a.sensor_plane:
         ap.error("--field-stats and --sensor-plane are separate runs")
     if a.array and not a.sensor_plane:
         ap.error("--array needs --sensor-plane")
@@ -154,7 +161,7 @@ def main():
         run_with_sensors(a, solver, mesh, comm, rank, world, L, float_type, t0, tf, dt, nstep, budget, t_collect, step_per_period,
                          source_frequency)
         return
-    if a.field_stats:
+    if a.field_stats or a.thermal:
         run_with_monitor(a, solver, mesh, comm, rank, world, float_type, t0, tf, dt, nstep, budget, t_collect, step_per_period,
                          source_frequency)
         return
@@ -254,8 +261,9 @@ def run_with_monitor(a, solver, mesh, comm, rank, world, float_type, t0, tf, dt,
                    u_mean_square=host(m.mean_square("u")), q=host(m.heat_deposition(solver)), focus_max=foc["max"], focus_dof=foc["dof"],
                    focus_rank=foc["rank"], focus_position=np.asarray(foc["position"] if foc["position"] is not None else [np.nan] * 3),
                    focus_volume=foc["volume"], focus_level=foc["level"])
-    name = a.field_stats if world == 1 else f"{os.path.splitext(a.field_stats)[0]}.rank{rank}.npz"
-    np.savez(name, **out)
+    if a.field_stats:
+        name = a.field_stats if world == 1 else f"{os.path.splitext(a.field_stats)[0]}.rank{rank}.npz"
+        np.savez(name, **out)
     if rank == 0:
         print(f"t: {t:5.5},\t Steps: {steps}/{nstep}", flush=True)
         print(f"Fields accumulated over the last period: {m.nacc}/{step_per_period}")
@@ -263,8 +271,35 @@ def run_with_monitor(a, solver, mesh, comm, rank, world, float_type, t0, tf, dt,
             print(f"Focus of |H1|: {out['focus_max']:.6g} Pa at {tuple(out['focus_position'])}, -6 dB volume {out['focus_volume']:.6g} m^3")
         print(f"Solve time: {el}")
         print(f"Solve time per step: {el / max(steps, 1)}")
+    if a.thermal and m.nacc:
+        run_thermal(a, solver, m, mesh, comm, rank, world, float_type)
     if world > 1:
         dist.destroy_process_group()
+
+
+def run_thermal(a, solver, monitor, mesh, comm, rank, world, float_type):
+    """Pressure -> heat -> temperature -> dose on the same mesh and partition: the heat deposition of the last period drives Pennes'
+    equation (soft tissue, insulated boundaries) for SECONDS_ON, then the tissue cools for SECONDS_OFF; nothing leaves the device
+    but the printed figures."""
+    import fusgpu_loader
+
+    fm, bh = fusgpu_loader.submodule("field_monitor"), fusgpu_loader.submodule("bioheat")
+    th = bh.BioheatSpectral3D(mesh, float_type, comm=comm)
+    th.set_heat_source(bh.heat_source_from(monitor, solver, th))
+    dt = th.stable_time_step()
+    t_on, t_off = a.thermal[0], (a.thermal[1] if len(a.thermal) > 1 else 0.0)
+    t, steps = th.advance(0.0, t_on, dt)
+    if t_off > 0.0:
+        t, more = th.advance(t_on, t_on + t_off, dt, power=(0.0, 0.0))
+        steps += more
+    reduce = comm if world > 1 else None
+    peak = fm.focus(th.peak_temperature(), th, 1.0, reduce)
+    dose = fm.focus(th.cem43(), th, 0.5, reduce)
+    lesion = fm.focus(th.cem43(), th, 240.0 / dose["max"], reduce)["volume"] if dose["max"] >= 240.0 else 0.0
+    if rank == 0:
+        print(f"Thermal steps: {steps} of {dt:.6g} s ({t_on:g} s on, {t_off:g} s off)")
+        print(f"Focus of cem43: {dose['max']:.6g} min at {dose['position']}, half-maximum volume {dose['volume']:.6g} m^3")
+        print(f"thermal: peak temperature={peak['max']:.6f} degC, max cem43={dose['max']:.6g} min, volume above 240 cem43={lesion:.6g} m^3")
 
 
 if __name__ == "__main__":

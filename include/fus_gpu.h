@@ -54,7 +54,8 @@ extern "C" {
  *      fus_comm_health; the PEER blob identifies the exporting process by a random token and its device by PCI bus id.
  *      Added since without a bump (new symbols only): fus_mass_gather_plan_bytes / _build / _info, fus_mass_apply_gather_*,
  *      fus_mass_gather_plan_build_rows, fus_mass_gather_static_bytes / _build_* , fus_mass_apply_gather_static_*,
- *      fus_probe_eval_*, fus_facet_source_array_* / fus_facet_source_array_dev_*, fus_field_accumulate_*.
+ *      fus_probe_eval_*, fus_facet_source_array_* / fus_facet_source_array_dev_*, fus_field_accumulate_*,
+ *      fus_bioheat_stage_*.
  * There are deliberately NO fus_cpu_* twins of the entry points (SURVEY.md 8b proposed them): a CPU path inside the
  * product would be a silent fallback; the CPU restatement of the reference is test infrastructure and lives outside the product tree.
  */
@@ -218,6 +219,28 @@ int fus_field_accumulate_f64(const double* u, const double* v, int64_t n, double
                              double* hre, double* him, int64_t hstride, const double* coef, int H, int init, void* stream);
 int fus_field_accumulate_f32(const float* u, const float* v, int64_t n, float* pmax, float* pmin, double* usq, double* vsq,
                              double* hre, double* him, int64_t hstride, const double* coef, int H, int init, void* stream);
+
+/*
+ * Pennes bioheat stage (csrc/bioheat.hpp): the vector pass between two stiffness applies of an explicit RK4 step of
+ *   M(rho C) dT/dt = -K(k) T - M(w_b rho_b C_b)(T - T_a) + g(t) M(1) q       (GLL collocation: every mass is diagonal)
+ * with b = -K(k) Tn already assembled:  k = minv b - pr (Tn - t_a) + gate s  per owned dof, minv = 1 / M(rho C) 1,
+ * pr = M(w_b rho_b C_b) 1 minv, s = M(1) 1 q minv (pr, s: NULL switches the term off).  bw = b_i dt, aw = a_{i+1} dt.  ``kind``:
+ *   0 FIRST   (Tn of this stage is T0 itself)  acc = T0 + bw k ; Tn = T0 + aw k
+ *   1 MIDDLE                                   acc += bw k     ; Tn = T0 + aw k
+ *   2 LAST                                     T0 = acc + bw k, then from the new T0 (the step's end temperature, deg C)
+ *        cem43 double[nlocal] (minutes)  += (dt / 60) R^(43 - T0), R = 0.5 for T0 >= 43, 0.25 below    (NULL: off)
+ *        tmax  T[nlocal]                  = max(tmax, T0)                                                (NULL: off)
+ *      ``init`` != 0 WRITES cem43 and tmax instead of updating them (the first step of a dose window).
+ * Updates run over [0, nlocal); b is re-zeroed over [0, ntotal) in every kind.  cem43 / tmax / init are ignored unless kind == 2.
+ * FUS_ERR_INVALID_ARGUMENT for a null minv, b, T0, Tn or acc, a negative size, nlocal > ntotal or another kind; ntotal == 0 is a
+ * no-op.  Each dof is written by one thread: no atomics.  No reference counterpart (the reference stops at the acoustic field).
+ */
+int fus_bioheat_stage_f64(double bw, double aw, int kind, double gate, double t_a, double dt, const double* minv, const double* pr,
+                          const double* s, double* b, double* T0, double* Tn, double* acc, double* cem43, double* tmax, int init,
+                          int64_t nlocal, int64_t ntotal, void* stream);
+int fus_bioheat_stage_f32(float bw, float aw, int kind, float gate, float t_a, double dt, const float* minv, const float* pr,
+                          const float* s, float* b, float* T0, float* Tn, float* acc, double* cem43, float* tmax, int init,
+                          int64_t nlocal, int64_t ntotal, void* stream);
 
 /*
  * Opt-in fast path for AFFINE cells (reported separately from the headline, whose

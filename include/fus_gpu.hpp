@@ -84,6 +84,10 @@ struct Abi<double> {
                    int64_t hstride, const double* coef, int H, int init, void* s) {
     return fus_field_accumulate_f64(u, v, n, pmax, pmin, usq, vsq, hre, him, hstride, coef, H, init, s);
   }
+  static int bioheat(double bw, double aw, int kind, double gate, double ta, double dt, const double* minv, const double* pr, const double* s, double* b, double* T0, double* Tn, double* acc,
+                     double* cem43, double* tmax, int init, int64_t nlocal, int64_t ntotal, void* st) {
+    return fus_bioheat_stage_f64(bw, aw, kind, gate, ta, dt, minv, pr, s, b, T0, Tn, acc, cem43, tmax, init, nlocal, ntotal, st);
+  }
   static int source_array(double* y, const double* c1, const double* c2, const double* dA, const int32_t* dmA, const int32_t* eid, int64_t nA,
                           const double* a, const double* ph, const double* tau, int64_t E, const double* xB, const double* cB, const double* dB,
                           const int32_t* dmB, int64_t nB, int N, const double* stage, bool dev, void* s) {
@@ -120,6 +124,10 @@ struct Abi<float> {
   static int field(const float* u, const float* v, int64_t n, float* pmax, float* pmin, double* usq, double* vsq, double* hre, double* him,
                    int64_t hstride, const double* coef, int H, int init, void* s) {
     return fus_field_accumulate_f32(u, v, n, pmax, pmin, usq, vsq, hre, him, hstride, coef, H, init, s);
+  }
+  static int bioheat(float bw, float aw, int kind, float gate, float ta, double dt, const float* minv, const float* pr, const float* s, float* b, float* T0, float* Tn, float* acc,
+                     double* cem43, float* tmax, int init, int64_t nlocal, int64_t ntotal, void* st) {
+    return fus_bioheat_stage_f32(bw, aw, kind, gate, ta, dt, minv, pr, s, b, T0, Tn, acc, cem43, tmax, init, nlocal, ntotal, st);
   }
   static int source_array(float* y, const float* c1, const float* c2, const float* dA, const int32_t* dmA, const int32_t* eid, int64_t nA,
                           const double* a, const double* ph, const double* tau, int64_t E, const float* xB, const float* cB, const float* dB,
@@ -394,6 +402,37 @@ class FieldAccumulator {
   double *usq_, *vsq_, *hre_, *him_;
   int64_t hstride_;
   int H_;
+};
+
+// Pennes bioheat stage (fus_bioheat_stage_*): the vector pass between two stiffness applies of an explicit RK4 step of
+// M(rho C) T' = -K(k) T - M(w)(T - Ta) + g M(1) q with b = -K(k) Tn assembled: k = minv b - pr (Tn - Ta) + gate s per owned dof.
+// ``pr`` / ``s`` / ``cem43`` / ``tmax`` may be null (term off).  Device arrays, caller-owned: T0, Tn, acc, b [ntotal]; the rest [nlocal].
+template <typename T>
+class BioheatStage {
+ public:
+  enum Kind { FIRST = 0, MIDDLE = 1, LAST = 2 };
+  BioheatStage(int64_t nlocal, int64_t ntotal, T arterial_temperature, const T* minv, const T* pr, const T* s, T* b, T* T0, T* Tn, T* acc,
+               double* cem43 = nullptr, T* tmax = nullptr)
+      : nlocal_(nlocal), ntotal_(ntotal), ta_(arterial_temperature), minv_(minv), pr_(pr), s_(s), b_(b), T0_(T0), Tn_(Tn), acc_(acc),
+        cem43_(cem43), tmax_(tmax) {
+    check_abi();
+  }
+  // stage ``i`` in 0..3 of the step of length ``dt``; ``gate``: g at the stage time; ``init`` (stage 3): the first step of a dose window
+  void operator()(int i, double dt, T gate, bool init = false, void* stream = nullptr) const {
+    static const double a[4] = {0.0, 0.5, 0.5, 1.0}, bq[4] = {1.0 / 6.0, 1.0 / 3.0, 1.0 / 3.0, 1.0 / 6.0};
+    const int kind = i == 3 ? LAST : (i == 0 ? FIRST : MIDDLE);
+    check(detail::Abi<T>::bioheat((T)(bq[i] * dt), (T)(i == 3 ? 0.0 : a[i + 1] * dt), kind, gate, ta_, dt, minv_, pr_, s_, b_, T0_, Tn_, acc_,
+                                  cem43_, tmax_, init ? 1 : 0, nlocal_, ntotal_, stream),
+          "fus_bioheat_stage");
+  }
+
+ private:
+  int64_t nlocal_, ntotal_;
+  T ta_;
+  const T *minv_, *pr_, *s_;
+  T *b_, *T0_, *Tn_, *acc_;
+  double* cem43_;
+  T* tmax_;
 };
 
 // Phased-array source facets (fus_facet_source_array_*): the source-facet term of one RK4 stage with a per-element amplitude,
