@@ -36,7 +36,7 @@ import torch
 from . import _lib
 from . import operators as ops
 from .gll import gll_points_weights, tensor_weights_3d
-from .solver_base import A_RUNGE, B_RUNGE, C_RUNGE, device_geometry, per_cell, rk4_steps
+from .solver_base import A_RUNGE, B_RUNGE, C_RUNGE, device_geometry, per_cell, rk4_steps, run_schedule
 
 # |1 - z + z^2/2 - z^3/6 + z^4/24| = 1: the stability limit of classical RK4 on the negative real axis
 RK4_REAL_AXIS_LIMIT = 2.785
@@ -285,13 +285,9 @@ class BioheatSpectral3D:
         ``power``: see ``parse_power``.  The step is not checked against ``stable_time_step``; one warning if it exceeds the
         unscaled limit, where an earlier ``stable_time_step`` call has made that limit known (``advance`` never computes it)."""
         gate = parse_power(power)
-        gen = self.advance_schedule(start_time, final_time, dt, gate, max_steps)
-        while True:
-            try:
-                next(gen)
-            except StopIteration as done:
-                self.check_halo_health("BioheatSpectral3D.advance")
-                return done.value
+        result = run_schedule(self.advance_schedule(start_time, final_time, dt, gate, max_steps))
+        self.check_halo_health("BioheatSpectral3D.advance")
+        return result
 
     def advance_schedule(self, start_time, final_time, dt, power=None, max_steps=None):
         """``advance`` as a generator that yields whenever this rank has posted halo exchanges (``HaloApply.schedule``); its
@@ -372,13 +368,9 @@ class BioheatSpectral3D:
         Lanczos recurrence in the ``M(rho C)`` inner product: same applies, two more dot products each) -- the quotient of the
         last iterate alone settles to 1 % while still 9 % short on a 3 x 2 x 2 mesh of degree 2.  At least 16 applies, then
         until two successive values agree to 1 %; raises after 200.  Every estimate is a lower bound of ``lambda_max``."""
-        gen = self.stable_time_step_schedule(safety)
-        while True:
-            try:
-                next(gen)
-            except StopIteration as done:
-                self.check_halo_health("BioheatSpectral3D.stable_time_step")
-                return done.value
+        dt = run_schedule(self.stable_time_step_schedule(safety))
+        self.check_halo_health("BioheatSpectral3D.stable_time_step")
+        return dt
 
 
 def heat_source_from(monitor, wave_solver, thermal_solver=None):

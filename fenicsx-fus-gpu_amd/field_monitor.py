@@ -10,6 +10,9 @@ does this on the device for a list of points; a ``FieldMonitor`` does it for eve
     solver.rk4(t0, tf, dt, monitor=m, record_from=tf - period)
     m.peak(), m.mean_square("v"), m.harmonic_amplitude(2)      # device tensors [nlocal]: the caller decides what to copy
 
+Which steps are recorded and their harmonic factors on the device come from ``recording.py``, as for the sensors: no record blocks
+the host.
+
 ``v = dp/dt`` is not observable mid-run otherwise (the fused step keeps it in ``v0``); its mean square is what the absorbed power
 density of the Westervelt model needs, ``q = delta / (rho c^4) <(dp/dt)^2>`` (``heat_deposition``; ``2 alpha I`` for a harmonic
 wave).  ``focus`` finds the maximum of a map and the volume above a fraction of it.
@@ -17,22 +20,11 @@ wave).  ``focus`` finds the maximum of a map and the volume above a fraction of 
 
 from __future__ import annotations
 
-import io
-
 import numpy as np
 
-from .sensors import _coefficient_rows, harmonic_coefficients
+from .recording import HarmonicFactors, record_times  # noqa: F401  (record_times: re-exported)
 
 MAX_HARMONICS = 4  # csrc/field_monitor.hpp: the harmonic count is a template parameter of the kernel
-
-
-def record_times(start_time, final_time, dt, max_steps=None, record_from=None):
-    """The end times of the steps an ``rk4(start_time, final_time, dt, max_steps)`` call records: those of
-    ``solver_base.rk4_steps`` that end after ``record_from`` (the sums ``t + dt`` the time loop forms, bitwise)."""
-    from .solver_base import rk4_steps
-
-    rf = -np.inf if record_from is None else float(record_from)
-    return [t + h for t, h in rk4_steps(start_time, final_time, dt, max_steps) if t + h > rf]
 
 
 class FieldMonitor:
@@ -57,12 +49,11 @@ class FieldMonitor:
         if any(w not in ("u", "v") for w in ms):
             raise ValueError(f"mean_square: any of 'u', 'v', got {ms}")
         self.squares = tuple(w for w in ("u", "v") if w in ms)
-        self.harmonics = tuple(int(k) for k in harmonics)
-        if len(self.harmonics) > MAX_HARMONICS:
-            raise ValueError(f"at most {MAX_HARMONICS} harmonics per monitor, got {len(self.harmonics)}")
-        if self.harmonics and frequency is None:
-            raise ValueError("harmonics need the fundamental frequency")
-        self.omega = 2.0 * np.pi * float(frequency) if frequency is not None else None
+        harmonics = tuple(harmonics)
+        if len(harmonics) > MAX_HARMONICS:
+            raise ValueError(f"at most {MAX_HARMONICS} harmonics per monitor, got {len(harmonics)}")
+        self.factors = HarmonicFactors(harmonics, frequency)
+        self.harmonics, self.omega = self.factors.harmonics, self.factors.omega
         dev = torch.device("cuda", torch.cuda.current_device())
         self.dev = dev
         n, H = self.nlocal, len(self.harmonics)
@@ -74,7 +65,6 @@ class FieldMonitor:
         self._vsq = torch.empty(n, dtype=torch.float64, device=dev) if "v" in self.squares else None
         self._hre = torch.empty((H, self.npad), dtype=torch.float64, device=dev) if H else None
         self._him = torch.empty((H, self.npad), dtype=torch.float64, device=dev) if H else None
-        self._plan_t, self._plan_i, self._table, self._table_host, self._table_ev = np.zeros(0), 0, None, None, None
         self._fn = getattr(_lib.load(), f"fus_field_accumulate_{_lib.suffix(self.tdt)}")
         self.nacc = 0
 
@@ -84,27 +74,11 @@ class FieldMonitor:
 
     def expect_steps(self, start_time, final_time, dt, max_steps=None, record_from=None):
         """Upload, in one copy, the harmonic factors of every step an ``rk4(start_time, final_time, dt, max_steps)`` call will
-        record (the steps of ``solver_base.rk4_steps`` that end after ``record_from``), as ``PointSensors.expect_steps`` does."""
-        import torch
-
-        if not self.harmonics:
-            return
-        ends = record_times(start_time, final_time, dt, max_steps, record_from)
-        if self._table_ev is not None:
-            self._table_ev.synchronize()  # the previous table's host rows: copied long ago, normally
-        self._plan_t, self._plan_i = np.asarray(ends), 0
-        if not ends:
-            self._table = self._table_host = self._table_ev = None
-            return
-        self._table_host = torch.from_numpy(_coefficient_rows(self.harmonics, self.omega, ends)).pin_memory()
-        self._table = self._table_host.to(self.dev, non_blocking=True)
-        self._table_ev = torch.cuda.Event()
-        self._table_ev.record()
+        record (``recording.record_times``: the steps that end after ``record_from``), as ``PointSensors.expect_steps`` does."""
+        self.factors.plan(record_times(start_time, final_time, dt, max_steps, record_from))
 
     def record(self, u, v=None, t=0.0):
         """One launch: the owned dofs of ``u`` (and ``v``, for its mean square) at time ``t`` into every accumulator."""
-        import torch
-
         self._lib.require_device_tensor(u, self.tdt, "u")
         if u.numel() < self.nlocal:
             raise ValueError(f"u: {u.numel()} values, the monitor covers {self.nlocal} owned dofs")
@@ -114,13 +88,7 @@ class FieldMonitor:
             self._lib.require_device_tensor(v, self.tdt, "v")
             if v.numel() < self.nlocal:
                 raise ValueError(f"v: {v.numel()} values, the monitor covers {self.nlocal} owned dofs")
-        H, coef = len(self.harmonics), None
-        if H:
-            if self._plan_i < self._plan_t.size and self._plan_t[self._plan_i] == t:  # factors uploaded by expect_steps
-                coef = self._table[self._plan_i]
-                self._plan_i += 1
-            else:  # a record outside a planned rk4 call: this step's factors in a copy of their own
-                coef = torch.from_numpy(harmonic_coefficients(self.harmonics, self.omega, t)).to(self.dev)
+        coef, H = self.factors.row(t), len(self.harmonics)
         ptr = lambda x: None if x is None else x.data_ptr()  # noqa: E731
         self._lib.check(
             self._fn(ptr(u), ptr(v) if self._vsq is not None else None, self.nlocal, ptr(self._pmax), ptr(self._pmin), ptr(self._usq),
@@ -204,14 +172,6 @@ def lumped_mass_schedule(solver, cell_constants):
     return out[: solver.nlocal].to(torch.float64)
 
 
-def _run(gen):
-    while True:
-        try:
-            next(gen)
-        except StopIteration as done:
-            return done.value
-
-
 def dof_volumes_schedule(solver):
     """Generator: ``vol = M(1) 1``, the volume each owned dof stands for (kept on the solver once formed)."""
     vol = getattr(solver, "_dof_volumes", None)
@@ -222,7 +182,9 @@ def dof_volumes_schedule(solver):
 
 
 def dof_volumes(solver):
-    return _run(dof_volumes_schedule(solver))
+    from .solver_base import run_schedule
+
+    return run_schedule(dof_volumes_schedule(solver))
 
 
 def heat_deposition_schedule(monitor, solver):
@@ -241,7 +203,9 @@ def heat_deposition(monitor, solver):
     """The absorbed power density ``q = M(kappa) <v^2> / M(1) 1`` with ``kappa = delta / (rho c^4)`` per cell: the lumped-mass
     projection of ``kappa <(dp/dt)^2>``, well defined where the materials jump between cells (with GLL collocation
     ``M(kappa) x = diag(M(kappa) 1) x``).  Device tensor [nlocal], fp64."""
-    return _run(heat_deposition_schedule(monitor, solver))
+    from .solver_base import run_schedule
+
+    return run_schedule(heat_deposition_schedule(monitor, solver))
 
 
 def _focus_local(field, solver, level, vol):
@@ -277,18 +241,10 @@ def focus(field, solver, level=0.5, comm=None):
     size = int(getattr(comm, "size", 1)) if comm is not None else 1
     if size == 1:
         return rec
-    boot = getattr(comm, "_torch", None) if hasattr(comm, "handle") else comm  # NativeComm: its bootstrap
-    if boot is None or not hasattr(boot, "allgather_bytes"):
-        raise ValueError("focus: this communicator has no bootstrap (ranks in one process): use merge_focus")
+    from .scatterer import gather_arrays
 
     def gather(d):
-        buf = io.BytesIO()
-        np.savez(buf, **{k: np.asarray(v, dtype=np.float64) for k, v in d.items()})
-        out = []
-        for blob in boot.allgather_bytes(buf.getvalue()):
-            with np.load(io.BytesIO(blob), allow_pickle=False) as z:
-                out.append({k: z[k] for k in z.files})
-        return out
+        return gather_arrays(comm, {k: np.asarray(v, dtype=np.float64) for k, v in d.items()}, "focus", "merge_focus")
 
     pos = rec["position"] if rec["position"] is not None else (np.nan,) * 3
     every = gather({"max": rec["max"], "dof": rec["dof"], "rank": rec["rank"], "position": pos})

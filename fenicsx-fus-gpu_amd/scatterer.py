@@ -38,6 +38,8 @@ MI355X-first differences from the reference:
 
 from __future__ import annotations
 
+import io
+
 import numpy as np
 import torch
 import torch.distributed as dist
@@ -409,6 +411,21 @@ def as_comm(comm):
         return comm  # a TorchComm-shaped object (tests, bench.py's staged rehearsal communicator)
     raise TypeError(f"comm: expected a NativeComm, a TorchComm, or an MPI communicator (mpi4py.MPI.Comm: Get_rank / Get_size / allgather / "
                     f"alltoall / bcast), got {type(comm).__name__}")
+
+
+def gather_arrays(comm, arrays, what, instead):
+    """The named numpy ``arrays`` of every rank through the communicator's bootstrap (``allgather_bytes``): one dict per rank, in
+    rank order.  Ranks driven from one process have none: ``ValueError`` naming the caller (``what``) and what to use ``instead``."""
+    boot = getattr(comm, "_torch", None) if hasattr(comm, "handle") else comm  # NativeComm: its bootstrap
+    if boot is None or not hasattr(boot, "allgather_bytes"):
+        raise ValueError(f"{what}: this communicator has no bootstrap (ranks in one process): use {instead}")
+    buf = io.BytesIO()
+    np.savez(buf, **arrays)
+    out = []
+    for blob in boot.allgather_bytes(buf.getvalue()):
+        with np.load(io.BytesIO(blob), allow_pickle=False) as z:
+            out.append({k: z[k] for k in z.files})
+    return out
 
 
 class _NativeScatter:

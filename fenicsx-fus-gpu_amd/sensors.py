@@ -6,7 +6,8 @@ The reference keeps its output on the host: per step of its collection window it
 dolfinx's ``Function.eval`` at the points ``compute_eval_params`` found once (cuda/utils.py:117-154,
 cuda/demo_linear_piston.py, cuda/demo_nonlinear_bowl.py:662-680: ``u_n_.eval(x_eval, cell_eval)``).  Here the points are
 located once on the host (``point_evaluation.CellLocator`` + its Newton inversion, the same arithmetic as
-``eval_function``), their 1-D Lagrange rows are tabulated once, and each step costs one small launch inside ``rk4``:
+``eval_function``), their 1-D Lagrange rows are tabulated once, and each step costs one small launch inside ``rk4``
+(which steps, and their harmonic factors on the device: ``recording.py``, shared with ``field_monitor.FieldMonitor``):
 
     s = PointSensors(mesh, points, np.float64, capacity=steps_per_period, peak=True, harmonics=(1, 2), frequency=f0)
     solver.rk4(t0, tf, dt, sensors=s, record_from=tf - period)
@@ -20,15 +21,13 @@ that several hold.
 
 from __future__ import annotations
 
-import io
 from dataclasses import dataclass
 
 import numpy as np
 
 from .gll import gll_points_weights
 from .point_evaluation import CellLocator, _invert, _lagrange_1d
-
-_RING = 64  # pinned host rows of per-step harmonic coefficients in flight (record() never synchronises the host)
+from .recording import HarmonicFactors, harmonic_coefficients, record_times  # noqa: F401  (harmonic_coefficients: re-exported)
 
 
 @dataclass
@@ -79,21 +78,6 @@ def sensor_setup(mesh, points, locator=None) -> SensorSetup:
     return SensorSetup(ids.astype(np.int64), p, cells, cell_index.astype(np.int32).reshape(-1), rows, w)
 
 
-def harmonic_coefficients(harmonics, omega, t):
-    """The per-step factors of the harmonic accumulators: ``[cos(k w t), -sin(k w t)]`` for each ``k``, so that the
-    accumulators hold ``sum_t p(t) e^{-i k w t}``."""
-    k = np.asarray(harmonics, dtype=np.float64).reshape(-1)
-    ph = k * float(omega) * float(t)
-    return np.stack([np.cos(ph), -np.sin(ph)], axis=1).reshape(-1)
-
-
-def _coefficient_rows(harmonics, omega, times):
-    """``harmonic_coefficients`` of every time in ``times``, [len(times), 2H] (the same operations, vectorised)."""
-    k = np.asarray(harmonics, dtype=np.float64).reshape(-1)
-    ph = (k * float(omega))[None, :] * np.asarray(times, dtype=np.float64)[:, None]
-    return np.ascontiguousarray(np.stack([np.cos(ph), -np.sin(ph)], axis=2).reshape(ph.shape[0], -1))
-
-
 def merge(per_rank, npoints=None):
     """``per_rank``: ``[(point_ids, values), ...]`` in rank order, ``values`` with the points on the LAST axis.  Returns
     ``values`` over the global point list (``npoints`` columns, default: the largest id + 1); a point held by several
@@ -130,12 +114,10 @@ class PointSensors:
         self.tdt_np = np.dtype(float_type)
         self.tdt = _lib.torch_dtype(float_type)
         self.capacity = int(capacity)
-        self.harmonics = tuple(int(k) for k in harmonics)
         if self.capacity < 0:
             raise ValueError("capacity must be >= 0")
-        if self.harmonics and frequency is None:
-            raise ValueError("harmonics need the fundamental frequency")
-        self.omega = 2.0 * np.pi * float(frequency) if frequency is not None else None
+        self.factors = HarmonicFactors(harmonics, frequency)
+        self.harmonics, self.omega = self.factors.harmonics, self.factors.omega
         if self.setup.rows.size and int(self.setup.rows.max()) >= self.ndofs:
             raise ValueError("dofmap row outside the local vector")
         dev = torch.device("cuda", torch.cuda.current_device())
@@ -151,11 +133,6 @@ class PointSensors:
         self._pmin = torch.empty(m, dtype=torch.float64, device=dev) if peak else None
         self._hre = torch.empty((H, m), dtype=torch.float64, device=dev) if H else None
         self._him = torch.empty((H, m), dtype=torch.float64, device=dev) if H else None
-        self._coef = torch.zeros(2 * H, dtype=torch.float64, device=dev) if H else None
-        self._ring = torch.zeros((_RING, 2 * H), dtype=torch.float64).pin_memory() if H else None
-        self._ring_ev = [None] * _RING
-        self._ri = 0
-        self._plan_t, self._plan_i, self._table, self._table_host, self._table_ev = np.zeros(0), 0, None, None, None
         self._fn = getattr(_lib.load(), f"fus_probe_eval_{_lib.suffix(self.tdt)}")
         self.reset()
 
@@ -202,63 +179,18 @@ class PointSensors:
 
     def expect_steps(self, start_time, final_time, dt, max_steps=None, record_from=None):
         """Upload, in one copy, the harmonic factors of every step an ``rk4(start_time, final_time, dt, max_steps)`` call
-        will record (its steps: ``solver_base.rk4_steps``; those that end after ``record_from``, while the series has room).
-        ``record`` then reads them from this table instead of copying each step's factors (the solvers call this at the
-        start of ``rk4``; a per-step copy ordered between the launches of a step costs more than the sensor launch)."""
-        import torch
-
-        from .solver_base import rk4_steps
-
-        if not self.harmonics:
-            return
-        rf = -np.inf if record_from is None else float(record_from)
+        will record (``recording.record_times``: the steps that end after ``record_from``, while the series has room);
+        ``record`` then reads them from that table.  The solvers call this at the start of ``rk4``."""
         room = self.capacity - self.nrec if self.capacity else 1 << 16
-        ends = []
-        for t, h in rk4_steps(start_time, final_time, dt, max_steps):
-            if len(ends) >= room:
-                break
-            if t + h > rf:
-                ends.append(t + h)
-        if self._table_ev is not None:
-            self._table_ev.synchronize()  # the previous table's host rows: copied long ago, normally
-        self._plan_t, self._plan_i = np.asarray(ends), 0
-        if not ends:
-            self._table = self._table_host = self._table_ev = None
-            return
-        rows = _coefficient_rows(self.harmonics, self.omega, ends)
-        self._table_host = torch.from_numpy(rows).pin_memory()
-        self._table = self._table_host.to(self.dev, non_blocking=True)
-        self._table_ev = torch.cuda.Event()
-        self._table_ev.record()
+        self.factors.plan(record_times(start_time, final_time, dt, max_steps, record_from, limit=room))
 
     def record(self, u, t):
         """One launch: row ``nrec`` of the series, the peaks and the harmonic terms of the field ``u`` at time ``t``."""
-        import torch
-
         self._check_field(u)
         if self.full:
             raise ValueError(f"record: the series is full ({self.capacity} rows)")
-        H = len(self.harmonics)
-        if H and self._plan_i < self._plan_t.size and self._plan_t[self._plan_i] == t:  # factors uploaded by expect_steps
-            coef = self._table[self._plan_i]
-            self._plan_i += 1
-            self._launch(u, self._rec, self.capacity, self.nrec, self._pmax, self._pmin, self._hre, self._him, coef, H)
-            if self._rec is not None:
-                self.nrec += 1
-            self.nacc += 1
-            return
-        if H:
-            # this step's factors: a pinned row (reused once its copy has run) -> the device array the kernel reads
-            k = self._ri
-            self._ri = (k + 1) % _RING
-            if self._ring_ev[k] is not None:
-                self._ring_ev[k].synchronize()
-            self._ring[k].copy_(torch.from_numpy(harmonic_coefficients(self.harmonics, self.omega, t)))
-            self._coef.copy_(self._ring[k], non_blocking=True)
-            ev = torch.cuda.Event()
-            ev.record()
-            self._ring_ev[k] = ev
-        self._launch(u, self._rec, self.capacity, self.nrec, self._pmax, self._pmin, self._hre, self._him, self._coef, H)
+        coef, H = self.factors.row(t), len(self.harmonics)
+        self._launch(u, self._rec, self.capacity, self.nrec, self._pmax, self._pmin, self._hre, self._him, coef, H)
         if self._rec is not None:
             self.nrec += 1
         self.nacc += 1
@@ -289,30 +221,13 @@ class PointSensors:
 
     def gather(self, comm, values=None):
         """``values`` (default: ``series()``; points on the last axis) of every rank merged over the global point list
-        through the communicator's bootstrap (``allgather_bytes``).  Ranks driven from one process have none: use
+        through the communicator's bootstrap (``scatterer.gather_arrays``).  Ranks driven from one process have none: use
         ``merge``."""
         values = self.series() if values is None else np.asarray(values)
         size = int(getattr(comm, "size", 1)) if comm is not None else 1
         if size == 1:
             return merge([(self.point_ids, values)], self.npoints)
-        boot = getattr(comm, "_torch", None) if hasattr(comm, "handle") else comm  # NativeComm: its bootstrap
-        if boot is None or not hasattr(boot, "allgather_bytes"):
-            raise ValueError("gather: this communicator has no bootstrap (ranks in one process): use sensors.merge")
-        buf = io.BytesIO()
-        np.savez(buf, ids=self.point_ids, values=values)
-        per_rank = []
-        for blob in boot.allgather_bytes(buf.getvalue()):
-            with np.load(io.BytesIO(blob), allow_pickle=False) as z:
-                per_rank.append((z["ids"], z["values"]))
-        return merge(per_rank, self.npoints)
+        from .scatterer import gather_arrays
 
-
-def record_schedule(sensors, field, t, halo=None):
-    """Generator: record ``field`` at the end of a step.  On a partitioned mesh the ghost entries of ``field`` are not
-    current after a step: its forward exchange is posted first, with a ``yield`` after posting (the solvers' schedules
-    post their stage exchanges the same way, so in-process lockstep drivers keep working)."""
-    if halo is not None:
-        wk = halo.fwd.begin(field)
-        yield "forward"
-        halo.fwd.end(field, wk)
-    sensors.record(field, t)
+        every = gather_arrays(comm, {"ids": self.point_ids, "values": values}, "gather", "sensors.merge")
+        return merge([(z["ids"], z["values"]) for z in every], self.npoints)

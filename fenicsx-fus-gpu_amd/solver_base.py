@@ -10,6 +10,9 @@ physics through hooks:
   ``_source_scalars(t)``                ``(s1, s2)`` of the source facet term at time ``t``
   ``_source_set`` / ``_absorbing_set``  ``(c1, c2 or None, detJ, dofmap)`` / ``(c, detJ, dofmap)`` of the two facet sets
 
+``rk4_schedule`` and ``rk4_graph`` record through one hook, ``_recording`` (the steps and their factors: ``recording.py``);
+``run_schedule`` drives one rank's schedule generator to its value (``rk4``, ``bioheat.py``, ``field_monitor.py``).
+
 hipGraph replay of the fused step (single rank) is for meshes small enough that the launches, not the kernels, bound the
 step -- below roughly 0.5 M dofs when driven from Python (tools/time_rk4_graph.py: 1.7x at 50 k dofs, 1.4x at 118 k,
 nothing to gain from 1 M dofs up, where consecutive stream launches overlap their tails and graph nodes do not).  Every
@@ -38,7 +41,7 @@ from .precompute import (
     tabulate_facet_gradients,
     tabulate_hex_p1_gradients,
 )
-from .sensors import record_schedule
+from .recording import rk4_steps  # also for bioheat.py and the tests, which take it from here
 
 A_RUNGE = (0.0, 0.5, 0.5, 1.0)
 B_RUNGE = (1.0 / 6.0, 1.0 / 3.0, 1.0 / 3.0, 1.0 / 6.0)
@@ -81,16 +84,13 @@ def device_geometry(mesh, P, ft, dev, facet_sets):
     return D, G, detJ, out
 
 
-def rk4_steps(start_time, final_time, dt, max_steps=None):
-    """``(t, dt)`` of every step of ``rk4(start_time, final_time, dt, max_steps)``: its start and its length, the last step
-    shortened to end at ``final_time``.  A step ends at ``t + dt``: ``sensors.PointSensors.expect_steps`` matches the
-    recording times against those sums bitwise."""
-    t, tf, step = float(start_time), float(final_time), 0
-    while t < tf and (max_steps is None or step < max_steps):
-        dt = min(dt, tf - t)
-        yield t, dt
-        t += dt
-        step += 1
+def run_schedule(gen):
+    """Run one rank's schedule generator (it yields whenever the rank has posted halo exchanges) to exhaustion; returns its value."""
+    while True:
+        try:
+            next(gen)
+        except StopIteration as done:
+            return done.value
 
 
 class SpectralSolver3D:
@@ -196,20 +196,41 @@ class SpectralSolver3D:
         ``record_from`` (default: every step) while its series has room -- the supported way to observe the field mid-run.
         ``monitor``: a ``field_monitor.FieldMonitor`` that accumulates (u, v) over the owned dofs after the same steps (one
         launch, no exchange); it may be given together with ``sensors``."""
-        gen = self.rk4_schedule(start_time, final_time, dt, max_steps, sensors, record_from, monitor)
-        while True:
-            try:
-                next(gen)
-            except StopIteration as done:
-                # N > 1: every device-side wait of the exchange is bounded, so a late or dead neighbour cannot hang this
-                # rank -- it must not hand back a field computed from stale ghosts either (the reference would block in
-                # MPI Waitall, cuda/scatterer.py:175): raise.  One synchronisation per rk4() call.
-                self.check_halo_health(f"{type(self).__name__}.rk4")
-                return done.value
+        result = run_schedule(self.rk4_schedule(start_time, final_time, dt, max_steps, sensors, record_from, monitor))
+        # N > 1: every device-side wait of the exchange is bounded, so a late or dead neighbour cannot hang this
+        # rank -- it must not hand back a field computed from stale ghosts either (the reference would block in
+        # MPI Waitall, cuda/scatterer.py:175): raise.  One synchronisation per rk4() call.
+        self.check_halo_health(f"{type(self).__name__}.rk4")
+        return result
 
     def check_halo_health(self, what="halo exchange"):
         if self.halo is not None:
             self.halo.check_health(what)
+
+    def _recording(self, sensors, monitor, start_time, final_time, dt, max_steps, record_from):
+        """Plan both recorders for this ``rk4`` call (``expect_steps``) and return ``record(t)``: the generator that records what is
+        due after a step ending at ``t``.  On a partitioned mesh the ghost entries of the field are not current after a step: the
+        sensors' forward exchange is posted first, with a ``yield`` after posting (the solvers' schedules post their stage
+        exchanges the same way, so in-process lockstep drivers keep working); the monitor reads owned dofs only."""
+        for recorder in (sensors, monitor):
+            if recorder is not None:
+                recorder.expect_steps(start_time, final_time, dt, max_steps, record_from)
+        rf = -np.inf if record_from is None else float(record_from)
+
+        def record(t):
+            if not t > rf:
+                return
+            u, v = (self.u0, self.v0) if self.fused else (self.u, self.v)
+            if sensors is not None and not sensors.full:
+                if self.halo is not None:
+                    wk = self.halo.fwd.begin(u)
+                    yield "forward"
+                    self.halo.fwd.end(u, wk)
+                sensors.record(u, t)
+            if monitor is not None:
+                monitor.record(u, v, t)
+
+        return record
 
     def rk4_schedule(self, start_time, final_time, dt, max_steps=None, sensors=None, record_from=None, monitor=None):
         """``rk4`` as a generator that yields whenever this rank has posted halo exchanges (see
@@ -219,11 +240,7 @@ class SpectralSolver3D:
         mid-run through ``sensors`` (see ``rk4``; on a partitioned mesh a recording step posts a forward exchange of the
         field first, with a yield) or, over every owned dof, through ``monitor`` (no exchange, no yield)."""
         t, step = float(start_time), 0
-        rf = -np.inf if record_from is None else float(record_from)
-        if sensors is not None:
-            sensors.expect_steps(t, final_time, dt, max_steps, record_from)
-        if monitor is not None:
-            monitor.expect_steps(t, final_time, dt, max_steps, record_from)
+        record = self._recording(sensors, monitor, t, final_time, dt, max_steps, record_from)
         if self.fused:
             self._fused_enter()
         for t0, h in rk4_steps(t, final_time, dt, max_steps):
@@ -235,10 +252,7 @@ class SpectralSolver3D:
                 for i in range(4):
                     yield from self._stage_reference(i, t0, h)
             t, step = t0 + h, step + 1
-            if sensors is not None and t > rf and not sensors.full:
-                yield from record_schedule(sensors, self.u0 if self.fused else self.u, t, self.halo)
-            if monitor is not None and t > rf:
-                monitor.record(*((self.u0, self.v0) if self.fused else (self.u, self.v)), t)
+            yield from record(t)
         if self.fused:
             self._fused_exit()
         return t, step
@@ -285,12 +299,8 @@ class SpectralSolver3D:
         if not self.fused or self.halo is not None:
             raise _lib.FusGpuError("rk4_graph: single-rank fused path only")
         t, tf = float(start_time), float(final_time)
-        rf = -np.inf if record_from is None else float(record_from)
         rows, ends = [], []
-        if sensors is not None:
-            sensors.expect_steps(t, tf, dt, max_steps, record_from)
-        if monitor is not None:
-            monitor.expect_steps(t, tf, dt, max_steps, record_from)
+        record = self._recording(sensors, monitor, t, tf, dt, max_steps, record_from)
         src = self.source
         for t0, h in rk4_steps(t, tf, dt, max_steps):
             if h != dt:
@@ -314,10 +324,8 @@ class SpectralSolver3D:
             for k in range(len(rows)):
                 slot.copy_(table[k])
                 graph.replay()
-                if sensors is not None and ends[k] > rf and not sensors.full:
-                    sensors.record(self.u0, ends[k])
-                if monitor is not None and ends[k] > rf:
-                    monitor.record(self.u0, self.v0, ends[k])
+                for _ in record(ends[k]):  # one rank: no exchange, nothing yielded
+                    pass
             self._fused_exit()
         steps = len(rows)
         if t < tf and (max_steps is None or steps < max_steps):

@@ -17,6 +17,8 @@ def test_constructor_errors():
         fm.FieldMonitor(10, np.float64, harmonics=(1, 2))
     with pytest.raises(ValueError, match="at most 4"):
         fm.FieldMonitor(10, np.float64, harmonics=(1, 2, 3, 4, 5), frequency=1e6)
+    with pytest.raises(ValueError, match="at most 4"):
+        fm.FieldMonitor(10, np.float64, harmonics=(k for k in range(1, 6)), frequency=1e6)  # any iterable, as before
     with pytest.raises(ValueError, match="mean_square"):
         fm.FieldMonitor(10, np.float64, mean_square=("u", "w"))
     with pytest.raises(ValueError):
@@ -25,11 +27,19 @@ def test_constructor_errors():
         fm.FieldMonitor(10, np.float16, peak=True)
 
 
-def _sensor_plan(start_time, final_time, dt, max_steps, record_from):
-    """The steps PointSensors.expect_steps selects (sensors.py), for a series with room for all of them."""
+def _sensor_plan(start_time, final_time, dt, max_steps, record_from, capacity=0, nrec=0):
+    """The steps PointSensors.expect_steps selects (sensors.py) for a series of ``capacity`` rows of which ``nrec`` are written
+    (no series: room for 1 << 16), the rule written out."""
     rk4_steps = pkg("solver_base").rk4_steps
     rf = -np.inf if record_from is None else float(record_from)
-    return [t + h for t, h in rk4_steps(start_time, final_time, dt, max_steps) if t + h > rf]
+    room = capacity - nrec if capacity else 1 << 16
+    ends = []
+    for t, h in rk4_steps(start_time, final_time, dt, max_steps):
+        if len(ends) >= room:
+            break
+        if t + h > rf:
+            ends.append(t + h)
+    return ends
 
 
 @pytest.mark.parametrize("case", [
@@ -55,6 +65,11 @@ def test_record_times_are_the_steps_the_time_loop_records(case):
     assert got == ends
     if got and ms is None:
         assert got[-1] == tf or abs(got[-1] - tf) <= 1e-15 * tf
+    for k in (0, 1, 3, 10**6):  # limit: the first k of them
+        assert fm.record_times(t0, tf, dt, ms, rf, limit=k) == got[:k]
+    for capacity, nrec in ((5, 0), (5, 2), (5, 5), (len(got) + 1, 1), (0, 0)):  # the room a PointSensors series has left
+        room = capacity - nrec if capacity else 1 << 16
+        assert fm.record_times(t0, tf, dt, ms, rf, limit=room) == _sensor_plan(t0, tf, dt, ms, rf, capacity, nrec)
 
 
 def test_merge_focus_of_hand_made_records():

@@ -188,6 +188,29 @@ def test_known_signal():
         mv.record(torch.zeros(n - 1, dtype=torch.float64, device="cuda"), torch.zeros(n, dtype=torch.float64, device="cuda"), 0.0)
 
 
+def test_planned_and_ring_records_accumulate_alike():
+    """80 records of which only the first 10 are planned (expect_steps): those read the uploaded table, the other 70 = _RING + 6
+    the pinned ring, whose first six rows are reused after the wrap.  n = 1027 = 4 * 256 + 3: several workgroups and a tail beyond
+    the 16-byte accesses."""
+    import torch
+
+    torch.cuda.set_device(0)
+    fm, ring = pkg("field_monitor"), pkg("recording")._RING
+    n, K, f0 = 1027, 10 + ring + 6, 1.1e6
+    rng = np.random.default_rng(23)
+    ends = fm.record_times(0.0, 1.0, 0.9e-7 / 7, max_steps=K)  # the step ends of a run: t_0 .. t_79
+    us = [10.0 * rng.standard_normal(n) for _ in range(K)]
+    vs = [1e3 * rng.standard_normal(n) for _ in range(K)]
+    m = fm.FieldMonitor(n, np.float64, peak=True, mean_square=("u", "v"), harmonics=(1, 2), frequency=f0)
+    m.expect_steps(0.0, 1.0, 0.9e-7 / 7, max_steps=10)  # a run whose step ends are t_0 .. t_9
+    assert np.array_equal(m.factors.planned_times, ends[:10]) and m.factors.planned_left == 10
+    for k in range(K):
+        m.record(torch.from_numpy(us[k]).cuda(), torch.from_numpy(vs[k]).cuda(), ends[k])
+        assert m.factors.planned_left == max(9 - k, 0)  # exhausted after record 9
+    assert m.nacc == K
+    _assert_statistics(_held(m), _reference_statistics(us, vs, ends, f0))
+
+
 def test_entry_point_errors_precede_device_work():
     lib = pkg("_lib").load()
     z, one = C.c_void_p(0), C.c_void_p(4096)  # non-null, never dereferenced: validation fails first
@@ -284,13 +307,13 @@ def test_solver_accumulates_the_recorded_steps(solver, fused):
     assert _rel(sd.series(), se.series()) <= 1e-11
     _assert_statistics(_held(md), ref)
     # the plan of recorded steps is the sensors' plan
-    assert np.array_equal(md._plan_t, record_plan(sens, mesh, pts, a.f0, tf, dt, K, 2.5 * dt))
+    assert np.array_equal(md.factors.planned_times, record_plan(sens, mesh, pts, a.f0, tf, dt, K, 2.5 * dt))
 
 
 def record_plan(sens, mesh, pts, f0, tf, dt, K, rf):
     s = sens.PointSensors(mesh, pts, np.float64, harmonics=(1,), frequency=f0)
     s.expect_steps(0.0, tf, dt, K, rf)
-    return s._plan_t
+    return s.factors.planned_times
 
 
 @pytest.mark.parametrize("solver", ["linear", "westervelt"])

@@ -146,6 +146,47 @@ def test_harmonic_coefficient_table():
     assert sens.harmonic_coefficients((), w, t).shape == (0,)
 
 
+@pytest.mark.parametrize("harmonics", [(), (1,), (1, 2, 5)])
+def test_coefficient_rows_equal_harmonic_coefficients(harmonics):
+    """A planned record reads a row of the table, any other one ``harmonic_coefficients`` of its time: the same factors, bitwise."""
+    rec = pkg("recording")
+    w = 2 * np.pi * 1.1e6
+    rng = np.random.default_rng(17)
+    ends = np.cumsum(rng.uniform(0.2e-7, 1.9e-7, 70))  # step ends of 70 steps of random length
+    rows = rec.coefficient_rows(harmonics, w, ends)
+    assert rows.shape == (70, 2 * len(harmonics)) and rows.flags.c_contiguous
+    for row, t in zip(rows, ends):
+        assert np.array_equal(row, pkg("sensors").harmonic_coefficients(harmonics, w, t))
+        k = np.asarray(harmonics, dtype=np.float64)
+        assert np.array_equal(row, np.stack([np.cos(k * w * t), -np.sin(k * w * t)], axis=1).reshape(-1))  # the formula itself
+
+
+def test_gather_arrays_through_a_bootstrap():
+    """What PointSensors.gather and field_monitor.focus send through the communicator's bootstrap comes back as one dict per rank;
+    a communicator of ranks driven from one process has none."""
+    scat = pkg("scatterer")
+
+    class Boot:  # two ranks; the other one sends what this one does
+        size = 2
+
+        def allgather_bytes(self, payload):
+            return [payload, payload]
+
+    class InProcess:  # NativeComm(local=...): a handle, no bootstrap
+        size, handle, _torch = 2, 1, None
+
+    arrays = {"ids": np.arange(3), "values": np.arange(6.0).reshape(2, 3), "max": 2.5}
+    every = scat.gather_arrays(Boot(), arrays, "gather", "sensors.merge")
+    assert len(every) == 2
+    for z in every:
+        assert sorted(z) == sorted(arrays) and all(np.array_equal(z[k], arrays[k]) for k in arrays)
+        assert z["ids"].dtype == np.int64 and z["max"].shape == ()
+    with pytest.raises(ValueError, match=r"^gather: this communicator has no bootstrap \(ranks in one process\): use sensors.merge$"):
+        scat.gather_arrays(InProcess(), arrays, "gather", "sensors.merge")
+    with pytest.raises(ValueError, match=r"^focus: this communicator has no bootstrap \(ranks in one process\): use merge_focus$"):
+        scat.gather_arrays(object(), arrays, "focus", "merge_focus")
+
+
 def test_probe_argument_validation_precedes_device_work():
     lib = pkg("_lib").load()
     z = C.c_void_p(0)

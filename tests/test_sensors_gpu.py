@@ -153,6 +153,38 @@ def test_accumulators_against_numpy(dtype):
     assert np.max(h.harmonic_amplitude(3)) <= tol * 3 * np.max(np.abs(a1))
 
 
+def test_planned_and_ring_records_accumulate_alike():
+    """80 records of which only the first 10 are planned (expect_steps): those read the uploaded table, the other 70 = _RING + 6
+    the pinned ring, whose first six rows are reused after the wrap.  Harmonics and peaks against numpy over the per-record
+    evaluate() rows."""
+    import torch
+
+    torch.cuda.set_device(0)
+    sens, rec = pkg("sensors"), pkg("recording")
+    mesh = _mesh("perturbed", 2)
+    rng = np.random.default_rng(29)
+    K, f0, dt = 10 + rec._RING + 6, 1.1e6, 0.9e-7 / 7
+    s = sens.PointSensors(mesh, 0.001 + 0.01 * rng.random((40, 3)), np.float64, peak=True, harmonics=(1, 2), frequency=f0)
+    assert s.m == 40
+    ends = rec.record_times(0.0, 1.0, dt, max_steps=K)
+    s.expect_steps(0.0, 1.0, dt, max_steps=10)  # a run whose step ends are t_0 .. t_9
+    assert np.array_equal(s.factors.planned_times, ends[:10])
+    rows = []
+    for k in range(K):
+        fd = _dev(1e3 * rng.standard_normal(mesh.ndofs), np.float64)
+        rows.append(s.evaluate(fd).cpu().numpy())
+        s.record(fd, ends[k])
+        assert s.factors.planned_left == max(9 - k, 0)
+    rows = np.asarray(rows)  # [K, m]
+    assert s.nacc == K and s.nrec == 0
+    pmax, pmin = s.peak()
+    assert np.array_equal(pmax, rows.max(axis=0)) and np.array_equal(pmin, rows.min(axis=0))
+    for k in (1, 2):
+        ph = k * 2 * np.pi * f0 * np.asarray(ends)
+        amp = 2.0 / K * np.hypot(rows.T @ np.cos(ph), rows.T @ -np.sin(ph))
+        assert np.max(amp) > 0 and np.max(np.abs(s.harmonic_amplitude(k) - amp)) <= 1e-10 * np.max(amp)
+
+
 def _linear(mesh, fused, P, L):
     ls = pkg("linear_solver")
     h = ls.time_step_parameters(mesh, P, 1500.0, 0.5e6, L)
