@@ -35,8 +35,7 @@ import torch
 
 from . import _lib
 from . import operators as ops
-from .gll import gll_points_weights, tensor_weights_3d
-from .solver_base import A_RUNGE, B_RUNGE, C_RUNGE, device_geometry, per_cell, rk4_steps, run_schedule
+from .solver_base import A_RUNGE, B_RUNGE, C_RUNGE, MeshSolver3D, per_cell, rk4_steps, run_schedule, stiffness_form
 
 # |1 - z + z^2/2 - z^3/6 + z^4/24| = 1: the stability limit of classical RK4 on the negative real axis
 RK4_REAL_AXIS_LIMIT = 2.785
@@ -96,7 +95,7 @@ def _check_arguments(mesh, float_type, materials, fixed_tags):
     return ft, cells, tags
 
 
-class BioheatSpectral3D:
+class BioheatSpectral3D(MeshSolver3D):
     def __init__(self, mesh, float_type=np.float64, conductivity=0.5, density=1050.0, specific_heat=3600.0, perfusion_rate=0.0,
                  blood_density=1060.0, blood_specific_heat=3617.0, arterial_temperature=37.0, initial_temperature=37.0,
                  fixed_tags=(), comm=None, halo_plan=None, defer_setup_exchange=False, in_kernel_geometry="auto", affine="auto"):
@@ -110,15 +109,8 @@ class BioheatSpectral3D:
             dict(conductivity=conductivity, density=density, specific_heat=specific_heat, perfusion_rate=perfusion_rate,
                  blood_density=blood_density, blood_specific_heat=blood_specific_heat), fixed_tags)
         self.Ta = float(arterial_temperature)
-        if comm is not None:
-            from .scatterer import as_comm
-
-            comm = as_comm(comm)
-        self.comm, self.mesh, self.P = comm, mesh, mesh.P
-        self.tdt_np, self.tdt = ft, _lib.torch_dtype(ft)
-        self.dev = dev = torch.device("cuda", torch.cuda.current_device())
-        self.nlocal, self.ndofs = mesh.nlocal, mesh.ndofs
-        P, n = self.P, self.P + 1
+        self.D, G_d, self.detJ, _ = self._init_mesh(mesh, ft, comm)
+        P, n, dev = self.P, self.P + 1, self.dev
         td = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)  # noqa: E731
         self.k_cells = cells["conductivity"]
         rho_c = cells["density"] * cells["specific_heat"]
@@ -128,32 +120,14 @@ class BioheatSpectral3D:
         self.cell_coeff = td((-self.k_cells).astype(ft))  # b = -K(k) T
         self._c_rho_c, self._c_perf, self._c_one = td(rho_c.astype(ft)), td(perf.astype(ft)), td(np.ones(mesh.ncells, dtype=ft))
 
-        # ---- geometry and the stiffness operator: the choices of LinearSpectral3D ---------------------------------------
-        D, G_d, detJ_d, _ = device_geometry(mesh, P, ft, dev, ())
-        self.D, self.G, self.detJ, self.dofmap = D, G_d, detJ_d, td(mesh.dofmap)
-        w3 = tensor_weights_3d(gll_points_weights(P)[1])
-        self.affine = bool(affine) if affine != "auto" else ops.is_affine_geometry(self.G, w3, rtol=1e-11 if ft == np.float64 else 1e-5)
-        self.stiff = ops.stiffness_operator(P, D.flatten(), ft, affine_weights=w3 if self.affine else None)
-        if in_kernel_geometry == "auto":
-            in_kernel_geometry = P >= 3
-        self.in_kernel_geometry = bool(in_kernel_geometry) and not self.affine
+        # ---- the stiffness operator (the G array is not kept), and the halo with one reverse closure per lumped vector ----
+        self.stiff, self.G, self.affine, self.in_kernel_geometry, _ = stiffness_form(mesh, P, self.D, G_d, ft, affine, in_kernel_geometry)
+        del G_d
         if self.in_kernel_geometry:
-            pts1, wts1 = gll_points_weights(P)
-            self.x_dofs = td(mesh.x_dofs)
-            self.stiff = ops.stiffness_operator(P, D.flatten(), ft, geometry=(self.x_dofs, mesh.x_g, pts1, wts1))
-            self.G = self.x_dofs  # x_dofs rows travel in the G position (cell sub-ranges slice them)
-            del G_d
+            self.x_dofs = self.G
+        self.dofmap = td(mesh.dofmap)
         self.mass_cell = ops.mass_operator(n**3, ft)
-
-        # ---- halo ---------------------------------------------------------------------------------------------------
-        self.halo, self._rev_setup = None, []
-        if self.comm is not None and self.comm.size > 1:
-            from .scatterer import HaloApply, scatter_reverse
-
-            self.halo = HaloApply(mesh, self.stiff, self.comm, ft, plan=halo_plan)
-            # one closure per vector of the set-up exchange, built here (building one is a collective step of the PEER transport)
-            self._rev_setup = [self.halo.rev] + [scatter_reverse(self.comm, self.halo.owners_data, self.halo.ghosts_data, mesh.nlocal, ft)
-                                                 for _ in range(3)]
+        self._init_halo(halo_plan, reverse=3)
 
         z = lambda: torch.zeros(self.ndofs, dtype=self.tdt, device=dev)  # noqa: E731
         self.T, self.Tn, self.acc, self.b = z(), z(), z(), z()
@@ -176,21 +150,12 @@ class BioheatSpectral3D:
             if fd.size:
                 self._fix[td(np.unique(fd).astype(np.int64))] = 1.0
         self.set_temperature(initial_temperature)
-        self._setup = self.setup_schedule()
-        if not defer_setup_exchange:
-            for _ in self._setup:
-                pass
+        self._start_setup(defer_setup_exchange)
 
     def setup_schedule(self):
         """Generator: post the set-up exchange (reverse scatters of the three lumped vectors and of the fixed-dof marks), yield,
         complete it and form minv, pr.  One rank per process exhausts it in the constructor."""
-        if self.halo is not None:
-            from .scatterer import begin_all
-
-            pending = begin_all(zip(self._rev_setup, (self.minv, self.pr, self.vol, self._fix)))
-            yield "reverse"
-            for sc, vec, wk in pending:
-                sc.end(vec, wk)
+        yield from self._reverse_setup((self.minv, self.pr, self.vol, self._fix))
         n = self.nlocal
         free = (self._fix[:n] == 0).to(self.tdt)
         self.mc = self.minv[:n].clone()  # M(rho C) 1 over the owned dofs
@@ -254,10 +219,6 @@ class BioheatSpectral3D:
         """Owned part of the temperature field on the host."""
         return self.T[: self.nlocal].detach().cpu().numpy()
 
-    def check_halo_health(self, what="halo exchange"):
-        if self.halo is not None:
-            self.halo.check_health(what)
-
     # -- one stage ------------------------------------------------------------------------------------------------------------
     def _apply(self, x):
         """b += -K(k) x; next to a halo the interior cells overlap the forward exchange of x and the reverse exchange of b."""
@@ -315,10 +276,13 @@ class BioheatSpectral3D:
             reduce.put(seq, self.comm.rank, values)
             yield "reduce"
             return reduce.get(seq)
-        if getattr(self.comm, "_torch", None) is None:
+        from .scatterer import gather_floats
+
+        every = gather_floats(self.comm, values)
+        if len(every) != self.comm.size:  # the local row alone: no bootstrap spans the ranks
             raise _lib.FusGpuError("stable_time_step: ranks driven from one process share no collective: drive "
                                    "stable_time_step_schedule(safety, reduce=InProcessGather(nranks)) in lock step")
-        return self.comm.allgather_floats(values)
+        return every
 
     def stable_time_step_schedule(self, safety=0.8, reduce=None, rtol=0.01, min_iterations=16, max_iterations=200):
         """Generator form of ``stable_time_step`` (yields where ``HaloApply`` yields, and after depositing partial sums in

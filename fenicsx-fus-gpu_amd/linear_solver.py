@@ -30,8 +30,7 @@ import torch
 
 from . import _lib
 from . import operators as ops
-from .gll import gll_points_weights, tensor_weights_3d
-from .solver_base import A_RUNGE, B_RUNGE, SpectralSolver3D, per_cell
+from .solver_base import A_RUNGE, B_RUNGE, SpectralSolver3D, per_cell, stiffness_form
 
 
 def time_step_parameters(mesh, P, speed_of_sound, source_frequency, domain_length, CFL=0.65):
@@ -89,7 +88,6 @@ class LinearSpectral3D(SpectralSolver3D):
         self.G, self.detJ, self.dofmap = G_d, detJ_d, td(mesh.dofmap)
         self.detJ_f1, self.detJ_f2 = dF1_d, dF2_d
         self.fdm1, self.fdm2 = td(mesh.facet_dofmap(bd1)), td(mesh.facet_dofmap(bd2))
-        self.nlocal, self.ndofs = mesh.nlocal, mesh.ndofs
         # the fused stage's facet sets: M_f1(g c1) 1 with g = source_value(t), M_f2(c2) v_n
         self._source_set = (self.facet_coeff1, None, self.detJ_f1, self.fdm1)
         self._absorbing_set = (self.facet_coeff2, self.detJ_f2, self.fdm2)
@@ -97,40 +95,16 @@ class LinearSpectral3D(SpectralSolver3D):
         self.source = None if source is None else source.bind(mesh, bd1, ft, dev, frequency=self.f0, scale=self.p0 * self.w0 / self.c0,
                                                               coeff1=self.facet_coeff1, detJ=self.detJ_f1, dofmap=self.fdm1)
 
-        # ---- operators --------------------------------------------------------------------------
-        # affine cells (every box mesh of the reference's demos): opt into the constant-G fast path
-        # after checking the geometry factors really are affine ("auto"), or on request / never
-        w3 = tensor_weights_3d(gll_points_weights(P)[1])
-        self.affine = bool(affine) if affine != "auto" else ops.is_affine_geometry(
-            self.G, w3, rtol=1e-11 if ft == np.float64 else 1e-5)
-        self.stiff = ops.stiffness_operator(P, D.flatten(), ft, affine_weights=w3 if self.affine else None)
-        # opt-in for non-affine (trilinear) cells: G formed in the kernel from the cell vertices; the
-        # per-cell argument of the stiffness apply is then the cell's vertex ids instead of G
-        if in_kernel_geometry == "auto":
-            in_kernel_geometry = P >= 3  # below that G is not the dominant stream and the kernel form loses
-        self.in_kernel_geometry = bool(in_kernel_geometry) and not self.affine
-        self.G_array = self.G  # the reference's geometric-factor array (None once dropped)
+        # ---- operators and halo ---------------------------------------------------------------------
+        self.stiff, self.G, self.affine, self.in_kernel_geometry, self.G_array = stiffness_form(
+            mesh, P, D, G_d, ft, affine, in_kernel_geometry, keep_G)
+        del G_d
         if self.in_kernel_geometry:
-            pts1, wts1 = gll_points_weights(P)
-            self.x_dofs = td(mesh.x_dofs)
-            self.stiff = ops.stiffness_operator(P, D.flatten(), ft, geometry=(self.x_dofs, mesh.x_g, pts1, wts1))
-            self.G = self.x_dofs  # x_dofs rows travel in the G position (cell sub-ranges slice them)
-            if not keep_G:
-                self.G_array = None  # 6 n^3 values per cell nobody reads any more (config 3: 945 MB)
-                del G_d
+            self.x_dofs = self.G
         self.mass_cell = ops.mass_operator(n**3, ft)
         self.mass_facet = ops.mass_operator(n * n, ft)
         self.axpy = ops.axpy(self.ndofs)
-
-        # ---- halo ---------------------------------------------------------------------------------
-        self.halo = None
-        if self.comm is not None and self.comm.size > 1:
-            from .scatterer import HaloApply, scatter_forward
-
-            # halo_plan = (owners_data, ghosts_data) computed elsewhere (a host that drives several ranks from
-            # one process has no index exchange to run); default: exchanged over ``comm`` now
-            self.halo = HaloApply(mesh, self.stiff, self.comm, ft, overlap=overlap, kernels=halo_kernels, plan=halo_plan)
-            self.fwd_v = scatter_forward(self.comm, self.halo.owners_data, self.halo.ghosts_data, mesh.nlocal, ft, halo_kernels)
+        self.fwd_v, = self._init_halo(halo_plan, forward=1, overlap=overlap, kernels=halo_kernels)
         # the facet mass applies of a stage are ``boundary_terms`` of HaloApply: in its concurrent schedule they run on the
         # communicator's stream WHILE the interior stiffness launch adds into the same b with float atomics (interior cells
         # on the x = 0 / x = L faces touch exactly the facet dofs).  The atomic-free gather kernel's plain load + store would
@@ -154,10 +128,7 @@ class LinearSpectral3D(SpectralSolver3D):
     def setup_schedule(self):
         """Generator: post the set-up exchange (reverse scatter of the lumped mass), yield, complete it and
         form 1/m.  One rank per process exhausts it in the constructor."""
-        if self.halo is not None:
-            wk = self.halo.rev.begin(self.m)
-            yield "reverse"
-            self.halo.rev.end(self.m, wk)
+        yield from self._reverse_setup([self.m])
         ops.fill(1.0, self.minv)
         ops.pointwise_divide(self.minv, self.m, self.minv)  # owned entries are what the fused kernel reads
 

@@ -18,8 +18,7 @@ import torch
 
 from . import _lib
 from . import operators as ops
-from .gll import tabulate_1d
-from .solver_base import A_RUNGE, B_RUNGE, SpectralSolver3D, per_cell
+from .solver_base import A_RUNGE, B_RUNGE, IN_KERNEL_GEOMETRY_FROM_DEGREE, SpectralSolver3D, per_cell, vertex_geometry
 
 
 def compute_diffusivity_of_sound(frequency, speed, attenuationdB):
@@ -80,7 +79,6 @@ class WesterveltSpectral3D(SpectralSolver3D):
         self.dF1, self.dF2 = dF1_d, dF2_d
         self.fdm1 = torch.from_numpy(mesh.facet_dofmap(bd1)).to(dev)
         self.fdm2 = torch.from_numpy(mesh.facet_dofmap(bd2)).to(dev)
-        self.nlocal, self.ndofs = mesh.nlocal, mesh.ndofs
         # the fused stage's facet sets: M_f1(fc1_1 g + fc2_1 dg) 1 with (g, dg) = source_values(t), M_f2(fc2_2) v_n
         self._source_set = (self.fc1_1, self.fc2_1, self.dF1, self.fdm1)
         self._absorbing_set = (self.fc2_2, self.dF2, self.fdm2)
@@ -93,14 +91,10 @@ class WesterveltSpectral3D(SpectralSolver3D):
         self.mass_cell = ops.mass_operator(n**3, ft, static_detJ=not self.fused)
         self.mass_facet = ops.mass_operator(n * n, ft)
         self.axpy = ops.axpy(self.ndofs)
-        self.halo = None
-        if self.comm is not None and self.comm.size > 1:
-            from .scatterer import HaloApply, scatter_forward, scatter_reverse
-
-            self.halo = HaloApply(mesh, self.stiff, self.comm, ft, overlap=overlap, plan=halo_plan)
-            mk = lambda: scatter_forward(self.comm, self.halo.owners_data, self.halo.ghosts_data, mesh.nlocal, ft)  # noqa: E731
-            self.fwd_u, self.fwd_v, self.fwd_w = self.halo.fwd, mk(), mk()
-            self.rev_m = scatter_reverse(self.comm, self.halo.owners_data, self.halo.ghosts_data, mesh.nlocal, ft)
+        # the reverse closures of the set-up exchange of the three assembled diagonals (m0, w2, w5) with the others
+        self.fwd_v, self.fwd_w = self._init_halo(halo_plan, forward=2, reverse=2, overlap=overlap)
+        if self.halo is not None:
+            self.fwd_u, self.rev_m = self.halo.fwd, self._rev_setup[1]
         z = lambda: torch.zeros(self.ndofs, dtype=self.tdt, device=dev)  # noqa: E731
         (self.u, self.v, self.u0, self.v0, self.un, self.vn, self.ku, self.kv, self.u_n, self.v_n, self.w_n,
          self.g, self.dg, self.b, self.m, self.m0) = (z() for _ in range(16))
@@ -119,14 +113,7 @@ class WesterveltSpectral3D(SpectralSolver3D):
         self.w2, self.w5 = z(), z()
         self.mass_cell(self.g, self.cc2, self.w2, self.detJ, self.dofmap)  # g == 1 here
         self.mass_cell(self.g, self.cc5, self.w5, self.detJ, self.dofmap)
-        # the reverse scatters of the three assembled diagonals (m0, w2, w5), as one grouped exchange: now, or
-        # by a driver that runs several ranks from one process (setup_schedule, see LinearSpectral3D)
-        # the third reverse closure of the set-up exchange is built HERE, with the others: building a closure is a collective
-        # step of the PEER transport (arena handles), and ranks driven from one process must all have built theirs before
-        # any of them exchanges
-        self._rev_w5 = None
-        if self.halo is not None:
-            self._rev_w5 = scatter_reverse(self.halo.comm, self.halo.owners_data, self.halo.ghosts_data, self.nlocal, self.tdt_np)
+        # the reverse scatters of the three assembled diagonals, as one grouped exchange
         self._start_setup(defer_setup_exchange)
         # uniform ratio c4 / c3 (= delta / c^2: every homogeneous medium): K(c3) u + K(c4) v = K(c3)(u + kappa v),
         # so the cell pass CAN be one plain stiffness apply on w = u_n + kappa v_n, which the vector kernel writes (uniform_ratio=True)
@@ -134,18 +121,13 @@ class WesterveltSpectral3D(SpectralSolver3D):
         kmin, kmax = float(ratio.min().item()), float(ratio.max().item())
         # the decision (and kappa itself) must be the SAME on every rank -- a rank in single-gather mode forward-scatters
         # w where a neighbour in two-gather mode expects u_n, with matching counts, so nothing would hang and the result
-        # would be silently wrong: min / max over all ranks.  cc3 / cc4 must not be edited after construction.
-        if self.comm is not None and getattr(self.comm, "size", 1) > 1 and getattr(self.comm, "_world_id", None) is None:
-            import torch.distributed as dist
+        # would be silently wrong: min / max over all ranks (the ranks of one process decide locally).  cc3 / cc4 must not be
+        # edited after construction.
+        if not getattr(self.comm, "in_process", False):
+            from .scatterer import gather_floats
 
-            if hasattr(self.comm, "allgather_floats"):  # NativeComm: over its bootstrap (torch.distributed or MPI)
-                every = self.comm.allgather_floats([kmin, kmax])
-                kmin, kmax = float(every[:, 0].min()), float(every[:, 1].max())
-            elif dist.is_available() and dist.is_initialized():
-                on_gpu = dist.get_backend() == "nccl"
-                t = torch.tensor([-kmin, kmax], dtype=torch.float64, device=self.dev if on_gpu else "cpu")
-                dist.all_reduce(t, op=dist.ReduceOp.MAX)
-                kmin, kmax = -float(t[0].item()), float(t[1].item())
+            every = gather_floats(self.comm, [kmin, kmax])
+            kmin, kmax = float(every[:, 0].min()), float(every[:, 1].max())
         self.kappa = kmin if abs(kmax - kmin) <= 1e-14 * max(abs(kmin), abs(kmax), 1e-300) else None
         # Which form: since the vector pass streams with non-temporal accesses (round 4) the TWO-gather cell pass is the faster one --
         # the single-gather form pays for writing w in the vector pass and re-reading it: P = 6, 36^3 cells, paired: 1.285 against
@@ -157,16 +139,16 @@ class WesterveltSpectral3D(SpectralSolver3D):
         # opt-in (fused mode): G and detJ formed in the cell kernel from the vertices -- the cells of
         # the reference's meshes are trilinear (P1 geometry, cuda/demo_nonlinear_bowl.py:317)
         if in_kernel_geometry == "auto":
-            in_kernel_geometry = self.fused and P >= 3
+            in_kernel_geometry = self.fused and P >= IN_KERNEL_GEOMETRY_FROM_DEGREE
         self.in_kernel_geometry = bool(in_kernel_geometry)
         if self.in_kernel_geometry and self.fused and not keep_G:
             self.G = None  # the fused stage does not read it (P = 6, 36^3 cells: 768 MB)
         stiff, pair = self.stiff, self.cell_fused
         if self.in_kernel_geometry:
-            pts, wts, _ = tabulate_1d(P, ft)
-            self.x_dofs = torch.from_numpy(np.ascontiguousarray(mesh.x_dofs)).to(dev)
-            self.cell_fused_geom = ops.westervelt_cell_operator(P, D.flatten(), ft, geometry=(mesh.x_g, pts, wts))
-            self.stiff_geom = ops.stiffness_operator(P, D.flatten(), ft, geometry=(self.x_dofs, mesh.x_g, pts, wts))
+            geometry = vertex_geometry(mesh, P, dev)
+            self.x_dofs = geometry[0]
+            self.cell_fused_geom = ops.westervelt_cell_operator(P, D.flatten(), ft, geometry=geometry[1:])
+            self.stiff_geom = ops.stiffness_operator(P, D.flatten(), ft, geometry=geometry)
             stiff, pair = self.stiff_geom, self.cell_fused_geom
         # the fused stage's cell pass, one of four: single gather (K(c3) w, w = u_n + kappa v_n) or two (K(c3) u_n + K(c4) v_n),
         # each with the G array or G formed in the kernel (x_dofs rows travel in the G position)
@@ -177,14 +159,7 @@ class WesterveltSpectral3D(SpectralSolver3D):
             self._cell_pass = lambda u_n, v_n, c3, c4, G_, dm_: pair.stiffness_only(u_n, v_n, c3, c4, self.b, G_, dm_)
 
     def setup_schedule(self):
-        if self.halo is not None:
-            from .scatterer import begin_all
-
-            self._rev_setup = [self.halo.rev, self.rev_m, self._rev_w5]
-            pending = begin_all(zip(self._rev_setup, (self.m0, self.w2, self.w5)))
-            yield "reverse"
-            for sc, vec, wk in pending:
-                sc.end(vec, wk)
+        yield from self._reverse_setup((self.m0, self.w2, self.w5))
 
     def source_values(self, t):
         """g and dg/dt (cuda/demo_nonlinear_bowl.py:560-595)."""

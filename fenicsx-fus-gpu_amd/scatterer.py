@@ -216,17 +216,10 @@ class NativeComm:
         if self._torch is not None:
             self._torch.barrier()
 
-    def allgather_floats(self, values):
-        """Every rank's ``values`` (a few host floats) as an array [size, len(values)] -- set-up agreements of the drivers
-        (a min / max over the ranks) through whatever carries this communicator's bootstrap.  One-rank world or all ranks in
-        this process without a bootstrap: the local values alone."""
-        import struct
-
-        v = [float(x) for x in values]
-        if self._torch is None or self.size == 1:
-            return np.asarray([v])
-        blobs = self._torch.allgather_bytes(struct.pack(f"<{len(v)}d", *v))
-        return np.asarray([struct.unpack(f"<{len(v)}d", b) for b in blobs])
+    @property
+    def in_process(self):
+        """True for the ranks of a ``local=`` world: driven, with others, from this process."""
+        return self._world_id is not None
 
     def close(self):
         if self.handle:
@@ -426,6 +419,21 @@ def gather_arrays(comm, arrays, what, instead):
         with np.load(io.BytesIO(blob), allow_pickle=False) as z:
             out.append({k: z[k] for k in z.files})
     return out
+
+
+def gather_floats(comm, values):
+    """Every rank's ``values`` (a few host floats) as a float64 array [size, len(values)] in rank order: the solvers' set-up agreements.
+    Through a ``NativeComm``'s bootstrap or a ``TorchComm``'s own ``allgather_bytes``; a stand-in with neither (rehearsal over gloo): the
+    default ``torch.distributed`` group if initialised.  No communicator, one rank, ranks of one process without a bootstrap: the local row."""
+    import struct
+
+    v = [float(x) for x in values]
+    boot = getattr(comm, "_torch", None) if hasattr(comm, "handle") else comm  # NativeComm: its bootstrap
+    if boot is not None and not hasattr(boot, "allgather_bytes") and dist.is_available() and dist.is_initialized():
+        boot = TorchComm()
+    if boot is None or getattr(comm, "size", None) == 1 or not hasattr(boot, "allgather_bytes"):
+        return np.asarray([v], dtype=np.float64)
+    return np.asarray([struct.unpack(f"<{len(v)}d", b) for b in boot.allgather_bytes(struct.pack(f"<{len(v)}d", *v))], dtype=np.float64)
 
 
 class _NativeScatter:
@@ -1032,7 +1040,7 @@ class HaloApply:
                     self.op.prepare(self._views(name, (cell_constants, G, dofmap))[2])
         # the device-side waits of the PEER transport are bounded: line the ranks up on the host before the first
         # exchange, so that a rank whose set-up took longer is not mistaken for a dead one
-        if hasattr(self.comm, "barrier") and getattr(self.comm, "_world_id", None) is None:
+        if hasattr(self.comm, "barrier") and not getattr(self.comm, "in_process", False):
             self.comm.barrier()
         self.fwd(x)
         self.rev(x.new_zeros(x.shape))

@@ -11,7 +11,8 @@ physics through hooks:
   ``_source_set`` / ``_absorbing_set``  ``(c1, c2 or None, detJ, dofmap)`` / ``(c, detJ, dofmap)`` of the two facet sets
 
 ``rk4_schedule`` and ``rk4_graph`` record through one hook, ``_recording`` (the steps and their factors: ``recording.py``);
-``run_schedule`` drives one rank's schedule generator to its value (``rk4``, ``bioheat.py``, ``field_monitor.py``).
+``run_schedule`` drives one rank's schedule generator to its value (``rk4``, ``bioheat.py``, ``field_monitor.py``), ``run_lockstep``
+those of several ranks of one process.  ``MeshSolver3D`` is the set-up these solvers share with ``bioheat.py``.
 
 hipGraph replay of the fused step (single rank) is for meshes small enough that the launches, not the kernels, bound the
 step -- below roughly 0.5 M dofs when driven from Python (tools/time_rk4_graph.py: 1.7x at 50 k dofs, 1.4x at 118 k,
@@ -34,7 +35,7 @@ import torch
 
 from . import _lib
 from . import operators as ops
-from .gll import tabulate_1d, tensor_points_3d, tensor_weights_2d, tensor_weights_3d
+from .gll import gll_points_weights, tabulate_1d, tensor_points_3d, tensor_weights_2d, tensor_weights_3d
 from .precompute import (
     compute_boundary_facets_scaled_jacobian_determinant_device,
     compute_scaled_geometrical_factor_device,
@@ -84,6 +85,33 @@ def device_geometry(mesh, P, ft, dev, facet_sets):
     return D, G, detJ, out
 
 
+# in_kernel_geometry="auto": from this degree; below it G is not the dominant stream and the kernel form loses
+IN_KERNEL_GEOMETRY_FROM_DEGREE = 3
+
+
+def vertex_geometry(mesh, P, dev):
+    """``(x_dofs on the device, x_g, pts, wts)``: what an operator that forms G in the kernel from the 8 vertices of each cell is
+    built with (the reference's geometry is P1 everywhere, cuda/demo_nonlinear_bowl.py:317)."""
+    return (torch.from_numpy(np.ascontiguousarray(mesh.x_dofs)).to(dev), mesh.x_g) + gll_points_weights(P)
+
+
+def stiffness_form(mesh, P, D, G, float_type, affine="auto", in_kernel_geometry="auto", keep_G=False):
+    """The stiffness operator of ``LinearSpectral3D`` / ``BioheatSpectral3D``: ``(operator, what travels in the G position of its
+    call, affine, in_kernel_geometry, G_array)``.  Affine cells (every box mesh of the reference's demos): the constant-G fast path,
+    after checking that the geometry factors really are affine (``"auto"``), or on request / never.  Otherwise, on request or by
+    ``IN_KERNEL_GEOMETRY_FROM_DEGREE``: G formed in the kernel; the rows of ``x_dofs`` then travel in the G position (cell sub-ranges
+    slice them) and ``G_array``, the reference's array, is ``None`` unless ``keep_G`` (6 n^3 values per cell: 945 MB at config 3)."""
+    ft = np.dtype(float_type)
+    w3 = tensor_weights_3d(gll_points_weights(P)[1])
+    affine = bool(affine) if affine != "auto" else ops.is_affine_geometry(G, w3, rtol=1e-11 if ft == np.float64 else 1e-5)
+    if in_kernel_geometry == "auto":
+        in_kernel_geometry = P >= IN_KERNEL_GEOMETRY_FROM_DEGREE
+    if affine or not in_kernel_geometry:
+        return ops.stiffness_operator(P, D.flatten(), ft, affine_weights=w3 if affine else None), G, affine, False, G
+    geometry = vertex_geometry(mesh, P, G.device)
+    return ops.stiffness_operator(P, D.flatten(), ft, geometry=geometry), geometry[0], False, True, G if keep_G else None
+
+
 def run_schedule(gen):
     """Run one rank's schedule generator (it yields whenever the rank has posted halo exchanges) to exhaustion; returns its value."""
     while True:
@@ -93,37 +121,90 @@ def run_schedule(gen):
             return done.value
 
 
-class SpectralSolver3D:
-    """The time loop of an explicit RK4 solver for u' = v, M v' = r(u, v, t) (see the module docstring for its hooks)."""
+def run_lockstep(gens):
+    """Advance the generators of several in-process ranks together: each ``next`` runs a rank up to the point
+    where it has posted a set of halo exchanges; results are the generators' return values."""
+    out = [None] * len(gens)
+    live = list(enumerate(gens))
+    while live:
+        nxt = []
+        for i, g in live:
+            try:
+                next(g)
+                nxt.append((i, g))
+            except StopIteration as done:
+                out[i] = done.value
+        live = nxt
+    return out
 
-    def _init_common(self, mesh, float_type, comm, fused, source_time):
-        """The attributes both solvers set first; returns the source and absorbing facet sets and the device geometry:
-        ``bd1, bd2, D, G, detJ, (dF1, dF2)``."""
+
+class MeshSolver3D:
+    """What a solver does before its first step: communicator, device, dtype, geometry, halo closures and the set-up exchange."""
+
+    def _init_mesh(self, mesh, float_type, comm, facet_sets=()):
+        """The attributes every solver sets first; returns ``device_geometry``: ``D, G, detJ, [facet detJ of each set]``."""
         if comm is not None:  # an MPI.Comm (the reference's comm = MPI.COMM_WORLD) becomes the bootstrap of a NativeComm
             from .scatterer import as_comm
 
             comm = as_comm(comm)
-        self.comm = comm
-        self.mesh, self.P = mesh, mesh.P
-        self.tdt_np = np.dtype(float_type)
-        self.tdt = _lib.torch_dtype(float_type)
+        self.comm, self.mesh, self.P = comm, mesh, mesh.P
+        self.nlocal, self.ndofs = mesh.nlocal, mesh.ndofs
+        self.tdt_np, self.tdt = np.dtype(float_type), _lib.torch_dtype(float_type)
         self.dev = torch.device("cuda", torch.cuda.current_device())
-        self.fused, self.source_time = bool(fused), source_time
-        self.lean_stages = os.environ.get("FUS_RK4_LEAN", "1") != "0"  # the fused stage's vector pass: kinds 4-7 of csrc/rk4.hpp (_stage_args)
-        # the two tagged facet sets (cuda/demo_linear_box.py:230-243, cuda/utils.py:81-114): a structured box names them by its
-        # faces (x = 0: source, x = L: absorbing), a mesh handed over as arrays (dolfinx_adaptor.ArrayMesh) by its facet tags
-        bd1 = mesh.boundary_facets([getattr(mesh, "source_tag", 2)])
-        bd2 = mesh.boundary_facets([getattr(mesh, "absorbing_tag", 3)])
-        # geometry precompute (reference: numba on the host, cuda/demo_linear_box.py:245-317)
-        return (bd1, bd2) + device_geometry(mesh, self.P, self.tdt_np, self.dev, (bd1, bd2))
+        return device_geometry(mesh, self.P, self.tdt_np, self.dev, facet_sets)
+
+    def _init_halo(self, halo_plan, forward=0, reverse=0, overlap=True, kernels=None):
+        """``self.halo`` around ``self.stiff`` (``None`` on one rank), ``forward`` more forward closures (returned) and ``reverse``
+        more reverse ones (``self._rev_setup``: ``halo.rev`` and those, one per vector of the set-up exchange).  ``halo_plan =
+        (owners_data, ghosts_data)`` computed elsewhere (a host that drives several ranks from one process has no index exchange
+        to run); default: exchanged over ``comm`` now.  Every closure is built HERE, at construction: building one is a collective
+        step of the PEER transport (arena handles), and ranks driven from one process must all have built theirs before any exchanges."""
+        self.halo, self._rev_setup = None, []
+        if self.comm is None or self.comm.size == 1:
+            return [None] * forward
+        from .scatterer import HaloApply, scatter_forward, scatter_reverse
+
+        self.halo = HaloApply(self.mesh, self.stiff, self.comm, self.tdt_np, overlap=overlap, kernels=kernels, plan=halo_plan)
+        make = lambda scatter, k=None: scatter(self.comm, self.halo.owners_data, self.halo.ghosts_data, self.nlocal, self.tdt_np, k)  # noqa: E731
+        more = [make(scatter_forward, kernels) for _ in range(forward)]
+        self._rev_setup = [self.halo.rev] + [make(scatter_reverse) for _ in range(reverse)]
+        return more
 
     def _start_setup(self, defer_setup_exchange):
         """The set-up exchange (``setup_schedule``): now, or -- several ranks driven from one process, every rank must have
         posted before any completes -- by the driver through ``self._setup``."""
         self._setup = self.setup_schedule()
         if not defer_setup_exchange:
-            for _ in self._setup:
-                pass
+            run_schedule(self._setup)
+
+    def _reverse_setup(self, vectors):
+        """Generator: post the reverse scatters of the assembled ``vectors`` (one per closure of ``self._rev_setup``), yield, complete."""
+        if self.halo is not None:
+            from .scatterer import begin_all
+
+            pending = begin_all(zip(self._rev_setup, vectors, strict=True))
+            yield "reverse"
+            for sc, vec, wk in pending:
+                sc.end(vec, wk)
+
+    def check_halo_health(self, what="halo exchange"):
+        if self.halo is not None:
+            self.halo.check_health(what)
+
+
+class SpectralSolver3D(MeshSolver3D):
+    """The time loop of an explicit RK4 solver for u' = v, M v' = r(u, v, t) (see the module docstring for its hooks)."""
+
+    def _init_common(self, mesh, float_type, comm, fused, source_time):
+        """The attributes both wave solvers set first; returns the source and absorbing facet sets and the device geometry:
+        ``bd1, bd2, D, G, detJ, (dF1, dF2)``."""
+        self.fused, self.source_time = bool(fused), source_time
+        self.lean_stages = os.environ.get("FUS_RK4_LEAN", "1") != "0"  # the fused stage's vector pass: kinds 4-7 of csrc/rk4.hpp (_stage_args)
+        # the two tagged facet sets (cuda/demo_linear_box.py:230-243, cuda/utils.py:81-114): a structured box names them by its
+        # faces (x = 0: source, x = L: absorbing), a mesh handed over as arrays (dolfinx_adaptor.ArrayMesh) by its facet tags
+        bd1 = mesh.boundary_facets([getattr(mesh, "source_tag", 2)])
+        bd2 = mesh.boundary_facets([getattr(mesh, "absorbing_tag", 3)])
+        return (bd1, bd2) + self._init_mesh(mesh, float_type, comm, (bd1, bd2))
 
     def init(self):
         """u = v = 0 (cuda/demo_linear_box.py:434-435)."""
@@ -202,10 +283,6 @@ class SpectralSolver3D:
         # MPI Waitall, cuda/scatterer.py:175): raise.  One synchronisation per rk4() call.
         self.check_halo_health(f"{type(self).__name__}.rk4")
         return result
-
-    def check_halo_health(self, what="halo exchange"):
-        if self.halo is not None:
-            self.halo.check_health(what)
 
     def _recording(self, sensors, monitor, start_time, final_time, dt, max_steps, record_from):
         """Plan both recorders for this ``rk4`` call (``expect_steps``) and return ``record(t)``: the generator that records what is

@@ -280,18 +280,7 @@ def hybrid(args, proc, nproc, dev):
         assert len(gd[0][3]) == 7 and len(od[R - 1][3]) == 7 and min(int(v) for v in od[R - 1][1]) == 1
     what = args[9]
 
-    def lockstep(gens):
-        live = list(gens)
-        while live:
-            nxt = []
-            for g in live:
-                try:
-                    next(g)
-                    nxt.append(g)
-                except StopIteration:
-                    pass
-            live = nxt
-
+    lockstep = pkg("solver_base").run_lockstep
     if what == "apply":
         pts, wts, D = gll.tabulate_1d(P)
         n = P + 1

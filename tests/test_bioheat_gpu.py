@@ -327,19 +327,7 @@ def test_advance_warns_once_above_the_limit():
 
 
 # ---- 5. partitioned ----------------------------------------------------------------------------------------------------------------
-def _lockstep(gens):
-    out = [None] * len(gens)
-    live = list(enumerate(gens))
-    while live:
-        nxt = []
-        for i, g in live:
-            try:
-                next(g)
-                nxt.append((i, g))
-            except StopIteration as done:
-                out[i] = done.value
-        live = nxt
-    return out
+_lockstep = pkg("solver_base").run_lockstep
 
 
 @pytest.mark.parametrize("grid", [(2, 1, 1), (2, 2, 1)], ids=["2ranks", "4ranks"])
@@ -362,7 +350,12 @@ def test_partitioned_against_serial_cpu_loop(grid):
         wb = np.where(slab_of(mm), 0.05, 0.2) * lam * (mr["rho"] * mr["C"]) / RHO_B_C_B
         solvers.append(bh.BioheatSpectral3D(mm, np.float64, conductivity=mr["k"], density=mr["rho"], specific_heat=mr["C"], perfusion_rate=wb,
                                             comm=scat.NativeComm(local=(7300 + R, R, r)), halo_plan=(od[r], gd[r]), defer_setup_exchange=True))
+    with pytest.raises(pkg("_lib").FusGpuError, match="complete the set-up exchange first"):
+        solvers[0].set_heat_source(np.zeros(meshes[0].nlocal))
     _lockstep([s._setup for s in solvers])
+    for s in solvers:  # minv = fl(1 / mc) on the free dofs: fl(minv mc) = (1 + d1)(1 + d2), |d| <= eps / 2
+        free = s._free == 1
+        assert bool(free.any()) and float((s.minv[: s.nlocal] * s.mc - 1.0)[free].abs().max().item()) <= 2 * EPS64
     lex = [mm.global_lexicographic_ids()[: mm.nlocal] for mm in meshes]
     lex_serial = serial.global_lexicographic_ids()
     at = np.empty(serial.ndofs, dtype=np.int64)
@@ -374,6 +367,8 @@ def test_partitioned_against_serial_cpu_loop(grid):
     assert max(dts) == min(dts)
     serial_solver = bh.BioheatSpectral3D(serial, np.float64, conductivity=m["k"], density=m["rho"], specific_heat=m["C"], perfusion_rate=ref["wb"])
     dt_serial = serial_solver.stable_time_step(0.8)
+    vol, vol_serial = (math.fsum(np.concatenate([s.vol[: s.nlocal].cpu().numpy() for s in ss])) for ss in (solvers, [serial_solver]))
+    assert abs(vol / vol_serial - 1.0) <= 1e-13
     print("stable_time_step: ranks", dts[0], "serial", dt_serial)
     assert abs(dts[0] / dt_serial - 1.0) < 0.01
     dt, steps = dts[0], 12

@@ -328,18 +328,7 @@ def test_linear_solver_steps_array_meshes_two_in_process_ranks(transport):
     solvers = [ls.LinearSpectral3D(meshes[r], np.float64, comm=comms[r], fused=True, halo_plan=(od[r], gd[r]), defer_setup_exchange=True)
                for r in range(2)]
 
-    def lockstep(gens):
-        live = list(gens)
-        while live:
-            nxt = []
-            for g in live:
-                try:
-                    next(g)
-                    nxt.append(g)
-                except StopIteration:
-                    pass
-            live = nxt
-
+    lockstep = pkg("solver_base").run_lockstep
     lockstep([s._setup for s in solvers])
     for s in solvers:
         s.init()

@@ -273,19 +273,7 @@ def test_graph_replay_records_like_rk4(solver):
     assert _rel(a.u, b.u) < 1e-13
 
 
-def _lockstep(gens):
-    out = [None] * len(gens)
-    live = list(enumerate(gens))
-    while live:
-        nxt = []
-        for i, g in live:
-            try:
-                next(g)
-                nxt.append((i, g))
-            except StopIteration as done:
-                out[i] = done.value
-        live = nxt
-    return out
+_lockstep = pkg("solver_base").run_lockstep
 
 
 @pytest.mark.parametrize("fused", [True, False], ids=["fused", "reference-sequence"])

@@ -296,21 +296,7 @@ def test_nonlinear_bowl_driver_dumps_last_period(tmp_path, oracle_c):
     assert np.max(np.abs(last[:, 2] - u_ref[sel])) < 1e-7 + 1e-9 * np.max(np.abs(u_ref[sel]))
 
 
-def _lockstep(gens):
-    """Advance the generators of several in-process ranks together: each ``next`` runs a rank up to the point
-    where it has posted a set of halo exchanges; results are the generators' return values."""
-    out = [None] * len(gens)
-    live = list(enumerate(gens))
-    while live:
-        nxt = []
-        for i, g in live:
-            try:
-                next(g)
-                nxt.append((i, g))
-            except StopIteration as done:
-                out[i] = done.value
-        live = nxt
-    return out
+_lockstep = pkg("solver_base").run_lockstep
 
 
 @pytest.mark.parametrize("fused", [True, False], ids=["fused", "reference-sequence"])

@@ -251,19 +251,7 @@ def test_steering_mirrors_under_y_reflection():
     assert _rel(um[mirror], up) <= 1e-11  # ... and the mirrored steering mirrors it
 
 
-def _lockstep(gens):
-    out = [None] * len(gens)
-    live = list(enumerate(gens))
-    while live:
-        nxt = []
-        for i, g in live:
-            try:
-                next(g)
-                nxt.append((i, g))
-            except StopIteration as done:
-                out[i] = done.value
-        live = nxt
-    return out
+_lockstep = pkg("solver_base").run_lockstep
 
 
 @pytest.mark.parametrize("grid", [(1, 2, 1), (1, 2, 2)], ids=["2ranks", "4ranks"])

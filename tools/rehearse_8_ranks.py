@@ -68,18 +68,7 @@ def worker(a):
         halos.append(scat.HaloApply(mesh, op, comm, np.float64, plan=(od[r], gd[r]), schedule="concurrent"))
     setup_s = time.time() - t0
 
-    def lockstep(gens):
-        live = list(gens)
-        while live:
-            nxt = []
-            for g in live:
-                try:
-                    next(g)
-                    nxt.append(g)
-                except StopIteration:
-                    pass
-            live = nxt
-
+    lockstep = fusgpu_loader.submodule("solver_base").run_lockstep
     dist.barrier()
     # forward: poisoned ghosts must come back as the analytic field, exactly
     expect = []
