@@ -87,6 +87,7 @@ def _signatures():
         sig[f"fus_stiffness_apply_planned_{suf}"] = [_vp, _vp, _vp, _vp, _vp, _vp, _int, _i64, _vp]
         sig[f"fus_stiffness_apply_planned_affine_{suf}"] = [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _int, _i64, _vp]
         sig[f"fus_stiffness_apply_planned_geom_{suf}"] = [_vp] * 9 + [_int, _i64, _vp]
+        sig[f"fus_gradient_apply_planned_geom_{suf}"] = [_vp] * 3 + [_i64] + [_vp] * 6 + [_int, _i64, _vp]
         sig[f"fus_mass_apply_planned_{suf}"] = [_vp, _vp, _vp, _vp, _vp, _int, _int, _i64, _vp]
         sig[f"fus_mass_apply_{suf}"] = [_vp, _vp, _vp, _vp, _vp, _int, _i64, _vp]
         sig[f"fus_mass_apply_gather_{suf}"] = [_vp, _vp, _vp, _vp, _vp, _int, _i64, _vp]

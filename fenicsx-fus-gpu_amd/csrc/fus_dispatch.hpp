@@ -138,5 +138,8 @@ template <typename T>
 int westervelt_cell_geom(const T* u, const T* v, const T* c2, const T* c3, const T* c4, const T* c5, T* b, T* m, const T* x_g,
                          const int32_t* x_dofs, const T* pts, const T* wts, const void* ws, const T* dphi, int P, int64_t ncell,
                          void* stream);
+template <typename T>
+int gradient_apply_planned_geom(const T* x, const T* cc, T* y, int64_t ystride, const T* x_g, const int32_t* x_dofs, const T* pts,
+                                const T* wts, const void* ws, const T* dphi, int P, int64_t ncell, void* stream);  // dispatch_gradient.hip
 
 }  // namespace fus_abi

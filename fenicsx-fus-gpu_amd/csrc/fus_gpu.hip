@@ -646,6 +646,16 @@ FUS_GEOMK(double, f64)
 FUS_GEOMK(float, f32)
 #undef FUS_GEOMK
 
+#define FUS_GRADK(T, SUF)                                                                                             \
+  int fus_gradient_apply_planned_geom_##SUF(const T* x, const T* cc, T* y, int64_t ystride, const T* x_g,            \
+                                            const int32_t* x_dofs, const T* pts, const T* wts, const void* ws,       \
+                                            const T* dphi, int P, int64_t ncell, void* s) {                          \
+    return gradient_apply_planned_geom<T>(x, cc, y, ystride, x_g, x_dofs, pts, wts, ws, dphi, P, ncell, s);          \
+  }
+FUS_GRADK(double, f64)
+FUS_GRADK(float, f32)
+#undef FUS_GRADK
+
 #define FUS_WEST(T, SUF)                                                                                          \
   int fus_westervelt_cell_apply_planned_##SUF(const T* u, const T* v, const T* c2, const T* c3, const T* c4,      \
                                               const T* c5, T* b, T* m, const T* G, const T* detJ, const void* ws, \

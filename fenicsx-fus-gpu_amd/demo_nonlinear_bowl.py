@@ -13,6 +13,7 @@ cells (G varies per quadrature point; P1 geometry, cuda/demo_nonlinear_bowl.py:3
     python fenicsx-fus-gpu_amd/demo_nonlinear_bowl.py --sensor-plane 141,241 --out-dir DIR [--peak-out FILE]   # recorded on the device
     python fenicsx-fus-gpu_amd/demo_nonlinear_bowl.py --sensor-plane 61,61 --peak-out FILE --array 6,6 --focus 0.008,0.006,0.006
     python fenicsx-fus-gpu_amd/demo_nonlinear_bowl.py --field-stats maps.npz     # last-period maps of every dof, accumulated on the device
+    python fenicsx-fus-gpu_amd/demo_nonlinear_bowl.py --intensity                # the focus of the intensity |I| and the peak radiation force density |F|
     python fenicsx-fus-gpu_amd/demo_nonlinear_bowl.py --thermal 10 20            # then heat for 10 s and cool for 20 s with the last period's q (bioheat.py)
     python -m torch.distributed.run --nproc-per-node 8 fenicsx-fus-gpu_amd/demo_nonlinear_bowl.py
 
@@ -56,6 +57,10 @@ def main():
                     help="accumulate the last period of EVERY owned dof on the device in ONE rk4 call (field_monitor.FieldMonitor) and "
                          "write pmax, pmin, |H1|, |H2|, the heat deposition q and the focus of |H1| to FILE.npz (several ranks: "
                          "FILE.rank<r>.npz each, the focus reduced over the ranks)")
+    ap.add_argument("--intensity", action="store_true",
+                    help="implies --field-stats (without a FILE.npz nothing is written): after the run, print the focus of the time-averaged intensity |I| "
+                         "(intensity.py: from the harmonic maps and the gradient operator), the focal plane-wave estimate p1^2 / (2 rho c) beside it, "
+                         "and the peak radiation force density |F|")
     ap.add_argument("--thermal", default=None, nargs="+", type=float, metavar=("SECONDS_ON", "SECONDS_OFF"),
                     help="implies --field-stats (without a FILE.npz nothing is written): after the acoustic run, heat soft tissue for SECONDS_ON "
                          "with the heat deposition q of the last period and cool it for SECONDS_OFF (bioheat.BioheatSpectral3D: Pennes' equation, "
@@ -63,7 +68,7 @@ def main():
     a = ap.parse_args()
     if a.thermal is not None and (len(a.thermal) > 2 or min(a.thermal) < 0.0):
         ap.error("--thermal SECONDS_ON [SECONDS_OFF], both >= 0")
-    if (a.field_stats or a.thermal) and a.sensor_plane:
+    if (a.field_stats or a.thermal or a.intensity) and a.sensor_plane:
         ap.error("--field-stats and --sensor-plane are separate runs")
     if a.array and not a.sensor_plane:
         ap.error("--array needs --sensor-plane")
@@ -161,7 +166,7 @@ def main():
         run_with_sensors(a, solver, mesh, comm, rank, world, L, float_type, t0, tf, dt, nstep, budget, t_collect, step_per_period,
                          source_frequency)
         return
-    if a.field_stats or a.thermal:
+    if a.field_stats or a.thermal or a.intensity:
         run_with_monitor(a, solver, mesh, comm, rank, world, float_type, t0, tf, dt, nstep, budget, t_collect, step_per_period,
                          source_frequency)
         return
@@ -271,10 +276,31 @@ def run_with_monitor(a, solver, mesh, comm, rank, world, float_type, t0, tf, dt,
             print(f"Focus of |H1|: {out['focus_max']:.6g} Pa at {tuple(out['focus_position'])}, -6 dB volume {out['focus_volume']:.6g} m^3")
         print(f"Solve time: {el}")
         print(f"Solve time per step: {el / max(steps, 1)}")
+    if a.intensity and m.nacc:
+        run_intensity(solver, m, comm, rank, world)
     if a.thermal and m.nacc:
         run_thermal(a, solver, m, mesh, comm, rank, world, float_type)
     if world > 1:
         dist.destroy_process_group()
+
+
+def run_intensity(solver, monitor, comm, rank, world):
+    """The intensity vector and the radiation force density of the last period, from the monitor's harmonic maps and the gradient
+    operator (intensity.py); nothing leaves the device but the printed figures."""
+    import fusgpu_loader
+
+    fm, it = fusgpu_loader.submodule("field_monitor"), fusgpu_loader.submodule("intensity")
+    reduce = comm if world > 1 else None
+    mag_i = it.magnitude(monitor.intensity(solver))
+    foc = fm.focus(mag_i, solver, 0.5, reduce)
+    # beside it, for the reader: what a plane wave of the focal first-harmonic amplitude would carry (no check: a focus is not one)
+    p1 = fm.focus(monitor.harmonic_amplitude(1), solver, 0.5, reduce)["max"]
+    plane = p1 * p1 / (2.0 * float(np.mean(solver.rho_cells)) * float(np.mean(solver.c_cells)))
+    force = fm.focus(it.magnitude(monitor.radiation_force(solver)), solver, 0.5, reduce)
+    if rank == 0:
+        print(f"Focus of |I|: {foc['max']:.6g} W/m^2 at {foc['position']}, -6 dB volume {foc['volume']:.6g} m^3")
+        print(f"Plane-wave estimate p1^2 / (2 rho c) at the focus of |H1|: {plane:.6g} W/m^2")
+        print(f"Peak |F|: {force['max']:.6g} N/m^3 at {force['position']}")
 
 
 def run_thermal(a, solver, monitor, mesh, comm, rank, world, float_type):

@@ -143,6 +143,16 @@ class FieldMonitor:
     def heat_deposition(self, solver):
         return heat_deposition(self, solver)
 
+    def intensity(self, solver):
+        from .intensity import intensity
+
+        return intensity(self, solver)
+
+    def radiation_force(self, solver):
+        from .intensity import radiation_force
+
+        return radiation_force(self, solver)
+
     @staticmethod
     def focus(field, solver, level=0.5, comm=None):
         return focus(field, solver, level, comm)

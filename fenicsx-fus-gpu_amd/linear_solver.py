@@ -69,6 +69,7 @@ class LinearSpectral3D(SpectralSolver3D):
         c_cells, rho_cells = per_cell(speed_of_sound, mesh, "speed_of_sound"), per_cell(density, mesh, "density")
         bd1, bd2, D, G_d, detJ_d, (dF1_d, dF2_d) = self._init_common(mesh, float_type, comm, fused, source_time)
         self.c0, self.rho0 = float(c_cells.mean()), float(rho_cells.mean())
+        self.rho_cells, self.c_cells = rho_cells, c_cells  # per cell, the mesh's cell order (intensity.py)
         self.f0, self.p0 = float(source_frequency), float(source_amplitude)
         self.w0 = 2.0 * np.pi * self.f0
         P, n, dev, ft = self.P, self.P + 1, self.dev, self.tdt_np

@@ -837,6 +837,69 @@ def stiffness_operator(P, *args, affine_weights=None, geometry=None):
     raise TypeError("stiffness_operator(P, dphi, float_type) or stiffness_operator(P, float_type)")
 
 
+class _GradientOperator:
+    """Returned by ``gradient_operator``: ``op(x, cell_constants, y3, dofmap)`` adds the weak gradient C(c) x
+    (csrc/gradient_geom.hpp) to the three rows of ``y3``."""
+
+    def __init__(self, P, dphi, float_type, geometry):
+        if geometry is None or len(geometry) != 4:
+            raise ValueError("gradient_operator needs geometry=(x_dofs, x_g, pts, wts): the gradient is formed from the cell vertices")
+        if dphi is None:
+            raise ValueError("gradient_operator needs the 1-D derivative table dphi")
+        self._st = _StiffnessOperator(P, float_type, dphi, None, geometry)  # reuses table / geometry conversion + checks
+        self.P, self.n, self.dtype = self._st.P, self._st.n, self._st.dtype
+        self._fn = getattr(_lib.load(), f"fus_gradient_apply_planned_geom_{_lib.suffix(self.dtype)}")
+
+    def __call__(self, x, cell_constants, y3, dofmap):
+        dt = self.dtype
+        _req(x, dt, "x")
+        _req(cell_constants, dt, "cell_constants")
+        if isinstance(y3, torch.Tensor) and y3.dim() == 2 and y3.shape[0] == 3 and y3.stride(1) == 1:
+            _req(y3[0], dt, "y3")  # rows may be further apart than ndofs (a view): the kernel takes the row stride
+        else:
+            _req(y3, dt, "y3")
+            raise ValueError("y3 must be [3, ndofs] with contiguous rows")
+        _req(dofmap, torch.int32, "dofmap")
+        nd = self.n**3
+        if dofmap.dim() != 2 or dofmap.shape[1] != nd:
+            raise ValueError(f"dofmap must be [ncell, {nd}] for P={self.P}")
+        ncell = dofmap.shape[0]
+        ystride = y3.stride(0) if y3.shape[1] > 0 else 0
+        if x.dim() != 1 or y3.shape[1] != x.numel() or ystride < y3.shape[1]:
+            raise ValueError("x must be [ndofs] and y3 [3, ndofs] over the same dofs")
+        if cell_constants.numel() != ncell:
+            raise ValueError("cell_constants must have one value per cell")
+        xd, xg, pt, wt = self._st._geom
+        if xd.shape[0] != ncell:
+            raise ValueError(f"geometry: x_dofs has {xd.shape[0]} cells, dofmap has {ncell}")
+        if ncell == 0:
+            return
+        ws, _ = _PLANS.get(dofmap, strips=True)
+        _lib.check(
+            self._fn(x.data_ptr(), cell_constants.data_ptr(), y3.data_ptr(), int(ystride), xg.data_ptr(), xd.data_ptr(), pt.data_ptr(),
+                     wt.data_ptr(), ws.data_ptr(), self._st._dphi.data_ptr(), self.P, int(ncell), _lib.stream_ptr()),
+            "fus_gradient_apply_planned_geom",
+        )
+
+    def prepare(self, dofmap):
+        """Set-up, not an apply: build (and cache) the batch plan for ``dofmap`` now."""
+        _req(dofmap, torch.int32, "dofmap")
+        if dofmap.shape[0] > 0:
+            _PLANS.get(dofmap, strips=True)
+
+
+def gradient_operator(P, dphi, float_type, geometry=None):
+    """``gradient_operator(P, dphi, float_type, geometry=(x_dofs, x_g, pts, wts))`` -> ``op(x, cell_constants, y3, dofmap)``
+    (no reference counterpart).  ``y3[d] += C_d(c) x``, the weak gradient
+
+        y_d[i] += sum_cells c_cell sum_{q: dof(cell, q) = i} w_q |det J_q| (dx / dx_d)(q)
+
+    with the geometry formed in the kernel from the 8 vertices of each (trilinear) cell, in the conventions of
+    ``stiffness_operator(..., geometry=)``; ``y3`` is a ``[3, ndofs]`` tensor with contiguous rows (a view whose row stride
+    exceeds ``ndofs`` is accepted).  ``y3 / (M(1) 1)`` is the lumped-mass projection of ``c grad x`` (``intensity.recovered_gradient``)."""
+    return _GradientOperator(P, dphi, float_type, geometry)
+
+
 def _stiffness_only_ncell(op, u, v, c3, c4, b, dofmap):
     """The argument checks of a Westervelt cell operator's ``stiffness_only``; returns the number of cells."""
     for name, t in (("u", u), ("v", v), ("c3", c3), ("c4", c4), ("b", b)):

@@ -275,6 +275,26 @@ int fus_stiffness_apply_planned_geom_f32(const float* x, const float* cell_const
                                          const void* workspace, const float* dphi, int P, int64_t ncell, void* stream);
 
 /*
+ * Weak gradient C(c) x with the geometry formed in the kernel from the 8 vertices of each cell (no reference counterpart; the
+ * conventions are those of fus_stiffness_apply_planned_geom_*: J_[a][d] = d x_d / d xi_a, trilinear cells, the tensor GLL rule
+ * q = qx n^2 + qy n + qz).  Three vectors, d = 0, 1, 2, component d at y + d * ystride:
+ *   y_d[i] += sum_cells c_cell  sum_{q : dof(cell, q) = i}  w_q |det J_q| (d x / d x_d)(q),   grad = inv(J_) grad_xi
+ * (the GLL points are the nodes: no backward contraction).  y_d / (M(1) 1)_i is the lumped-mass projection of c grad x.
+ *   y        T[3][ystride], ystride >= number of dofs (in elements); contributions are ADDED, one atomic per distinct dof of a batch
+ *            and component
+ *   x_g, x_dofs, pts, wts, workspace, dphi   as for fus_stiffness_apply_planned_geom_* (the same plan serves both)
+ * Checks in the order of the planned cell operators: ncell < 0 -> FUS_ERR_INVALID_ARGUMENT, the degree -> FUS_ERR_UNSUPPORTED_DEGREE,
+ * ncell == 0 -> FUS_OK, a null pointer (y included) or ystride < 0 -> FUS_ERR_INVALID_ARGUMENT, the plan -> FUS_ERR_PLAN_MISMATCH;
+ * all before any device work.
+ */
+int fus_gradient_apply_planned_geom_f64(const double* x, const double* cell_constants, double* y, int64_t ystride, const double* x_g,
+                                        const int32_t* x_dofs, const double* pts, const double* wts, const void* workspace,
+                                        const double* dphi, int P, int64_t ncell, void* stream);
+int fus_gradient_apply_planned_geom_f32(const float* x, const float* cell_constants, float* y, int64_t ystride, const float* x_g,
+                                        const int32_t* x_dofs, const float* pts, const float* wts, const void* workspace,
+                                        const float* dphi, int P, int64_t ncell, void* stream);
+
+/*
  * Generic batch plan (any entity kind: cells N = n^3, boundary facets N = n^2) and planned mass
  * apply.  fus_plan_entities_per_batch(N) returns the preferred batch size (for cells it equals
  * the stiffness plan's, so ONE workspace built from the cell dofmap serves both operators:

@@ -63,6 +63,10 @@ struct Abi<double> {
                        int64_t nc, void* s) {
     return fus_stiffness_apply_planned_f64(x, c, y, G, ws, dphi, P, nc, s);
   }
+  static int gradient(const double* x, const double* c, double* y, int64_t ys, const double* xg, const int32_t* xd, const double* pts, const double* wts,
+                      const void* ws, const double* dphi, int P, int64_t nc, void* s) {
+    return fus_gradient_apply_planned_geom_f64(x, c, y, ys, xg, xd, pts, wts, ws, dphi, P, nc, s);
+  }
   static int mass(const double* x, const double* c, double* y, const double* dJ, const void* ws, int N, int epb, int64_t ne,
                   void* s) {
     return fus_mass_apply_planned_f64(x, c, y, dJ, ws, N, epb, ne, s);
@@ -104,6 +108,10 @@ struct Abi<float> {
   static int stiffness(const float* x, const float* c, float* y, const float* G, const void* ws, const float* dphi, int P, int64_t nc,
                        void* s) {
     return fus_stiffness_apply_planned_f32(x, c, y, G, ws, dphi, P, nc, s);
+  }
+  static int gradient(const float* x, const float* c, float* y, int64_t ys, const float* xg, const int32_t* xd, const float* pts, const float* wts,
+                      const void* ws, const float* dphi, int P, int64_t nc, void* s) {
+    return fus_gradient_apply_planned_geom_f32(x, c, y, ys, xg, xd, pts, wts, ws, dphi, P, nc, s);
   }
   static int mass(const float* x, const float* c, float* y, const float* dJ, const void* ws, int N, int epb, int64_t ne, void* s) {
     return fus_mass_apply_planned_f32(x, c, y, dJ, ws, N, epb, ne, s);
@@ -346,6 +354,38 @@ private:
   const T* G_ = nullptr;
   detail::DeviceBuffer<T> G_own_;
   const T* dphi_ = nullptr;
+  detail::Plan plan_;
+};
+
+/// y[d] += C_d(coeffs) x, d = 0, 1, 2: the weak gradient with the geometry formed in the kernel (fus_gradient_apply_planned_geom_*;
+/// no reference counterpart).  Divided by the lumped mass M(1) 1 it is the nodal projection of coeffs * grad x.
+template <typename T, int P>
+class GradientSpectral3D {
+  static_assert(std::is_same<T, double>::value || std::is_same<T, float>::value, "T: float or double");
+  static_assert(P >= FUS_MIN_DEGREE && P <= FUS_MAX_DEGREE, "degree out of range");
+
+public:
+  static constexpr int Nd = (P + 1) * (P + 1) * (P + 1);
+  /// x_g [nvert][3], x_dofs [ncells][8], pts / wts: 1-D GLL points on [0, 1] and weights T[P+1], dphi T[P+1][P+1]: device arrays
+  GradientSpectral3D(const int32_t* dofmap, int64_t ncells, const T* x_g, const int32_t* x_dofs, const T* pts, const T* wts, const T* dphi,
+                     hipStream_t stream = nullptr)
+      : Nc(ncells), x_g_(x_g), x_dofs_(x_dofs), pts_(pts), wts_(wts), dphi_(dphi) {
+    check_abi();
+    plan_.build(dofmap, Nd, Nc, stream);
+  }
+  GradientSpectral3D(const GradientSpectral3D&) = delete;
+  GradientSpectral3D& operator=(const GradientSpectral3D&) = delete;
+  /// y: T[3][ystride], ystride >= number of dofs; contributions are added
+  void operator()(const T* x, const T* coeffs, T* y, int64_t ystride, hipStream_t stream = nullptr) const {
+    check(detail::Abi<T>::gradient(x, coeffs, y, ystride, x_g_, x_dofs_, pts_, wts_, plan_.ws, dphi_, P, Nc, stream),
+          "fus_gradient_apply_planned_geom");
+  }
+
+private:
+  int64_t Nc;
+  const T* x_g_ = nullptr;
+  const int32_t* x_dofs_ = nullptr;
+  const T *pts_ = nullptr, *wts_ = nullptr, *dphi_ = nullptr;
   detail::Plan plan_;
 };
 

@@ -29,6 +29,8 @@ def compile_tree(root):
     newest = max(os.path.getmtime(p) for p in srcs)
     procs, files = [], []
     for src, defs in ru.UNITS:
+        if not os.path.exists(os.path.join(csrc, src)):  # a unit the other tree does not have yet: its kernels are "only in" one tree
+            continue
         stem = os.path.join(out, src[:-4] + "".join(d.replace("-DFUS_INST_T=", "_") for d in defs))
         files.append(stem)
         if os.path.exists(stem + ".s") and os.path.exists(stem + ".txt") and os.path.getmtime(stem + ".txt") >= newest:
