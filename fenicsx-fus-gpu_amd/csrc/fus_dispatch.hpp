@@ -7,10 +7,9 @@
 #include <hip/hip_runtime.h>
 
 #include <atomic>
-#include <mutex>
-#include <unordered_map>
 
 #include "plan.hpp"
+#include "plan_registry.hpp"
 
 namespace fus_abi {
 
@@ -40,37 +39,9 @@ inline bool plan_use_runs(int ndof_per_entity, bool runs_pay = true) {
 }
 inline std::atomic<int> g_plan_variant{-1};  // -1 = auto
 
-// Host mirror of the plans built through this library, keyed by workspace address: the apply entry
-// points check that a workspace was built, and for the (N, entities per batch, entity count) they are
-// called with, before any kernel indexes it (a mismatch would gather / scatter out of bounds), and
-// learn from it whether the plan carries a cell order.
-struct PlanInfo {
-  int N = 0, epb = 0;
-  int64_t nent = 0;
-  bool ordered = false;
-  bool exclusive = false;  // fus_plan_mark_exclusive has run: the plan carries exclusive-dof marks
-  bool runs_pay = true;    // at least half of the batches carry a run table (plan_use_runs)
-  int64_t nbatch = 0, with_runs = 0;
-};
-inline std::mutex g_plans_mu;
-inline std::unordered_map<const void*, PlanInfo> g_plans;
-
-inline void plan_register(const void* ws, int N, int epb, int64_t nent, bool ordered, int64_t nbatch = 0, int64_t with_runs = 0) {
-  std::lock_guard<std::mutex> lk(g_plans_mu);
-  g_plans[ws] = PlanInfo{N, epb, nent, ordered, false, 2 * with_runs >= nbatch, nbatch, with_runs};
-}
-// true if ``ws`` holds a plan for exactly this shape; ``ordered`` out
-inline bool plan_check(const void* ws, int N, int epb, int64_t nent, bool* ordered, bool* exclusive = nullptr, bool* runs_pay = nullptr) {
-  std::lock_guard<std::mutex> lk(g_plans_mu);
-  auto it = g_plans.find(ws);
-  if (it == g_plans.end()) return false;
-  const PlanInfo& p = it->second;
-  if (p.N != N || p.epb != epb || p.nent != nent) return false;
-  *ordered = p.ordered;
-  if (exclusive) *exclusive = p.exclusive;
-  if (runs_pay) *runs_pay = p.runs_pay;
-  return true;
-}
+// The one workspace registry of the library (plan_registry.hpp) is defined in fus_gpu.hip, where the header type of the gather plans is
+// complete.  true if ``ws`` holds a batch plan for exactly this shape; ``ordered`` out
+bool plan_check(const void* ws, int N, int epb, int64_t nent, bool* ordered, bool* exclusive = nullptr, bool* runs_pay = nullptr);
 
 inline int hip_rc(hipError_t e) { return e == hipSuccess ? FUS_OK : FUS_ERR_HIP_BASE - (int)e; }
 
@@ -119,7 +90,6 @@ int planned_cell_entry(bool args_ok, const void* ws, int P, int64_t ncell, L&& l
   degree_dispatch(P, [&](auto p) { e = launch(p, ord, use_runs); });
   return hip_rc(e);
 }
-
 
 // ---- the planned cell operators: defined and explicitly instantiated (one object per operator family and scalar type, compiled in
 // parallel: Makefile) in dispatch_stiffness_plan.hip, dispatch_geometry.hip and dispatch_westervelt.hip

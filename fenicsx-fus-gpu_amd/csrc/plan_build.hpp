@@ -174,7 +174,7 @@ inline hipError_t launch_plan_build_generic(const int32_t* dofmap, int N, int ep
 
 // How many batches of a built plan carry a run table (the others kept their raw list: too many runs, or no gain).  Waits for the
 // build on ``stream``; the apply entry points launch the run-coded form of their kernels only for plans where that pays
-// (fus_dispatch.hpp: plan_register).
+// (plan_registry.hpp: PlanInfo::runs_pay).
 inline hipError_t plan_run_batches(const void* workspace, hipStream_t stream, int64_t* out) {
   unsigned long long c = 0;
   hipError_t e = hipMemcpyAsync(&c, static_cast<const char*>(workspace) + kPlanHeaderRunBatches, sizeof(c), hipMemcpyDeviceToHost, stream);

@@ -55,7 +55,8 @@ extern "C" {
  *      Added since without a bump (new symbols only): fus_mass_gather_plan_bytes / _build / _info, fus_mass_apply_gather_*,
  *      fus_mass_gather_plan_build_rows, fus_mass_gather_static_bytes / _build_* , fus_mass_apply_gather_static_*,
  *      fus_probe_eval_*, fus_facet_source_array_* / fus_facet_source_array_dev_*, fus_field_accumulate_*,
- *      fus_bioheat_stage_*.
+ *      fus_bioheat_stage_*.  Tightened without a bump: a build at a workspace address replaces what any family had registered
+ *      there; fus_rk4_stage_nl_* rejects new_step outside 0..3.
  * There are deliberately NO fus_cpu_* twins of the entry points (SURVEY.md 8b proposed them): a CPU path inside the
  * product would be a silent fallback; the CPU restatement of the reference is test infrastructure and lives outside the product tree.
  */
@@ -96,7 +97,8 @@ int fus_stiffness_apply_f32(const float* x, const float* cell_constants, float* 
  * Built once per dofmap on the device into a caller-owned workspace; see csrc/plan.hpp for the
  * layout.  Workspace contract: a planned apply accepts only a workspace that was BUILT through this library AT THAT
  * ADDRESS (host-side registry; anything else is FUS_ERR_PLAN_MISMATCH): do not copy or relocate a built workspace,
- * and call fus_plan_release(workspace) before freeing or reusing its memory.  The reference has no counterpart: its CUDA kernel issues one atomic per (cell, dof)
+ * and call fus_plan_release(workspace) before freeing or reusing its memory.  A build at an address REPLACES whatever was registered there, of
+ * any family (batch plan, transposed gather plan, static companion): only the kind built last is accepted with that address.  The reference has no counterpart: its CUDA kernel issues one atomic per (cell, dof)
  * (cuda/operators.py:190).  The planned apply reads the plan INSTEAD of ``dofmap``.
  *   fus_stiffness_plan_bytes : workspace size in bytes for (P, ncell), or a negative error code
  *   fus_stiffness_plan_build : fill ``workspace`` (256-byte aligned) from ``dofmap``; asynchronous
@@ -477,7 +479,8 @@ int fus_rk4_stage_f32(float bw, float aw, int new_step, const float* minv, float
  * launches over the same cells per RK4 stage (cuda/demo_nonlinear_bowl.py:612-632 + square :603)
  *   b += K(c3) u + K(c4) v + M(c5) v^2 ;   m += M(c2) u
  * reading G and detJ once and gathering u, v once.  c2..c5: per-cell constants T[ncell].
- * fus_rk4_stage_nl_*: fus_rk4_stage_* for a stage-dependent lumped mass: kv = b / m, then m = m0.
+ * fus_rk4_stage_nl_*: fus_rk4_stage_* for a stage-dependent lumped mass: kv = b / m, then m = m0.  new_step 0..3 only (the lean kinds 4..7
+ * exist for fus_rk4_stage_* and fus_rk4_stage_nl2_*): any other value is FUS_ERR_INVALID_ARGUMENT.
  *
  * Diagonal form (what the Westervelt solver of this repo runs): with GLL collocation the mass operator
  * is diagonal, M(c) x = diag(M(c) 1) x, so the two mass terms can be applied pointwise from diagonals

@@ -63,6 +63,20 @@ def test_argument_validation_precedes_device_work():
     assert lib.fus_unpack_rev_f64(one, z, one, 3, z) == -1
     assert lib.fus_stiffness_plan_build(one, 4, 10, C.c_void_p(257), 1 << 30, z) == -1  # misaligned workspace
     assert lib.fus_stiffness_plan_build(one, 4, 10, one, 16, z) == -1  # workspace too small
+    # an address nothing was built at: every family answers from the workspace registry, before any launch
+    ws, sws, out4 = C.c_void_p(512), C.c_void_p(768), (C.c_int64 * 4)()
+    assert lib.fus_mass_apply_gather_f64(one, one, one, one, ws, 8, 1, z) == -6
+    assert lib.fus_mass_apply_gather_static_f64(one, one, one, ws, sws, 8, 1, z) == -6
+    assert lib.fus_mass_gather_static_build_f64(ws, one, sws, 1 << 30, z) == -6
+    assert lib.fus_mass_gather_plan_info(ws, out4) == -6
+    assert lib.fus_plan_encoding(ws, None, None, None, None) == -6
+    assert lib.fus_mass_apply_planned_f64(one, one, one, one, ws, 8, 4, 1, z) == -6
+    assert lib.fus_stiffness_apply_planned_f64(one, one, one, one, ws, one, 2, 1, z) == -6
+    assert lib.fus_plan_release(ws) == 0
+    # the lean stage kinds 4..7 exist for fus_rk4_stage and fus_rk4_stage_nl2 only
+    nl = lambda new_step, ntotal, p: lib.fus_rk4_stage_nl_f64(1.0, 1.0, new_step, p, p, p, p, p, p, p, p, p, ntotal, ntotal, z)  # noqa: E731
+    assert nl(4, 1, one) == -1 and nl(-1, 1, one) == -1
+    assert nl(0, 0, z) == 0 and nl(9, 0, one) == 0  # nothing to do: no-op whatever the pointers
 
 
 def test_product_has_no_cpu_fallback():

@@ -771,6 +771,73 @@ def test_planned_apply_rejects_foreign_workspace(gpu):
     torch.cuda.synchronize()
 
 
+def test_workspace_kinds_are_exclusive(gpu):
+    """One registry for the three kinds of workspace: a build at an address replaces what another kind had registered there, so an apply of
+    the replaced kind is refused (FUS_ERR_PLAN_MISMATCH, from the look-up that precedes its launch) instead of indexing a workspace that
+    now holds something else; a release forgets the address and the static companions of the plan at it."""
+    import ctypes as C
+
+    import torch
+
+    lib = pkg("_lib").load()
+    pb = build_problem(2, (3, 3, 3))
+    mesh = pb["mesh"]
+    d = torch.device("cuda", 0)
+    N, ncells, nd = 27, mesh.ncells, mesh.ndofs
+    x, cc, G, dm, D = (torch.from_numpy(a).to(d) for a in (pb["x"], pb["cc"], pb["G"], mesh.dofmap, pb["D"]))
+    plan_bytes, gather_bytes = int(lib.fus_stiffness_plan_bytes(2, ncells)), int(lib.fus_mass_gather_plan_bytes(N, ncells, nd))
+    static_bytes = int(lib.fus_mass_gather_static_bytes(N, ncells, 8))
+    assert min(plan_bytes, gather_bytes, static_bytes) > 0
+    aligned = lambda t: t.data_ptr() + (-t.data_ptr() % 256)  # noqa: E731
+    ws, ws_fresh, sws = (torch.zeros(n + 512, dtype=torch.uint8, device=d) for n in (max(plan_bytes, gather_bytes), plan_bytes, static_bytes))
+    base, fresh, companion = aligned(ws), aligned(ws_fresh), aligned(sws)
+    epb = lib.fus_plan_entities_per_batch(N)
+    info = (C.c_int64 * 4)()
+
+    def stiffness(at):
+        y = torch.zeros_like(x)
+        return lib.fus_stiffness_apply_planned_f64(x.data_ptr(), cc.data_ptr(), y.data_ptr(), G.data_ptr(), at, D.data_ptr(), 2, ncells, None), y
+
+    # the gather applies of the 300 x 8 case of test_mass_gather_policy_and_errors: unit constants, y = (entries of the dof) * x
+    xx = torch.arange(1, nd + 1, dtype=torch.float64, device=d)
+    ones_c, ones_dj = torch.ones(ncells, dtype=torch.float64, device=d), torch.ones((ncells, N), dtype=torch.float64, device=d)
+    y_ref = np.bincount(mesh.dofmap.reshape(-1), minlength=nd) * np.arange(1, nd + 1)
+
+    def gather():
+        y = torch.zeros(nd, dtype=torch.float64, device=d)
+        return lib.fus_mass_apply_gather_f64(xx.data_ptr(), ones_c.data_ptr(), y.data_ptr(), ones_dj.data_ptr(), base, N, ncells, None), y
+
+    def gather_static():
+        y = torch.zeros(nd, dtype=torch.float64, device=d)
+        return lib.fus_mass_apply_gather_static_f64(xx.data_ptr(), ones_c.data_ptr(), y.data_ptr(), base, companion, N, ncells, None), y
+
+    try:
+        assert lib.fus_stiffness_plan_build(dm.data_ptr(), 2, ncells, base, plan_bytes, None) == 0  # (a)
+        assert lib.fus_stiffness_plan_build(dm.data_ptr(), 2, ncells, fresh, plan_bytes, None) == 0
+        (rc, y), (rc_fresh, y_fresh) = stiffness(base), stiffness(fresh)  # (b)
+        assert rc == 0 and rc_fresh == 0
+        _check(y.cpu().numpy(), y_fresh.cpu().numpy(), np.float64, "planned stiffness, shared against fresh workspace")
+        assert lib.fus_mass_gather_plan_build(dm.data_ptr(), N, ncells, nd, base, gather_bytes, None) == 0  # (c): same address, other kind
+        assert stiffness(base)[0] == -6  # (d)
+        assert lib.fus_plan_encoding(base, None, None, None, None) == -6
+        assert lib.fus_mass_apply_planned_f64(x.data_ptr(), cc.data_ptr(), y.data_ptr(), ones_dj.data_ptr(), base, N, epb, ncells, None) == -6
+        rc, yg = gather()  # (e)
+        assert rc == 0
+        assert np.allclose(yg.cpu().numpy(), y_ref)
+        assert lib.fus_mass_gather_static_build_f64(base, ones_dj.data_ptr(), companion, static_bytes, None) == 0  # (f)
+        rc, ys = gather_static()
+        assert rc == 0 and torch.equal(ys, yg)
+        assert lib.fus_stiffness_plan_build(dm.data_ptr(), 2, ncells, base, plan_bytes, None) == 0  # (g): back to the batch plan
+        assert gather()[0] == -6 and gather_static()[0] == -6 and lib.fus_mass_gather_plan_info(base, info) == -6  # (h)
+        assert lib.fus_plan_release(base) == 0  # (i)
+        assert stiffness(base)[0] == -6
+        assert lib.fus_plan_release(base) == 0
+        torch.cuda.synchronize()
+    finally:
+        for at in (base, fresh, companion):
+            lib.fus_plan_release(at)
+
+
 @pytest.mark.parametrize("dtype", [np.float64, np.float32], ids=["f64", "f32"])
 @pytest.mark.parametrize("P", list(range(1, 11)))
 def test_westervelt_cell_pass_in_kernel_geometry(gpu, oracle_c, P, dtype):

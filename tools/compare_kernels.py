@@ -5,7 +5,8 @@
 
 Every translation unit of libfusgpu.so (resource_usage.UNITS) is compiled device-only to assembly in both trees with the Makefile's flags;
 the output is split by kernel symbol and stripped of comment and directive lines (the rule of tests/test_kernel_isa.py).  A kernel whose
-instruction list is equal is reported ``identical``; any other with the resource lines of both trees (kernel-resource-usage remarks,
+instruction list is equal is reported ``identical`` (branch targets without the number of the function in its unit, ``.LBB<function>_<block>``:
+it changes when code is only moved between units); any other with the resource lines of both trees (kernel-resource-usage remarks,
 resource_usage.parse) and the opcodes whose counts differ.  No GPU needed.  Exit status 1 if a kernel differs or exists in one tree only."""
 import collections
 import os
@@ -58,7 +59,7 @@ def split_kernels(asm):
         if cur is not None:
             s = ln.strip()
             if s and not s.startswith((";", ".")):
-                found[cur].append(s)
+                found[cur].append(re.sub(r"\.LBB\d+_(\d+)", r".LBB_\1", s))
             if s.startswith("s_endpgm"):
                 cur = None
     return {k: v for k, v in found.items() if v and v[-1].startswith("s_endpgm")}

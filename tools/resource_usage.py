@@ -44,7 +44,7 @@ def parse(text):
 
 
 # the translation units of libfusgpu.so (csrc/Makefile): (source, defines)
-UNITS = [("fus_gpu.hip", ())] + [(f"{d}.hip", (f"-DFUS_INST_T={t}",)) for d in ("dispatch_stiffness_plan", "dispatch_geometry", "dispatch_westervelt", "dispatch_gradient")
+UNITS = [("fus_gpu.hip", ()), ("abi_halo.hip", ())] + [(f"{d}.hip", (f"-DFUS_INST_T={t}",)) for d in ("dispatch_stiffness_plan", "dispatch_geometry", "dispatch_westervelt", "dispatch_gradient")
                                    for t in ("double", "float")]
 
 
