@@ -11,7 +11,9 @@ Modules
 -------
 operators   mass / stiffness / vector-op call surface (numba-cpu factories and
             cuda ``kernel[grid, block](...)`` launch style) over the C ABI
-scatterer   scatter_forward / scatter_reverse (halo exchange)
+scatterer   scatter_forward / scatter_reverse (halo exchange); re-exports comm and halo_apply
+comm        NativeComm / TorchComm, as_comm, the bootstrap gathers
+halo_apply  HaloApply: the partitioned apply overlapped with the exchange
 utils       compute_scatterer_data
 precompute  detJ / G / facet detJ (host)
 boxmesh     synthetic structured hex meshes + block partitioning

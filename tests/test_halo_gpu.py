@@ -812,3 +812,101 @@ def test_fork_join_enforce_one_caller_stream(gpu):
     assert wrong == 0 and comm.health() == 0, f"{wrong} of {big.numel()} elements != 41 (min {float(big.min())}, max {float(big.max())})"
     del big
     comm.close()
+
+
+def test_concurrent_schedule_issue_order_two_in_process_ranks(gpu, oracle_c):
+    """What the concurrent schedule issues, in order, per rank (two in-process PEER ranks, applied twice in lock step): the fork
+    of the communicator's stream (lazy: folded into the first send kernel), ONE interior launch on the caller's stream, the
+    forward exchange, the boundary launch on the communicator's stream, the armed join, the reverse exchange, the join.  The
+    second apply is the warm one: its fork signal is attached to the interior launch and flushed directly after it, before the
+    forward exchange is posted.  A rank without boundary or without interior cells has no such launch.  Result against the serial
+    apply, and no failed device-side wait."""
+    torch = gpu
+    boxmesh, scat, ops, gll, pre, utils = (pkg(m) for m in ("boxmesh", "scatterer", "operators", "gll", "precompute", "utils"))
+    P, cells, grid, R = 2, (4, 2, 2), (2, 1, 1), 2
+    wid = next(_world_ids)
+    dev = torch.device("cuda", 0)
+    pts, wts, D = gll.tabulate_1d(P)
+    w3 = gll.tensor_weights_3d(wts)
+    dg = pre.tabulate_hex_p1_gradients(gll.tensor_points_3d(pts))
+    op = ops.stiffness_operator(P, D.flatten(), np.float64)
+    caller = torch.cuda.current_stream().cuda_stream
+    log = []  # the entries of the apply in progress, per rank
+
+    class Launches:  # the operator, recording each launch's cell count and stream
+        def __init__(self, r, comm):
+            self.r, self.comm = r, comm
+
+        def __call__(self, x, c, y, G, d):
+            s = torch.cuda.current_stream().cuda_stream
+            where = "caller" if s == caller else "comm" if s == self.comm.stream().cuda_stream else "other"
+            log[self.r].append(("launch", int(d.shape[0]), where))
+            op(x, c, y, G, d)
+
+    def recorded(r, fn, entry):
+        def call(*a, **k):
+            log[r].append(entry(*a, **k) if callable(entry) else entry)
+            return fn(*a, **k)
+        return call
+
+    ranks = []
+    for r in range(R):
+        mesh = boxmesh.BoxMesh(P, cells, grid=grid, rank=r, perturb=0.16, seed=3)
+        G = np.zeros((mesh.ncells, (P + 1)**3, 6))
+        pre.compute_scaled_geometrical_factor(G, (mesh.x_dofs, mesh.x_g), mesh.ncells, dg, w3)
+        x = ref_field(mesh.dof_coordinates())
+        x[mesh.nlocal:] = -777.0
+        ranks.append(dict(mesh=mesh, x=torch.from_numpy(x).to(dev), y=torch.zeros(mesh.ndofs, dtype=torch.float64, device=dev),
+                          cc=torch.from_numpy(global_cell_constants(mesh)).to(dev), G=torch.from_numpy(G).to(dev),
+                          dm=torch.from_numpy(mesh.dofmap).to(dev)))
+    od, gd = utils.compute_scatterer_data_all([rk["mesh"].index_map for rk in ranks])
+    halos = []
+    for r, rk in enumerate(ranks):
+        comm = scat.NativeComm(local=(wid, R, r), transport="peer")
+        h = scat.HaloApply(rk["mesh"], Launches(r, comm), comm, np.float64, plan=(od[r], gd[r]), schedule="concurrent")
+        assert h.schedule_kind == "concurrent"
+        comm.fork = recorded(r, comm.fork, lambda lazy=False, attach=False: ("fork", bool(lazy), bool(attach)))
+        for name in ("fork_flush", "arm_join", "join"):
+            setattr(comm, name, recorded(r, getattr(comm, name), name))
+        for sc, tag in ((h.fwd, "f"), (h.rev, "r")):
+            sc.begin = recorded(r, sc.begin, f"begin {tag}")
+            sc.end = recorded(r, sc.end, f"end {tag}")
+        halos.append(h)
+    logs = []
+    for rep in range(2):
+        log = [[] for _ in range(R)]
+        for rk in ranks:
+            rk["y"].zero_()
+        live = [(r, h.apply_schedule(rk["x"], rk["cc"], rk["y"], rk["G"], rk["dm"])) for r, (h, rk) in enumerate(zip(halos, ranks))]
+        while live:  # lock step: every rank posts before any rank completes
+            nxt = []
+            for r, g in live:
+                try:
+                    next(g)
+                    log[r].append("yield")
+                    nxt.append((r, g))
+                except StopIteration:
+                    pass
+            live = nxt
+        logs.append(log)
+    torch.cuda.synchronize()
+    for rep, warm in enumerate((False, True)):
+        for r, rk in enumerate(ranks):
+            nb, nc = rk["mesh"].num_boundary_cells, rk["mesh"].ncells
+            interior = [("launch", nc - nb, "caller")] if nc > nb else []
+            boundary = [("launch", nb, "comm")] if nb > 0 else []
+            attach = warm and nc > nb
+            want = [("fork", True, attach)] + interior + (["fork_flush"] if attach else []) + ["begin f", "yield", "end f"] + boundary + \
+                   ["arm_join", "begin r", "yield", "end r", "join"]
+            print(f"apply {rep} rank {r}: {logs[rep][r]}")
+            assert logs[rep][r] == want, f"apply {rep} rank {r}"
+    pb = build_problem(P, cells, perturb=0.16, seed=3)
+    ms = pb["mesh"]
+    y_ser = np.zeros(ms.ndofs)
+    oracle_c.stiffness_apply(P, pb["D"], pb["x"], global_cell_constants(ms), y_ser, pb["G"], ms.dofmap)
+    for rk in ranks:
+        m = rk["mesh"]
+        lex = m.global_lexicographic_ids()
+        assert rel_l2(rk["y"].cpu().numpy()[: m.nlocal], y_ser[lex[: m.nlocal]]) < 1e-12
+        assert np.allclose(rk["x"].cpu().numpy(), pb["x"][lex], rtol=0, atol=1e-12)  # ghosts refreshed
+    assert all(h.comm.health() == 0 for h in halos)

@@ -173,7 +173,7 @@ def test_gather_arrays_through_a_bootstrap():
             return [payload, payload]
 
     class InProcess:  # NativeComm(local=...): a handle, no bootstrap
-        size, handle, _torch = 2, 1, None
+        size, handle, bootstrap = 2, 1, None
 
     arrays = {"ids": np.arange(3), "values": np.arange(6.0).reshape(2, 3), "max": 2.5}
     every = scat.gather_arrays(Boot(), arrays, "gather", "sensors.merge")

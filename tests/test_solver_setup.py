@@ -9,10 +9,10 @@ from conftest import pkg
 
 
 def test_gather_floats():
-    """float64 [size, k] in rank order through a bootstrap (a NativeComm carries its own in ``_torch``); no communicator, one rank, a
+    """float64 [size, k] in rank order through a bootstrap (a NativeComm carries its own in ``bootstrap``); no communicator, one rank, a
     handle without a bootstrap: the local row.  ``BioheatSpectral3D._gather`` raises where the rows do not cover every rank."""
     boot = types.SimpleNamespace(size=2, allgather_bytes=lambda blob: [blob, (-np.frombuffer(blob, dtype="<f8")).tobytes()])
-    native = lambda size, bootstrap: types.SimpleNamespace(size=size, rank=0, handle=1, _torch=bootstrap)  # noqa: E731
+    native = lambda size, bootstrap: types.SimpleNamespace(size=size, rank=0, handle=1, bootstrap=bootstrap)  # noqa: E731
     for values in ([1.5, -2.0, 1e-300], []):
         both = [values, [-v for v in values]]
         for comm, rows in ((boot, both), (native(2, boot), both), (None, [values]), (types.SimpleNamespace(size=1), [values]), (native(2, None), [values])):
