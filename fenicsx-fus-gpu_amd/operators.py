@@ -24,6 +24,7 @@ there is no CPU fallback.
 
 from __future__ import annotations
 
+import ctypes as C
 import os
 
 import numpy as np
@@ -64,136 +65,11 @@ def use_strip_order(flag: bool):
     _STRIP_ORDER = bool(flag)
 
 
-
 def use_locality_order(flag: bool):
     global _LOCALITY_ORDER
     _LOCALITY_ORDER = bool(flag)
 
 
-class _PlanCache:
-    """Batch-plan workspaces keyed on the identity of the dofmap array (pointer, shape, version).
-    One cache for the whole module: the cell mass operator and the stiffness operator share a
-    plan when they are given the same dofmap."""
-
-    def __init__(self, capacity: int = 16):
-        self._plans = {}
-        self.capacity = capacity
-        self.last_order = None  # cell order of the plan built last (None: natural order)
-        self._recording = None  # while a hipGraph is captured: every (workspace, dofmap) handed out
-
-    def start_recording(self):
-        self._recording = []
-
-    def stop_recording(self):
-        """-> the (workspace, dofmap) tensors handed out since ``start_recording``: whoever baked their addresses
-        into a captured graph holds this list, so eviction from the cache cannot free them."""
-        held, self._recording = self._recording or [], None
-        return held
-
-    def get(self, dofmap: torch.Tensor, exclusive_ndofs=None, external_use=None, strips=False):
-        """-> (workspace tensor, entities_per_batch).  ``strips``: the plan of a kernel bound by its scatter side (in-kernel
-        geometry, affine cells): its cell order interleaves adjacent rows of cells (``plan_tiles.two_row_strip_order``: 2 x 5
-        pieces instead of 10 cells in a row at P = 4, -8 % distinct dofs per batch) when that lowers the number of distinct dofs
-        the batches touch -- a separate cache entry from the row-ordered plan of the same dofmap, which the general-G kernels keep.  ``exclusive_ndofs`` (length of the vectors the plan is applied to):
-        the plan also carries EXCLUSIVE-DOF MARKS (``fus_plan_mark_exclusive``: a dof touched by exactly one batch is finished
-        with a plain load + store instead of a float atomic), a separate cache entry from the unmarked plan of the same
-        dofmap.  ``external_use``: device int32[ndofs], what else adds into each dof while a launch with this plan runs
-        (default: nothing -- the launch runs alone or only next to launches of the same stream)."""
-        lib = _lib.load()
-        nent, N = dofmap.shape
-        strips = bool(strips) and _STRIP_ORDER and exclusive_ndofs is None
-        key = (dofmap.data_ptr(), nent, N, dofmap._version, dofmap.device.index,
-               None if exclusive_ndofs is None else (int(exclusive_ndofs), None if external_use is None else (external_use.data_ptr(), external_use._version)))
-        if strips:
-            key = key + ("strips",)
-        hit = self._plans.get(key)
-        if hit is None:
-            epb = lib.fus_plan_entities_per_batch(N)
-            if epb < 0:
-                _lib.check(epb, "fus_plan_entities_per_batch")
-            nbytes = lib.fus_plan_bytes(N, epb, nent)
-            if nbytes < 0:
-                _lib.check(int(nbytes), "fus_plan_bytes")
-
-            def build(order):
-                w = torch.empty(int(nbytes), dtype=torch.uint8, device=dofmap.device)
-                _lib.check(
-                    lib.fus_plan_build_ordered(dofmap.data_ptr(), order.data_ptr() if order is not None else None, N, epb, nent,
-                                               w.data_ptr(), int(nbytes), _lib.stream_ptr()),
-                    "fus_plan_build_ordered",
-                )
-                return w
-
-            def distinct_dofs(w):  # sum over batches of the distinct dofs a batch touches
-                nbatch = (nent + epb - 1) // epb
-                return int((w[256:256 + 4 * nbatch].view(torch.int32) & 0xFFFF).sum().item())
-
-            ws = build(None)
-            self.last_order = None
-            if _LOCALITY_ORDER and nent > 2 * epb:
-                mins = dofmap.min(dim=1).values
-                if not bool((mins[1:] >= mins[:-1]).all().item()):  # not already in that order
-                    order = torch.argsort(mins, stable=True).to(torch.int32)
-                    ws2 = build(order)
-                    if distinct_dofs(ws2) < 0.97 * distinct_dofs(ws):
-                        ws, ws2, self.last_order = ws2, ws, order
-                    lib.fus_plan_release(ws2.data_ptr())  # the plan that was not kept
-            if strips and nent > 4 * epb:
-                n = int(round(N ** (1.0 / 3.0)))
-                if n >= 3 and n**3 == N:  # cells of degree >= 2 in tensor-product local order
-                    from . import plan_tiles
-
-                    faces = torch.from_numpy(plan_tiles.face_interior_local_dofs(n)).to(dofmap.device)
-                    cand = plan_tiles.two_row_strip_order(dofmap[:, faces].cpu().numpy(),
-                                                          None if self.last_order is None else self.last_order.cpu().numpy())
-                    if cand is not None:
-                        order = torch.from_numpy(cand.astype("int32")).to(dofmap.device)
-                        ws2 = build(order)
-                        if distinct_dofs(ws2) < 0.97 * distinct_dofs(ws):
-                            ws, ws2, self.last_order = ws2, ws, order
-                        lib.fus_plan_release(ws2.data_ptr())
-            if exclusive_ndofs is not None:
-                use = (external_use.to(torch.int32).clone() if external_use is not None
-                       else torch.zeros(int(exclusive_ndofs), dtype=torch.int32, device=dofmap.device))
-                if use.numel() != int(exclusive_ndofs):
-                    raise ValueError("external_use must have one entry per dof")
-                _lib.check(lib.fus_plan_mark_exclusive(ws.data_ptr(), N, epb, nent, use.data_ptr(), int(exclusive_ndofs), _lib.stream_ptr()),
-                           "fus_plan_mark_exclusive")
-                del use  # a temporary: the caching allocator hands its memory out again in stream order
-            if len(self._plans) >= self.capacity:  # bounded: drop the oldest plan
-                old = self._plans.pop(next(iter(self._plans)))
-                lib.fus_plan_release(old[0].data_ptr())
-            # the entry holds the dofmap tensor itself: while a plan is cached its memory cannot be
-            # freed and handed to another array with the same address / shape / version
-            hit = (ws, epb, dofmap)
-            self._plans[key] = hit
-        if self._recording is not None:
-            self._recording.append((hit[0], hit[2]))
-        return hit[0], hit[1]
-
-    def has(self, dofmap: torch.Tensor) -> bool:
-        """True if an (unmarked) plan of ``dofmap`` is cached -- row-ordered or strip-ordered: an operator uses one of the two
-        consistently, and ``HaloApply`` asks only for a cell range the operator has been applied to before -- so an apply with
-        it does no set-up work (no allocation, no host synchronisation): what ``HaloApply`` needs to know before it lets a
-        launch carry a fork signal."""
-        nent, N = dofmap.shape
-        key = (dofmap.data_ptr(), nent, N, dofmap._version, dofmap.device.index, None)
-        return key in self._plans or key + ("strips",) in self._plans
-
-    def clear(self):
-        lib = _lib.load()
-        for ws, _, _ in self._plans.values():
-            lib.fus_plan_release(ws.data_ptr())
-        self._plans.clear()
-        gather = globals().get("_GATHER_PLANS")  # the transposed-dofmap plans of the mass apply go with them
-        if gather is not None:
-            gather.clear()
-        static = globals().get("_STATIC_DETJ")
-        if static is not None:
-            static.clear()
-
-
-_PLANS = _PlanCache()
 _MASS_PLAN_MIN_ENTRIES = 1 << 15  # below this the plan-free kernel is already launch-bound
 
 # The mass apply WITHOUT atomics (csrc/mass_gather.hpp): one thread per touched dof sums its (entity, local index) entries
@@ -213,21 +89,91 @@ def use_mass_gather(flag: bool):
     _USE_GATHER = bool(flag)
 
 
-class _GatherPlanCache:
+# ------------------------------------------------------------------------- caches
+class _Cache:
+    """What the three workspace caches below share.  A key names the identity of an array (pointer, shape, torch version counter);
+    an entry is a tuple ``(workspace, that array, ...)`` -- it holds the array itself: while the entry is cached the array's memory
+    cannot be freed and handed to another one with the same address / shape / version -- or ``None`` when the library refused to
+    build one.  Bounded: a full cache drops (and releases) its oldest entry.  ``dependants``: the caches whose entries are built
+    on this one's; they are cleared with it.  A subclass supplies the key and ``_build``."""
+
+    _held = None  # while a hipGraph is captured: every (workspace, keyed array) any of the caches handed out
+
+    def __init__(self, capacity, *dependants):
+        self._entries, self.capacity, self._dependants = {}, capacity, dependants
+
+    @staticmethod
+    def start_recording():
+        _Cache._held = []
+
+    @staticmethod
+    def stop_recording():
+        """-> the (workspace, keyed array) tensors handed out since ``start_recording``: whoever baked their addresses
+        into a captured graph holds this list, so eviction from a cache cannot free them."""
+        held, _Cache._held = _Cache._held or [], None
+        return held
+
+    def _lookup(self, key, *build_args):
+        hit = self._entries.get(key, self)  # (self: no entry -- None is one)
+        if hit is self:
+            hit = self._build(*build_args)
+            if len(self._entries) >= self.capacity:
+                self._release(self._entries.pop(next(iter(self._entries))))
+            self._entries[key] = hit
+        return hit
+
+    @staticmethod
+    def _hand_out(hit):
+        if hit is not None and _Cache._held is not None:
+            _Cache._held.append(hit[:2])
+        return hit
+
+    @staticmethod
+    def _release(hit):
+        if hit is not None:
+            _lib.load().fus_plan_release(hit[0].data_ptr())
+
+    def clear(self):
+        for cache in self._dependants:
+            cache.clear()
+        for hit in self._entries.values():
+            self._release(hit)
+        self._entries.clear()
+
+
+class _StaticDetJCache(_Cache):
+    """Static companions of transposed-dofmap plans (``fus_mass_gather_static_*``): detJ in row order, keyed on the plan's
+    workspace and on the identity of the detJ array.  An entry is ``None`` when the library refused (a block of 256 dofs
+    spanning more than 65 535 entities)."""
+
+    def get(self, plan_ws, detJ, n_per, nent):
+        key = (plan_ws.data_ptr(), detJ.data_ptr(), tuple(detJ.shape), detJ._version, detJ.dtype)
+        return self._hand_out(self._lookup(key, plan_ws, detJ, n_per, nent))
+
+    def _build(self, plan_ws, detJ, n_per, nent):
+        lib = _lib.load()
+        nbytes = lib.fus_mass_gather_static_bytes(int(n_per), int(nent), detJ.element_size())
+        if nbytes <= 0:
+            return None
+        sws = torch.empty(int(nbytes), dtype=torch.uint8, device=detJ.device)
+        fn = getattr(lib, f"fus_mass_gather_static_build_{_lib.suffix(detJ.dtype)}")
+        rc = fn(plan_ws.data_ptr(), detJ.data_ptr(), sws.data_ptr(), int(nbytes), _lib.stream_ptr())
+        if rc == _lib.ERR_UNSUPPORTED_ENTITY:
+            return None
+        _lib.check(rc, "fus_mass_gather_static_build")
+        return sws, detJ, plan_ws  # holds the plan too: its address cannot be re-used while this lives
+
+
+class _GatherPlanCache(_Cache):
     """Transposed-dofmap plans of the atomic-free mass apply, keyed like the batch plans (identity of the dofmap array) plus
     the length of the dof vectors.  An entry is ``None`` when the library refused the dofmap (a dof with more than 255
-    entries) or the gather would lose (``_GATHER_MAX_MEAN_ENTRIES``): the caller then takes the atomic path."""
-
-    def __init__(self, capacity: int = 16):
-        self._plans = {}
-        self._static_only = set()  # keys of plans kept for the static-detJ form alone (the plain gather would lose: P = 2)
-        self.capacity = capacity
+    entries) or the gather would lose (``_GATHER_STATIC_MAX_MEAN_ENTRIES``): the caller then takes the atomic path.  Otherwise it is
+    ``(workspace, dofmap, the four info integers, kept for the static-detJ form alone, row_set or None)``."""
 
     def get(self, dofmap: torch.Tensor, ndofs: int, rows=None, static=False):
         """``rows = (row_set, which)``: the plan of the dofs d with ``row_set[d] == which`` only (device uint8[ndofs]; the
         partitioned apply's split into rows next to the exchanges and rows between them).  ``static``: the caller will apply the
         static-detJ form, which pays up to a higher mean number of entries per dof than the plain gather."""
-        lib = _lib.load()
         nent, N = dofmap.shape
         key = (dofmap.data_ptr(), nent, N, dofmap._version, dofmap.device.index, int(ndofs))
         if rows is not None:
@@ -236,58 +182,136 @@ class _GatherPlanCache:
             if row_set.numel() != int(ndofs):
                 raise ValueError("row_set must have one mark per dof")
             key = key + (row_set.data_ptr(), row_set._version, int(which))
-        if key in self._plans:
-            hit = self._plans[key]
-        else:
-            import ctypes as C
+        hit = self._lookup(key, dofmap, int(ndofs), rows)
+        if hit is None or (hit[3] and not static):
+            return None  # (the plain gather would lose on this dofmap: the caller takes the atomic batch plan)
+        return self._hand_out(hit)
 
-            hit = None
-            nbytes = lib.fus_mass_gather_plan_bytes(N, nent, int(ndofs))
-            if nbytes > 0:
-                ws = torch.empty(int(nbytes), dtype=torch.uint8, device=dofmap.device)
-                if rows is None:
-                    rc = lib.fus_mass_gather_plan_build(dofmap.data_ptr(), N, nent, int(ndofs), ws.data_ptr(), int(nbytes), _lib.stream_ptr())
-                else:
-                    rc = lib.fus_mass_gather_plan_build_rows(dofmap.data_ptr(), N, nent, int(ndofs), rows[0].data_ptr(), int(rows[1]),
-                                                             ws.data_ptr(), int(nbytes), _lib.stream_ptr())
-                if rc == 0:
-                    info = (C.c_int64 * 4)()
-                    _lib.check(lib.fus_mass_gather_plan_info(ws.data_ptr(), info), "fus_mass_gather_plan_info")
-                    # (a row subset is judged by the full plan: the caller asks for it only when the full plan was kept)
-                    if rows is not None or (info[0] > 0 and nent * N <= _GATHER_STATIC_MAX_MEAN_ENTRIES * info[0]):
-                        hit = (ws, dofmap, tuple(int(v) for v in info)) + ((rows[0],) if rows is not None else ())
-                        if rows is None and nent * N > _GATHER_MAX_MEAN_ENTRIES * info[0]:
-                            self._static_only.add(key)
-                    else:
-                        lib.fus_plan_release(ws.data_ptr())
-                elif rc != _lib.ERR_UNSUPPORTED_ENTITY:
-                    _lib.check(rc, "fus_mass_gather_plan_build")
-            if len(self._plans) >= self.capacity:
-                oldest = next(iter(self._plans))
-                old = self._plans.pop(oldest)
-                self._static_only.discard(oldest)
-                if old is not None:
-                    lib.fus_plan_release(old[0].data_ptr())
-            self._plans[key] = hit
-        if hit is not None and not static and key in self._static_only:
-            return None  # the plain gather would lose on this dofmap: the caller takes the atomic batch plan
-        if hit is not None and _PLANS._recording is not None:
-            _PLANS._recording.append((hit[0], hit[1]))  # a captured graph keeps the workspace alive
-        return hit
-
-    def clear(self):
+    def _build(self, dofmap, ndofs, rows):
         lib = _lib.load()
-        static = globals().get("_STATIC_DETJ")  # row-ordered detJ copies belong to these plans
-        if static is not None:
-            static.clear()
-        for hit in self._plans.values():
-            if hit is not None:
-                lib.fus_plan_release(hit[0].data_ptr())
-        self._plans.clear()
-        self._static_only.clear()
+        nent, N = dofmap.shape
+        nbytes = lib.fus_mass_gather_plan_bytes(N, nent, ndofs)
+        if nbytes <= 0:
+            return None
+        ws = torch.empty(int(nbytes), dtype=torch.uint8, device=dofmap.device)
+        if rows is None:
+            rc = lib.fus_mass_gather_plan_build(dofmap.data_ptr(), N, nent, ndofs, ws.data_ptr(), int(nbytes), _lib.stream_ptr())
+        else:
+            rc = lib.fus_mass_gather_plan_build_rows(dofmap.data_ptr(), N, nent, ndofs, rows[0].data_ptr(), int(rows[1]),
+                                                     ws.data_ptr(), int(nbytes), _lib.stream_ptr())
+        if rc == _lib.ERR_UNSUPPORTED_ENTITY:
+            return None
+        _lib.check(rc, "fus_mass_gather_plan_build")
+        info = (C.c_int64 * 4)()
+        _lib.check(lib.fus_mass_gather_plan_info(ws.data_ptr(), info), "fus_mass_gather_plan_info")
+        if rows is not None:  # (a row subset is judged by the full plan: the caller asks for it only when the full plan was kept)
+            return ws, dofmap, tuple(int(v) for v in info), False, rows[0]
+        if not (info[0] > 0 and nent * N <= _GATHER_STATIC_MAX_MEAN_ENTRIES * info[0]):
+            lib.fus_plan_release(ws.data_ptr())
+            return None
+        return ws, dofmap, tuple(int(v) for v in info), nent * N > _GATHER_MAX_MEAN_ENTRIES * info[0], None
 
 
-_GATHER_PLANS = _GatherPlanCache()
+class _PlanCache(_Cache):
+    """Batch-plan workspaces keyed on the identity of the dofmap array (pointer, shape, version).
+    One cache for the whole module: the cell mass operator and the stiffness operator share a
+    plan when they are given the same dofmap.  An entry is ``(workspace, dofmap, entities per batch)``."""
+
+    def __init__(self, capacity, *dependants):
+        super().__init__(capacity, *dependants)
+        self._plans = self._entries
+        self.last_order = None  # cell order of the plan built last (None: natural order)
+
+    def get(self, dofmap: torch.Tensor, exclusive_ndofs=None, external_use=None, strips=False):
+        """-> (workspace tensor, entities_per_batch).  ``strips``: the plan of a kernel bound by its scatter side (in-kernel
+        geometry, affine cells): its cell order interleaves adjacent rows of cells (``plan_tiles.two_row_strip_order``: 2 x 5
+        pieces instead of 10 cells in a row at P = 4, -8 % distinct dofs per batch) when that lowers the number of distinct dofs
+        the batches touch -- a separate cache entry from the row-ordered plan of the same dofmap, which the general-G kernels keep.  ``exclusive_ndofs`` (length of the vectors the plan is applied to):
+        the plan also carries EXCLUSIVE-DOF MARKS (``fus_plan_mark_exclusive``: a dof touched by exactly one batch is finished
+        with a plain load + store instead of a float atomic), a separate cache entry from the unmarked plan of the same
+        dofmap.  ``external_use``: device int32[ndofs], what else adds into each dof while a launch with this plan runs
+        (default: nothing -- the launch runs alone or only next to launches of the same stream)."""
+        nent, N = dofmap.shape
+        strips = bool(strips) and _STRIP_ORDER and exclusive_ndofs is None
+        key = (dofmap.data_ptr(), nent, N, dofmap._version, dofmap.device.index,
+               None if exclusive_ndofs is None else (int(exclusive_ndofs), None if external_use is None else (external_use.data_ptr(), external_use._version)))
+        if strips:
+            key = key + ("strips",)
+        ws, _, epb = self._hand_out(self._lookup(key, dofmap, exclusive_ndofs, external_use, strips))
+        return ws, epb
+
+    def _build(self, dofmap, exclusive_ndofs, external_use, strips):
+        lib = _lib.load()
+        nent, N = dofmap.shape
+        epb = lib.fus_plan_entities_per_batch(N)
+        if epb < 0:
+            _lib.check(epb, "fus_plan_entities_per_batch")
+        nbytes = lib.fus_plan_bytes(N, epb, nent)
+        if nbytes < 0:
+            _lib.check(int(nbytes), "fus_plan_bytes")
+
+        def build(order):
+            w = torch.empty(int(nbytes), dtype=torch.uint8, device=dofmap.device)
+            _lib.check(
+                lib.fus_plan_build_ordered(dofmap.data_ptr(), order.data_ptr() if order is not None else None, N, epb, nent,
+                                           w.data_ptr(), int(nbytes), _lib.stream_ptr()),
+                "fus_plan_build_ordered",
+            )
+            return w
+
+        def distinct_dofs(w):  # sum over batches of the distinct dofs a batch touches
+            nbatch = (nent + epb - 1) // epb
+            return int((w[256:256 + 4 * nbatch].view(torch.int32) & 0xFFFF).sum().item())
+
+        ws = build(None)
+        self.last_order = None
+        if _LOCALITY_ORDER and nent > 2 * epb:
+            mins = dofmap.min(dim=1).values
+            if not bool((mins[1:] >= mins[:-1]).all().item()):  # not already in that order
+                order = torch.argsort(mins, stable=True).to(torch.int32)
+                ws2 = build(order)
+                if distinct_dofs(ws2) < 0.97 * distinct_dofs(ws):
+                    ws, ws2, self.last_order = ws2, ws, order
+                lib.fus_plan_release(ws2.data_ptr())  # the plan that was not kept
+        if strips and nent > 4 * epb:
+            n = int(round(N ** (1.0 / 3.0)))
+            if n >= 3 and n**3 == N:  # cells of degree >= 2 in tensor-product local order
+                from . import plan_tiles
+
+                faces = torch.from_numpy(plan_tiles.face_interior_local_dofs(n)).to(dofmap.device)
+                cand = plan_tiles.two_row_strip_order(dofmap[:, faces].cpu().numpy(),
+                                                      None if self.last_order is None else self.last_order.cpu().numpy())
+                if cand is not None:
+                    order = torch.from_numpy(cand.astype("int32")).to(dofmap.device)
+                    ws2 = build(order)
+                    if distinct_dofs(ws2) < 0.97 * distinct_dofs(ws):
+                        ws, ws2, self.last_order = ws2, ws, order
+                    lib.fus_plan_release(ws2.data_ptr())
+        if exclusive_ndofs is not None:
+            use = (external_use.to(torch.int32).clone() if external_use is not None
+                   else torch.zeros(int(exclusive_ndofs), dtype=torch.int32, device=dofmap.device))
+            if use.numel() != int(exclusive_ndofs):
+                raise ValueError("external_use must have one entry per dof")
+            _lib.check(lib.fus_plan_mark_exclusive(ws.data_ptr(), N, epb, nent, use.data_ptr(), int(exclusive_ndofs), _lib.stream_ptr()),
+                       "fus_plan_mark_exclusive")
+            del use  # a temporary: the caching allocator hands its memory out again in stream order
+        return ws, dofmap, epb
+
+    def has(self, dofmap: torch.Tensor) -> bool:
+        """True if an (unmarked) plan of ``dofmap`` is cached -- row-ordered or strip-ordered: an operator uses one of the two
+        consistently, and ``HaloApply`` asks only for a cell range the operator has been applied to before -- so an apply with
+        it does no set-up work (no allocation, no host synchronisation): what ``HaloApply`` needs to know before it lets a
+        launch carry a fork signal."""
+        nent, N = dofmap.shape
+        key = (dofmap.data_ptr(), nent, N, dofmap._version, dofmap.device.index, None)
+        return key in self._entries or key + ("strips",) in self._entries
+
+
+# a clear takes what was built on the cleared entries with it: the transposed-dofmap plans of the mass apply go with the batch
+# plans, the row-ordered detJ copies with the transposed plans
+_STATIC_DETJ = _StaticDetJCache(8)
+_GATHER_PLANS = _GatherPlanCache(16, _STATIC_DETJ)
+_PLANS = _PlanCache(16, _GATHER_PLANS)
 
 
 class _Launchable:
@@ -302,6 +326,37 @@ def _mass_gather_usable(nent, n_per):
     return _USE_GATHER and nent * n_per >= _MASS_PLAN_MIN_ENTRIES and n_per <= 2048 and nent * n_per < 2**31
 
 
+def _mass_route(entity_dofmap, ndofs, atomic=False, static=False, entity_detJ=None):
+    """Which kernel a mass apply takes, decided here alone: -> (route, workspaces) with the route one of ``_MASS_KERNELS`` (it
+    completes the entry's name, ``fus_mass_apply_<route><type>``) and the workspace tensors that kernel reads in place of the dofmap
+    (the batch plan is asked of ``_PLANS`` by the apply: it depends on the operator's exclusive-dof marks).  ``static``: an
+    operator made with ``static_detJ=True``; without ``entity_detJ`` it is judged by the transposed plan alone."""
+    nent, n_per = entity_dofmap.shape
+    if not atomic and _mass_gather_usable(nent, n_per):
+        plan = _GATHER_PLANS.get(entity_dofmap, ndofs, static=static)  # every dofmap value is checked against ndofs
+        if plan is not None and static and entity_detJ is not None:
+            companion = _STATIC_DETJ.get(plan[0], entity_detJ, n_per, nent)
+            if companion is not None:
+                return "gather_static_", (plan[0], companion[0])
+            if plan[3]:  # no companion, and the plain gather would lose: the default path is the batch plan
+                plan = None
+        if plan is not None:
+            return "gather_", (plan[0],)
+    if _USE_PLAN and 2 <= n_per <= 4096 and nent * n_per >= _MASS_PLAN_MIN_ENTRIES:  # plan batches hold <= 4096 entries
+        return "planned_", ()
+    return "", ()
+
+
+_MASS_KERNELS = {"gather_static_": "fus::mass_gather_kernel", "gather_": "fus::mass_gather_kernel", "planned_": "fus::mass_plan_kernel",
+                 "": "fus::mass_kernel"}
+
+
+def mass_kernel_name(entity_dofmap, ndofs, atomic=False, static=False):
+    """Which kernel ``mass_operator``'s apply launches for this dofmap and vector length (bench.py reports it); ``static``: of an operator made
+    with ``static_detJ=True`` (it keeps the gather kernel up to more entries per dof: P = 2)."""
+    return _MASS_KERNELS[_mass_route(entity_dofmap, int(ndofs), atomic, bool(static))[0]]
+
+
 def mass_rows_available(entity_dofmap, ndofs, row_set):
     """True if ``mass_operator``'s apply can run as two row-subset launches of the atomic-free kernel for this dofmap (the
     full transposed plan is one the operator would use, and both subsets build): what ``HaloApply`` asks before it splits a
@@ -314,35 +369,11 @@ def mass_rows_available(entity_dofmap, ndofs, row_set):
     return all(_GATHER_PLANS.get(entity_dofmap, int(ndofs), (row_set, w)) is not None for w in (0, 1))
 
 
-def _mass_apply_rows(x, entity_constants, y, entity_detJ, entity_dofmap, row_set, which, N=None):
-    """The rows ``row_set[d] == which`` of ``y += M(c) x`` with the atomic-free kernel (every row sums all its entries)."""
-    lib = _lib.load()
+def _mass_check(x, entity_constants, y, entity_detJ, entity_dofmap, N):
+    """The argument check of every mass apply -> (dtype, number of entities, dofs per entity)."""
     dt = x.dtype if isinstance(x, torch.Tensor) else None
     for name, t in (("x", x), ("entity_constants", entity_constants), ("y", y), ("entity_detJ", entity_detJ)):
         _req(t, dt, name)
-    _req(entity_dofmap, torch.int32, "entity_dofmap")
-    if entity_dofmap.dim() != 2 or entity_detJ.shape != entity_dofmap.shape:
-        raise ValueError("entity_dofmap must be [num_entities, N] and entity_detJ must have the same shape")
-    nent, n_per = entity_dofmap.shape
-    if (N is not None and n_per != N) or entity_constants.numel() != nent:
-        raise ValueError("dofs per entity / number of constants do not match the dofmap")
-    if nent == 0:
-        return
-    hit = _GATHER_PLANS.get(entity_dofmap, min(x.numel(), y.numel()), (row_set, int(which)))
-    if hit is None:
-        raise _lib.FusGpuError("no row-subset plan for this dofmap (mass_rows_available() says when there is one)")
-    fn = getattr(lib, f"fus_mass_apply_gather_{_lib.suffix(dt)}")
-    _lib.check(fn(x.data_ptr(), entity_constants.data_ptr(), y.data_ptr(), entity_detJ.data_ptr(), hit[0].data_ptr(), int(n_per), int(nent),
-                  _lib.stream_ptr()), "fus_mass_apply_gather (row subset)")
-
-
-def _mass_apply(x, entity_constants, y, entity_detJ, entity_dofmap, N=None, exclusive=False, atomic=False):
-    lib = _lib.load()
-    dt = x.dtype if isinstance(x, torch.Tensor) else None
-    _req(x, dt, "x")
-    _req(entity_constants, dt, "entity_constants")
-    _req(y, dt, "y")
-    _req(entity_detJ, dt, "entity_detJ")
     _req(entity_dofmap, torch.int32, "entity_dofmap")
     if entity_dofmap.dim() != 2 or entity_detJ.shape != entity_dofmap.shape:
         raise ValueError("entity_dofmap must be [num_entities, N] and entity_detJ must have the same shape")
@@ -351,88 +382,37 @@ def _mass_apply(x, entity_constants, y, entity_detJ, entity_dofmap, N=None, excl
         raise ValueError(f"operator was built for N={N} dofs per entity, dofmap has {n_per}")
     if entity_constants.numel() != nent:
         raise ValueError("entity_constants must have one value per entity")
+    return dt, nent, n_per
+
+
+def _mass_apply_rows(x, entity_constants, y, entity_detJ, entity_dofmap, row_set, which, N=None):
+    """The rows ``row_set[d] == which`` of ``y += M(c) x`` with the atomic-free kernel (every row sums all its entries)."""
+    dt, nent, n_per = _mass_check(x, entity_constants, y, entity_detJ, entity_dofmap, N)
     if nent == 0:
         return
-    if not atomic and _mass_gather_usable(nent, n_per):
-        hit = _GATHER_PLANS.get(entity_dofmap, min(x.numel(), y.numel()))  # every dofmap value is checked against both vectors
-        if hit is not None:
-            fn = getattr(lib, f"fus_mass_apply_gather_{_lib.suffix(dt)}")
-            _lib.check(
-                fn(x.data_ptr(), entity_constants.data_ptr(), y.data_ptr(), entity_detJ.data_ptr(), hit[0].data_ptr(),
-                   int(n_per), int(nent), _lib.stream_ptr()),
-                "fus_mass_apply_gather",
-            )
-            return
-    if _USE_PLAN and 2 <= n_per <= 4096 and nent * n_per >= _MASS_PLAN_MIN_ENTRIES:  # plan batches hold <= 4096 entries
-        ws, epb = _PLANS.get(entity_dofmap, exclusive_ndofs=y.numel() if exclusive else None)
-        fn = getattr(lib, f"fus_mass_apply_planned_{_lib.suffix(dt)}")
-        _lib.check(
-            fn(x.data_ptr(), entity_constants.data_ptr(), y.data_ptr(), entity_detJ.data_ptr(), ws.data_ptr(),
-               int(n_per), int(epb), int(nent), _lib.stream_ptr()),
-            "fus_mass_apply_planned",
-        )
+    hit = _GATHER_PLANS.get(entity_dofmap, min(x.numel(), y.numel()), (row_set, int(which)))
+    if hit is None:
+        raise _lib.FusGpuError("no row-subset plan for this dofmap (mass_rows_available() says when there is one)")
+    fn = getattr(_lib.load(), f"fus_mass_apply_gather_{_lib.suffix(dt)}")
+    _lib.check(fn(x.data_ptr(), entity_constants.data_ptr(), y.data_ptr(), entity_detJ.data_ptr(), hit[0].data_ptr(), int(n_per), int(nent),
+                  _lib.stream_ptr()), "fus_mass_apply_gather (row subset)")
+
+
+def _mass_apply(x, entity_constants, y, entity_detJ, entity_dofmap, N=None, exclusive=False, atomic=False, static=False):
+    dt, nent, n_per = _mass_check(x, entity_constants, y, entity_detJ, entity_dofmap, N)
+    if nent == 0:
         return
-    fn = getattr(lib, f"fus_mass_apply_{_lib.suffix(dt)}")
-    _lib.check(
-        fn(x.data_ptr(), entity_constants.data_ptr(), y.data_ptr(), entity_detJ.data_ptr(), entity_dofmap.data_ptr(),
-           int(n_per), int(nent), _lib.stream_ptr()),
-        "fus_mass_apply",
-    )
-
-
-def mass_kernel_name(entity_dofmap, ndofs, atomic=False, static=False):
-    """Which kernel ``mass_operator``'s apply launches for this dofmap and vector length (bench.py reports it); ``static``: of an operator made
-    with ``static_detJ=True`` (it keeps the gather kernel up to more entries per dof: P = 2)."""
-    nent, n_per = entity_dofmap.shape
-    big = nent * n_per >= _MASS_PLAN_MIN_ENTRIES
-    if (_USE_GATHER and not atomic and big and n_per <= 2048 and nent * n_per < 2**31
-            and _GATHER_PLANS.get(entity_dofmap, int(ndofs), static=bool(static)) is not None):
-        return "fus::mass_gather_kernel"
-    return "fus::mass_plan_kernel" if (_USE_PLAN and 2 <= n_per <= 4096 and big) else "fus::mass_kernel"
-
-
-class _StaticDetJCache:
-    """Static companions of transposed-dofmap plans (``fus_mass_gather_static_*``): detJ in row order, keyed on the plan's
-    workspace and on the identity of the detJ array (pointer, shape, torch version counter).  An entry is ``None`` when the library
-    refused (a block of 256 dofs spanning more than 65 535 entities)."""
-
-    def __init__(self, capacity: int = 8):
-        self._entries = {}
-        self.capacity = capacity
-
-    def get(self, plan_ws, detJ, n_per, nent):
-        lib = _lib.load()
-        key = (plan_ws.data_ptr(), detJ.data_ptr(), tuple(detJ.shape), detJ._version, detJ.dtype)
-        if key not in self._entries:
-            hit = None
-            nbytes = lib.fus_mass_gather_static_bytes(int(n_per), int(nent), detJ.element_size())
-            if nbytes > 0:
-                sws = torch.empty(int(nbytes), dtype=torch.uint8, device=detJ.device)
-                fn = getattr(lib, f"fus_mass_gather_static_build_{_lib.suffix(detJ.dtype)}")
-                rc = fn(plan_ws.data_ptr(), detJ.data_ptr(), sws.data_ptr(), int(nbytes), _lib.stream_ptr())
-                if rc == 0:
-                    hit = (sws, plan_ws, detJ)  # holds the plan and detJ: their addresses cannot be re-used while this lives
-                elif rc != _lib.ERR_UNSUPPORTED_ENTITY:
-                    _lib.check(rc, "fus_mass_gather_static_build")
-            if len(self._entries) >= self.capacity:
-                old = self._entries.pop(next(iter(self._entries)))
-                if old is not None:
-                    lib.fus_plan_release(old[0].data_ptr())
-            self._entries[key] = hit
-        hit = self._entries[key]
-        if hit is not None and _PLANS._recording is not None:
-            _PLANS._recording.append((hit[0], hit[2]))
-        return hit
-
-    def clear(self):
-        lib = _lib.load()
-        for hit in self._entries.values():
-            if hit is not None:
-                lib.fus_plan_release(hit[0].data_ptr())
-        self._entries.clear()
-
-
-_STATIC_DETJ = _StaticDetJCache()
+    route, ws = _mass_route(entity_dofmap, min(x.numel(), y.numel()), atomic, static, entity_detJ)
+    fn = getattr(_lib.load(), f"fus_mass_apply_{route}{_lib.suffix(dt)}")
+    head = (x.data_ptr(), entity_constants.data_ptr(), y.data_ptr())
+    if route == "gather_static_":  # detJ comes in row order from the companion
+        rc = fn(*head, ws[0].data_ptr(), ws[1].data_ptr(), int(n_per), int(nent), _lib.stream_ptr())
+    elif route == "planned_":
+        plan, epb = _PLANS.get(entity_dofmap, exclusive_ndofs=y.numel() if exclusive else None)
+        rc = fn(*head, entity_detJ.data_ptr(), plan.data_ptr(), int(n_per), int(epb), int(nent), _lib.stream_ptr())
+    else:  # the transposed plan, or the dofmap itself
+        rc = fn(*head, entity_detJ.data_ptr(), (ws[0] if ws else entity_dofmap).data_ptr(), int(n_per), int(nent), _lib.stream_ptr())
+    _lib.check(rc, "fus_mass_apply_" + route + "*")
 
 
 class _MassApply:
@@ -444,36 +424,11 @@ class _MassApply:
         self.atomic = self if atomic else _MassApply(N, tdt, exclusive, True)
 
     def __call__(self, x, entity_constants, y, entity_detJ, entity_dofmap):
+        """``static_detJ=True``: the apply with detJ streamed in row order when this dofmap has a transposed plan and a static
+        companion, the default path otherwise (same result)."""
         if isinstance(x, torch.Tensor) and x.dtype != self.dtype:
             raise TypeError(f"x: expected dtype {self.dtype}, got {x.dtype}")
-        if self._static and self._apply_static(x, entity_constants, y, entity_detJ, entity_dofmap):
-            return
-        _mass_apply(x, entity_constants, y, entity_detJ, entity_dofmap, self.N, exclusive=self._exclusive, atomic=self._atomic)
-
-    def _apply_static(self, x, entity_constants, y, entity_detJ, entity_dofmap):
-        """The apply with detJ streamed in row order (``static_detJ=True``); False when this dofmap has no transposed plan or no
-        static companion (the caller then takes the default path: same result)."""
-        dt = self.dtype
-        for name, t in (("x", x), ("entity_constants", entity_constants), ("y", y), ("entity_detJ", entity_detJ)):
-            _req(t, dt, name)
-        _req(entity_dofmap, torch.int32, "entity_dofmap")
-        if entity_dofmap.dim() != 2 or entity_detJ.shape != entity_dofmap.shape:
-            raise ValueError("entity_dofmap must be [num_entities, N] and entity_detJ must have the same shape")
-        nent, n_per = entity_dofmap.shape
-        if n_per != self.N or entity_constants.numel() != nent:
-            raise ValueError("dofs per entity / number of constants do not match the dofmap")
-        if nent == 0 or not _mass_gather_usable(nent, n_per):
-            return False
-        plan = _GATHER_PLANS.get(entity_dofmap, min(x.numel(), y.numel()), static=True)
-        if plan is None:
-            return False
-        st = _STATIC_DETJ.get(plan[0], entity_detJ, n_per, nent)
-        if st is None:
-            return False
-        fn = getattr(_lib.load(), f"fus_mass_apply_gather_static_{_lib.suffix(dt)}")
-        _lib.check(fn(x.data_ptr(), entity_constants.data_ptr(), y.data_ptr(), plan[0].data_ptr(), st[0].data_ptr(), int(n_per), int(nent),
-                      _lib.stream_ptr()), "fus_mass_apply_gather_static")
-        return True
+        _mass_apply(x, entity_constants, y, entity_detJ, entity_dofmap, self.N, self._exclusive, self._atomic, self._static)
 
     def refresh(self):
         """``static_detJ=True``: forget the row-ordered copies of detJ.  REQUIRED after changing a detJ array in place through
@@ -565,6 +520,28 @@ def diagonal_mass_operator(entity_constants, entity_detJ, entity_dofmap, ndofs, 
     return DiagonalMassOperator(entity_constants, entity_detJ, entity_dofmap, ndofs, float_type)
 
 
+def _ptrs(n, *tensors):
+    """The pointer arguments of a facet set: null for an empty set (``n == 0``) and for a tensor that is not given."""
+    return [t.data_ptr() if (n and t is not None) else None for t in tensors]
+
+
+def _facet_field(dt, field, n_source):
+    """Set B of the facet entry points, ``field = (x, c, detJ_f, facet_dofmap)`` or None, checked: -> (its four pointer
+    arguments, its number of facets, the dofs per facet).  ``n_source``: the dofs per facet of a non-empty set A, else None."""
+    if field is None:
+        return [None] * 4, 0, n_source
+    xB, cB, dB, dmB = field
+    for name, t in (("x", xB), ("c", cB), ("detJ_field", dB)):
+        _req(t, dt, name)
+    _req(dmB, torch.int32, "field dofmap")
+    nB = dmB.shape[0]
+    if nB and (dB.shape != dmB.shape or cB.numel() != nB):
+        raise ValueError("facet arrays: detJ must have the dofmap's shape, one constant per facet")
+    if nB and n_source is not None and dmB.shape[1] != n_source:
+        raise ValueError("both facet sets must have the same number of dofs per facet")
+    return _ptrs(nB, *field), nB, (dmB.shape[1] if nB else 1) if n_source is None else n_source
+
+
 def facet_terms(y, source, field, scalars=None):
     """The boundary-facet terms of one RK4 stage in one launch (csrc/mass.hpp, ``fus_facet_terms_*``):
 
@@ -578,44 +555,29 @@ def facet_terms(y, source, field, scalars=None):
     i.e. ``mass_operator(g, facet_coeff1, b, ...)`` [+ the dg term] and ``mass_operator(v_n, facet_coeff2, b, ...)``
     of cuda/demo_linear_box.py:546-549 / cuda/demo_nonlinear_bowl.py:633-641 without filling g into a vector."""
     c1, s1, c2, s2, dA, dmA = source
-    xB, cB, dB, dmB = field
     dt = y.dtype if isinstance(y, torch.Tensor) else None
     _req(y, dt, "y")
-    for name, t in (("c1", c1), ("detJ_source", dA), ("x", xB), ("c", cB), ("detJ_field", dB)):
+    for name, t in (("c1", c1), ("detJ_source", dA)) + (() if c2 is None else (("c2", c2),)):
         _req(t, dt, name)
-    if c2 is not None:
-        _req(c2, dt, "c2")
     _req(dmA, torch.int32, "source dofmap")
-    _req(dmB, torch.int32, "field dofmap")
-    nA, nB = dmA.shape[0], dmB.shape[0]
-    N = dmA.shape[1] if nA else (dmB.shape[1] if nB else 1)
-    if (nA and (dA.shape != dmA.shape or c1.numel() != nA)) or (nB and (dB.shape != dmB.shape or cB.numel() != nB)):
+    nA = dmA.shape[0]
+    if nA and (dA.shape != dmA.shape or c1.numel() != nA):
         raise ValueError("facet arrays: detJ must have the dofmap's shape, one constant per facet")
-    if nA and nB and dmA.shape[1] != dmB.shape[1]:
-        raise ValueError("both facet sets must have the same number of dofs per facet")
+    pB, nB, N = _facet_field(dt, field, dmA.shape[1] if nA else None)
     if nA + nB == 0:
         return
+    pc1, pc2, pdA, pdmA = _ptrs(nA, c1, c2, dA, dmA)
     if scalars is not None:
         _req(scalars, dt, "scalars")
         if scalars.numel() < 2:
             raise ValueError("scalars must hold (s1, s2)")
         fn = getattr(_lib.load(), f"fus_facet_terms_dev_{_lib.suffix(dt)}")
-        _lib.check(
-            fn(y.data_ptr(), c1.data_ptr() if nA else None, c2.data_ptr() if (nA and c2 is not None) else None, scalars.data_ptr(),
-               dA.data_ptr() if nA else None, dmA.data_ptr() if nA else None, int(nA), xB.data_ptr() if nB else None,
-               cB.data_ptr() if nB else None, dB.data_ptr() if nB else None, dmB.data_ptr() if nB else None, int(nB), int(N),
-               _lib.stream_ptr()),
-            "fus_facet_terms_dev",
-        )
+        _lib.check(fn(y.data_ptr(), pc1, pc2, scalars.data_ptr(), pdA, pdmA, int(nA), *pB, int(nB), int(N), _lib.stream_ptr()),
+                   "fus_facet_terms_dev")
         return
     fn = getattr(_lib.load(), f"fus_facet_terms_{_lib.suffix(dt)}")
-    _lib.check(
-        fn(y.data_ptr(), c1.data_ptr() if nA else None, float(s1), c2.data_ptr() if (nA and c2 is not None) else None, float(s2),
-           dA.data_ptr() if nA else None, dmA.data_ptr() if nA else None, int(nA), xB.data_ptr() if nB else None,
-           cB.data_ptr() if nB else None, dB.data_ptr() if nB else None, dmB.data_ptr() if nB else None, int(nB), int(N),
-           _lib.stream_ptr()),
-        "fus_facet_terms",
-    )
+    _lib.check(fn(y.data_ptr(), pc1, float(s1), pc2, float(s2), pdA, pdmA, int(nA), *pB, int(nB), int(N), _lib.stream_ptr()),
+               "fus_facet_terms")
 
 
 def facet_source_terms(y, bound_array, field, stage=None, stage_dev=None):
@@ -635,38 +597,21 @@ def facet_source_terms(y, bound_array, field, stage=None, stage_dev=None):
         raise TypeError(f"the source array was bound for {ba.dtype}, y is {dt}")
     nA = ba.nfacets
     if nA:
-        for name, t in (("coeff1", ba.coeff1), ("detJ_source", ba.detJ)):
+        for name, t in (("coeff1", ba.coeff1), ("detJ_source", ba.detJ)) + (() if ba.coeff2 is None else (("coeff2", ba.coeff2),)):
             _req(t, dt, name)
-        if ba.coeff2 is not None:
-            _req(ba.coeff2, dt, "coeff2")
         _req(ba.dofmap, torch.int32, "source dofmap")
         _req(ba.element_of_facet, torch.int32, "element_of_facet")
         for name, t in (("amplitude", ba.amplitude), ("phase", ba.phase), ("delay", ba.delay)):
             _req(t, torch.float64, name)
         if ba.detJ.shape != ba.dofmap.shape or ba.coeff1.numel() != nA or ba.dofmap.shape[0] != nA:
             raise ValueError("source facet arrays: detJ must have the dofmap's shape, one constant and one element id per facet")
-    nB = 0
-    if field is not None:
-        xB, cB, dB, dmB = field
-        for name, t in (("x", xB), ("c", cB), ("detJ_field", dB)):
-            _req(t, dt, name)
-        _req(dmB, torch.int32, "field dofmap")
-        nB = dmB.shape[0]
-        if nB and (dB.shape != dmB.shape or cB.numel() != nB):
-            raise ValueError("facet arrays: detJ must have the dofmap's shape, one constant per facet")
-        if nA and nB and ba.dofmap.shape[1] != dmB.shape[1]:
-            raise ValueError("both facet sets must have the same number of dofs per facet")
+    pB, nB, N = _facet_field(dt, field, ba.dofmap.shape[1] if nA else None)
     if nA + nB == 0:
         return
     if (stage is None) == (stage_dev is None):
         raise ValueError("facet_source_terms: give exactly one of stage (host) and stage_dev (device)")
-    N = ba.dofmap.shape[1] if nA else dmB.shape[1]
-    pA = lambda t: t.data_ptr() if (nA and t is not None) else None  # noqa: E731
-    pB = lambda t: t.data_ptr() if nB else None  # noqa: E731
-    args = [y.data_ptr(), pA(ba.coeff1), pA(ba.coeff2), pA(ba.detJ), pA(ba.dofmap), pA(ba.element_of_facet), int(nA),
-            pA(ba.amplitude), pA(ba.phase), pA(ba.delay), int(ba.n_elements)]
-    args += [pB(xB), pB(cB), pB(dB), pB(dmB)] if nB else [None] * 4
-    args += [int(nB), int(N)]
+    args = [y.data_ptr(), *_ptrs(nA, ba.coeff1, ba.coeff2, ba.detJ, ba.dofmap, ba.element_of_facet), int(nA),
+            *_ptrs(nA, ba.amplitude, ba.phase, ba.delay), int(ba.n_elements), *pB, int(nB), int(N)]
     if stage_dev is not None:
         _req(stage_dev, torch.float64, "stage_dev")
         if stage_dev.numel() < 6:
@@ -681,120 +626,124 @@ def facet_source_terms(y, bound_array, field, stage=None, stage_dev=None):
     _lib.check(fn(*args, st.ctypes.data, _lib.stream_ptr()), "fus_facet_source_array")
 
 
-# ---------------------------------------------------------------------- stiffness
-class _StiffnessOperator(_Launchable):
-    """Returned by ``stiffness_operator``; callable both ways."""
+# ----------------------------------------------------------------- cell operators
+def _to_device(a, dtype):
+    """Host array or tensor -> contiguous tensor of ``dtype`` on the current device."""
+    t = a if isinstance(a, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(np.asarray(a)))
+    return t.to(device=torch.device("cuda", torch.cuda.current_device()), dtype=dtype).contiguous()
 
-    def __init__(self, P: int, float_type, dphi=None, affine_weights=None, geometry=None):
+
+class _CellOperator:
+    """What the operators over the cells of a degree-P tensor-product mesh share: degree, type, the 1-D derivative table,
+    the vertex geometry of the in-kernel-geometry kernels, and the argument checks of an apply."""
+
+    def __init__(self, P, float_type, dphi=None):
         self.P = int(P)
         if not (1 <= self.P <= 10):
             raise ValueError(f"polynomial degree {P} outside the supported range 1..10")
         self.n = self.P + 1
         self.dtype = _lib.torch_dtype(float_type)
-        self._fn = getattr(_lib.load(), f"fus_stiffness_apply_{_lib.suffix(self.dtype)}")
-        self._fn_planned = getattr(_lib.load(), f"fus_stiffness_apply_planned_{_lib.suffix(self.dtype)}")
-        self._dphi = None
+        self._dphi = None if dphi is None else self._table(dphi)
+
+    def _entry(self, name):
+        return getattr(_lib.load(), f"fus_{name}_{_lib.suffix(self.dtype)}")
+
+    def _table(self, dphi):
+        """Accept the flat ``[q*n+i]`` (numba-cpu) or 2-D ``[q, i]`` (cuda) table, host or device."""
+        if (dphi.numel() if isinstance(dphi, torch.Tensor) else np.size(dphi)) != self.n * self.n:
+            raise ValueError(f"dphi must have {self.n * self.n} entries for P={self.P}")
+        return _to_device(dphi, self.dtype).reshape(-1)
+
+    def _geometry(self, x_g, pts, wts):
+        """-> (x_g T[nvert, 3], pts T[n], wts T[n]) on the device: the vertices and the 1-D GLL rule G is formed from in the kernel."""
+        xg, pt, wt = _to_device(x_g, self.dtype), _to_device(pts, self.dtype).reshape(-1), _to_device(wts, self.dtype).reshape(-1)
+        if xg.dim() != 2 or xg.shape[1] != 3:
+            raise ValueError("geometry: x_g must be [nvert, 3] (P1 hexahedra)")
+        if pt.numel() != self.n or wt.numel() != self.n:
+            raise ValueError(f"geometry: pts / wts must hold the {self.n} 1-D GLL points / weights")
+        return xg, pt, wt
+
+    def _check(self, dofmap, constants, tensors):
+        """The argument check of every apply; ``constants`` and ``tensors`` are (name, tensor) pairs: all of them have the
+        operator's type, ``dofmap`` is int32 [ncell, n^3], each of ``constants`` has one value per cell.  -> (ncell, n^3)"""
+        for name, t in tensors + constants:
+            _req(t, self.dtype, name)
+        _req(dofmap, torch.int32, "dofmap")
+        nd = self.n**3
+        if dofmap.dim() != 2 or dofmap.shape[1] != nd:
+            raise ValueError(f"dofmap must be [ncell, {nd}] for P={self.P}")
+        ncell = dofmap.shape[0]
+        for name, t in constants:
+            if t.numel() != ncell:
+                raise ValueError(f"{name} must have one value per cell")
+        return ncell, nd
+
+    def _check_G(self, G, ncell, nd):
+        _req(G, self.dtype, "G")
+        if G.numel() != ncell * nd * 6:
+            raise ValueError(f"G must be [ncell, {nd}, 6]")
+
+    @staticmethod
+    def _check_x_dofs(x_dofs, ncell):
+        _req(x_dofs, torch.int32, "x_dofs")
+        if x_dofs.dim() != 2 or x_dofs.shape[1] != 8:
+            raise ValueError("x_dofs must be [ncell, 8] (P1 hexahedra)")
+        if ncell is not None and x_dofs.shape[0] != ncell:
+            raise ValueError(f"geometry: x_dofs has {x_dofs.shape[0]} cells, dofmap has {ncell}")
+        return x_dofs
+
+
+class _StiffnessOperator(_CellOperator, _Launchable):
+    """Returned by ``stiffness_operator``; callable both ways."""
+
+    def __init__(self, P: int, float_type, dphi=None, affine_weights=None, geometry=None):
+        super().__init__(P, float_type, dphi)
+        self._fn = self._entry("stiffness_apply")
+        self._fn_planned = self._entry("stiffness_apply_planned")
         self._dphi_src = None
-        if dphi is not None:
-            self._dphi = self._table(dphi)
         # opt-in affine-cell fast path: tensor quadrature weights [n^3] of the rule G was built with
         self._wratio = None
         if affine_weights is not None:
             w = np.asarray(affine_weights, dtype=np.float64).reshape(-1)
             if w.size != self.n**3:
                 raise ValueError(f"affine_weights must hold the {self.n ** 3} tensor quadrature weights")
-            dev = torch.device("cuda", torch.cuda.current_device())
-            self._wratio = torch.from_numpy(w / w[0]).to(device=dev, dtype=self.dtype).contiguous()
-            self._fn_affine = getattr(_lib.load(), f"fus_stiffness_apply_planned_affine_{_lib.suffix(self.dtype)}")
-
+            self._wratio = _to_device(w / w[0], self.dtype)
+            self._fn_affine = self._entry("stiffness_apply_planned_affine")
         # opt-in in-kernel geometry: (x_dofs int32[ncell, 8], x_g T[nvert, 3], pts T[n], wts T[n]);
         # the G argument of the apply is then ignored (may be None)
         self._geom = None
         if geometry is not None:
-            x_dofs, x_g, pts, wts = geometry
-            dev = torch.device("cuda", torch.cuda.current_device())
-
-            def dev_t(a, dtype):
-                t = a if isinstance(a, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(np.asarray(a)))
-                return t.to(device=dev, dtype=dtype).contiguous()
-
-            xd, xg = dev_t(x_dofs, torch.int32), dev_t(x_g, self.dtype)
-            pt, wt = dev_t(pts, self.dtype).reshape(-1), dev_t(wts, self.dtype).reshape(-1)
-            if xd.dim() != 2 or xd.shape[1] != 8 or xg.dim() != 2 or xg.shape[1] != 3:
-                raise ValueError("geometry: x_dofs must be [ncell, 8] and x_g [nvert, 3] (P1 hexahedra)")
-            if pt.numel() != self.n or wt.numel() != self.n:
-                raise ValueError(f"geometry: pts / wts must hold the {self.n} 1-D GLL points / weights")
-            self._geom = (xd, xg, pt, wt)
-            self._fn_geom = getattr(_lib.load(), f"fus_stiffness_apply_planned_geom_{_lib.suffix(self.dtype)}")
-
-    def _table(self, dphi):
-        """Accept the flat ``[q*n+i]`` (numba-cpu) or 2-D ``[q, i]`` (cuda) table, host or device."""
-        if isinstance(dphi, torch.Tensor):
-            t = dphi
-        else:
-            t = torch.from_numpy(np.ascontiguousarray(np.asarray(dphi)))
-        if t.numel() != self.n * self.n:
-            raise ValueError(f"dphi must have {self.n * self.n} entries for P={self.P}, got {t.numel()}")
-        dev = torch.device("cuda", torch.cuda.current_device())
-        return t.to(device=dev, dtype=self.dtype).contiguous().reshape(-1)
+            self._geom = (self._check_x_dofs(_to_device(geometry[0], torch.int32), None),) + self._geometry(*geometry[1:])
+            self._fn_geom = self._entry("stiffness_apply_planned_geom")
 
     def _apply(self, x, cell_constants, y, G, dofmap, dphi_t):
-        dt = self.dtype
-        _req(x, dt, "x")
-        _req(cell_constants, dt, "cell_constants")
-        _req(y, dt, "y")
+        ncell, nd = self._check(dofmap, (("cell_constants", cell_constants),), (("x", x), ("y", y)))
         if self._geom is None:
-            _req(G, dt, "G")  # with geometry=: G is ignored (None), or carries the x_dofs rows of a cell sub-range
-        _req(dofmap, torch.int32, "dofmap")
-        nd = self.n**3
-        if dofmap.dim() != 2 or dofmap.shape[1] != nd:
-            raise ValueError(f"dofmap must be [ncell, {nd}] for P={self.P}")
-        ncell = dofmap.shape[0]
-        if self._geom is None and G.numel() != ncell * nd * 6:
-            raise ValueError(f"G must be [ncell, {nd}, 6]")
-        if cell_constants.numel() != ncell:
-            raise ValueError("cell_constants must have one value per cell")
-        if ncell == 0:
-            return
-        if self._geom is not None:
+            self._check_G(G, ncell, nd)
+        else:
             xd, xg, pt, wt = self._geom
             # a cell sub-range hands its rows of x_dofs in the G position (int32 [ncell, 8]: cannot be
-            # mistaken for a geometric-factor array)
+            # mistaken for a geometric-factor array); otherwise G is ignored (None)
             if isinstance(G, torch.Tensor) and G.dtype == torch.int32:
-                _req(G, torch.int32, "x_dofs")
-                if tuple(G.shape) != (ncell, 8):
-                    raise ValueError(f"x_dofs must be [{ncell}, 8]")
                 xd = G
-            if xd.shape[0] != ncell:
-                raise ValueError(f"geometry: x_dofs has {xd.shape[0]} cells, dofmap has {ncell}")
+            self._check_x_dofs(xd, ncell)
+        if ncell == 0:
+            return
+        head = (x.data_ptr(), cell_constants.data_ptr(), y.data_ptr())
+        tail = (dphi_t.data_ptr(), self.P, int(ncell), _lib.stream_ptr())
+        if self._geom is not None:
             ws, _ = _PLANS.get(dofmap, strips=True)
-            _lib.check(
-                self._fn_geom(x.data_ptr(), cell_constants.data_ptr(), y.data_ptr(), xg.data_ptr(), xd.data_ptr(),
-                              pt.data_ptr(), wt.data_ptr(), ws.data_ptr(), dphi_t.data_ptr(), self.P, int(ncell),
-                              _lib.stream_ptr()),
-                "fus_stiffness_apply_planned_geom",
-            )
+            _lib.check(self._fn_geom(*head, xg.data_ptr(), xd.data_ptr(), pt.data_ptr(), wt.data_ptr(), ws.data_ptr(), *tail),
+                       "fus_stiffness_apply_planned_geom")
         elif self._wratio is not None:
             ws, _ = _PLANS.get(dofmap, strips=True)
-            _lib.check(
-                self._fn_affine(x.data_ptr(), cell_constants.data_ptr(), y.data_ptr(), G.data_ptr(),
-                                self._wratio.data_ptr(), ws.data_ptr(), dphi_t.data_ptr(), self.P, int(ncell),
-                                _lib.stream_ptr()),
-                "fus_stiffness_apply_planned_affine",
-            )
+            _lib.check(self._fn_affine(*head, G.data_ptr(), self._wratio.data_ptr(), ws.data_ptr(), *tail),
+                       "fus_stiffness_apply_planned_affine")
         elif _USE_PLAN:
             ws, _ = _PLANS.get(dofmap)
-            _lib.check(
-                self._fn_planned(x.data_ptr(), cell_constants.data_ptr(), y.data_ptr(), G.data_ptr(), ws.data_ptr(),
-                                 dphi_t.data_ptr(), self.P, int(ncell), _lib.stream_ptr()),
-                "fus_stiffness_apply_planned",
-            )
+            _lib.check(self._fn_planned(*head, G.data_ptr(), ws.data_ptr(), *tail), "fus_stiffness_apply_planned")
         else:
-            _lib.check(
-                self._fn(x.data_ptr(), cell_constants.data_ptr(), y.data_ptr(), G.data_ptr(), dofmap.data_ptr(),
-                         dphi_t.data_ptr(), self.P, int(ncell), _lib.stream_ptr()),
-                "fus_stiffness_apply",
-            )
+            _lib.check(self._fn(*head, G.data_ptr(), dofmap.data_ptr(), *tail), "fus_stiffness_apply")
 
     def prepare(self, dofmap):
         """Set-up, not an apply: build (and cache) the batch plan for ``dofmap`` now instead of
@@ -837,7 +786,7 @@ def stiffness_operator(P, *args, affine_weights=None, geometry=None):
     raise TypeError("stiffness_operator(P, dphi, float_type) or stiffness_operator(P, float_type)")
 
 
-class _GradientOperator:
+class _GradientOperator(_CellOperator):
     """Returned by ``gradient_operator``: ``op(x, cell_constants, y3, dofmap)`` adds the weak gradient C(c) x
     (csrc/gradient_geom.hpp) to the three rows of ``y3``."""
 
@@ -846,38 +795,27 @@ class _GradientOperator:
             raise ValueError("gradient_operator needs geometry=(x_dofs, x_g, pts, wts): the gradient is formed from the cell vertices")
         if dphi is None:
             raise ValueError("gradient_operator needs the 1-D derivative table dphi")
-        self._st = _StiffnessOperator(P, float_type, dphi, None, geometry)  # reuses table / geometry conversion + checks
-        self.P, self.n, self.dtype = self._st.P, self._st.n, self._st.dtype
-        self._fn = getattr(_lib.load(), f"fus_gradient_apply_planned_geom_{_lib.suffix(self.dtype)}")
+        super().__init__(P, float_type, dphi)
+        self._geom = (self._check_x_dofs(_to_device(geometry[0], torch.int32), None),) + self._geometry(*geometry[1:])
+        self._fn = self._entry("gradient_apply_planned_geom")
 
     def __call__(self, x, cell_constants, y3, dofmap):
-        dt = self.dtype
-        _req(x, dt, "x")
-        _req(cell_constants, dt, "cell_constants")
-        if isinstance(y3, torch.Tensor) and y3.dim() == 2 and y3.shape[0] == 3 and y3.stride(1) == 1:
-            _req(y3[0], dt, "y3")  # rows may be further apart than ndofs (a view): the kernel takes the row stride
-        else:
-            _req(y3, dt, "y3")
+        rows = isinstance(y3, torch.Tensor) and y3.dim() == 2 and y3.shape[0] == 3 and y3.stride(1) == 1
+        # rows may be further apart than ndofs (a view): the kernel takes the row stride
+        ncell, _ = self._check(dofmap, (("cell_constants", cell_constants),), (("x", x), ("y3", y3[0] if rows else y3)))
+        if not rows:
             raise ValueError("y3 must be [3, ndofs] with contiguous rows")
-        _req(dofmap, torch.int32, "dofmap")
-        nd = self.n**3
-        if dofmap.dim() != 2 or dofmap.shape[1] != nd:
-            raise ValueError(f"dofmap must be [ncell, {nd}] for P={self.P}")
-        ncell = dofmap.shape[0]
         ystride = y3.stride(0) if y3.shape[1] > 0 else 0
         if x.dim() != 1 or y3.shape[1] != x.numel() or ystride < y3.shape[1]:
             raise ValueError("x must be [ndofs] and y3 [3, ndofs] over the same dofs")
-        if cell_constants.numel() != ncell:
-            raise ValueError("cell_constants must have one value per cell")
-        xd, xg, pt, wt = self._st._geom
-        if xd.shape[0] != ncell:
-            raise ValueError(f"geometry: x_dofs has {xd.shape[0]} cells, dofmap has {ncell}")
+        xd, xg, pt, wt = self._geom
+        self._check_x_dofs(xd, ncell)
         if ncell == 0:
             return
         ws, _ = _PLANS.get(dofmap, strips=True)
         _lib.check(
             self._fn(x.data_ptr(), cell_constants.data_ptr(), y3.data_ptr(), int(ystride), xg.data_ptr(), xd.data_ptr(), pt.data_ptr(),
-                     wt.data_ptr(), ws.data_ptr(), self._st._dphi.data_ptr(), self.P, int(ncell), _lib.stream_ptr()),
+                     wt.data_ptr(), ws.data_ptr(), self._dphi.data_ptr(), self.P, int(ncell), _lib.stream_ptr()),
             "fus_gradient_apply_planned_geom",
         )
 
@@ -900,120 +838,77 @@ def gradient_operator(P, dphi, float_type, geometry=None):
     return _GradientOperator(P, dphi, float_type, geometry)
 
 
-def _stiffness_only_ncell(op, u, v, c3, c4, b, dofmap):
-    """The argument checks of a Westervelt cell operator's ``stiffness_only``; returns the number of cells."""
-    for name, t in (("u", u), ("v", v), ("c3", c3), ("c4", c4), ("b", b)):
-        _req(t, op.dtype, name)
-    _req(dofmap, torch.int32, "dofmap")
-    nd = op.n**3
-    ncell = dofmap.shape[0]
-    if dofmap.dim() != 2 or dofmap.shape[1] != nd or c3.numel() != ncell or c4.numel() != ncell:
-        raise ValueError(f"dofmap [ncell, {nd}] and one c3 / c4 value per cell expected")
-    return ncell
-
-
-class _WesterveltCellOperator:
+class _WesterveltCellOperator(_CellOperator):
     """Fused Westervelt cell pass (csrc/westervelt.hpp): ``b += K(c3) u + K(c4) v + M(c5) v^2`` and
     ``m += M(c2) u`` in one sweep over the cells -- the four cell launches of
-    cuda/demo_nonlinear_bowl.py:612-632 (+ square :603).  No reference counterpart as a single call."""
+    cuda/demo_nonlinear_bowl.py:612-632 (+ square :603).  No reference counterpart as a single call.
+    The body of both forms; ``geometry``: the cell geometry a call hands over, ``(G, detJ)`` here."""
+
+    _entry_name, _strips = "westervelt_cell_apply_planned", False
 
     def __init__(self, P, dphi, float_type):
-        self._st = _StiffnessOperator(P, float_type, dphi)  # reuses table conversion + checks
-        self.P, self.n, self.dtype = self._st.P, self._st.n, self._st.dtype
-        self._fn = getattr(_lib.load(), f"fus_westervelt_cell_apply_planned_{_lib.suffix(self.dtype)}")
+        super().__init__(P, float_type, dphi)
+        self._fn = self._entry(self._entry_name)
 
-    def __call__(self, u, v, c2, c3, c4, c5, b, m, G, detJ, dofmap):
-        dt = self.dtype
-        for name, t in (("u", u), ("v", v), ("c2", c2), ("c3", c3), ("c4", c4), ("c5", c5), ("b", b), ("m", m),
-                        ("G", G), ("detJ", detJ)):
-            _req(t, dt, name)
-        _req(dofmap, torch.int32, "dofmap")
-        nd = self.n**3
-        ncell = dofmap.shape[0]
-        if dofmap.dim() != 2 or dofmap.shape[1] != nd or G.numel() != ncell * nd * 6 or detJ.numel() != ncell * nd:
-            raise ValueError(f"dofmap [ncell, {nd}], G [ncell, {nd}, 6], detJ [ncell, {nd}] expected")
-        for name, t in (("c2", c2), ("c3", c3), ("c4", c4), ("c5", c5)):
-            if t.numel() != ncell:
-                raise ValueError(f"{name} must have one value per cell")
+    def _geometry_args(self, geometry, ncell, nd, full):
+        G, detJ = geometry
+        self._check_G(G, ncell, nd)
+        if full:
+            _req(detJ, self.dtype, "detJ")
+            if detJ.numel() != ncell * nd:
+                raise ValueError(f"detJ must be [ncell, {nd}]")
+        return G.data_ptr(), detJ.data_ptr() if full else None
+
+    def _apply(self, u, v, c2, c3, c4, c5, b, m, geometry, dofmap):
+        """``c2``, ``c5``, ``m`` None: the stiffness part alone."""
+        full = c2 is not None
+        if full:
+            ncell, nd = self._check(dofmap, (("c2", c2), ("c3", c3), ("c4", c4), ("c5", c5)), (("u", u), ("v", v), ("b", b), ("m", m)))
+        else:
+            ncell, nd = self._check(dofmap, (("c3", c3), ("c4", c4)), (("u", u), ("v", v), ("b", b)))
+        geometry = self._geometry_args(geometry, ncell, nd, full)
         if ncell == 0:
             return
-        ws, _ = _PLANS.get(dofmap)
+        ws, _ = _PLANS.get(dofmap, strips=self._strips)
         _lib.check(
-            self._fn(u.data_ptr(), v.data_ptr(), c2.data_ptr(), c3.data_ptr(), c4.data_ptr(), c5.data_ptr(),
-                     b.data_ptr(), m.data_ptr(), G.data_ptr(), detJ.data_ptr(), ws.data_ptr(),
-                     self._st._dphi.data_ptr(), self.P, int(ncell), _lib.stream_ptr()),
-            "fus_westervelt_cell_apply_planned",
+            self._fn(u.data_ptr(), v.data_ptr(), c2.data_ptr() if full else None, c3.data_ptr(), c4.data_ptr(),
+                     c5.data_ptr() if full else None, b.data_ptr(), m.data_ptr() if full else None, *geometry, ws.data_ptr(),
+                     self._dphi.data_ptr(), self.P, int(ncell), _lib.stream_ptr()),
+            "fus_" + self._entry_name if full else "fus_westervelt_cell_apply_planned (stiffness part)",
         )
+
+    def __call__(self, u, v, c2, c3, c4, c5, b, m, G, detJ, dofmap):
+        self._apply(u, v, c2, c3, c4, c5, b, m, (G, detJ), dofmap)
 
     def stiffness_only(self, u, v, c3, c4, b, G, dofmap):
         """``b += K(c3) u + K(c4) v`` in one pass over the cells (G read once, u and v gathered once): the
         stiffness part of the Westervelt stage; the mass terms are applied pointwise by the driver from
         precomputed diagonals (``fus_rk4_stage_nl2_*``)."""
-        ncell = _stiffness_only_ncell(self, u, v, c3, c4, b, dofmap)
-        if ncell == 0:
-            return
-        ws, _ = _PLANS.get(dofmap)
-        _req(G, self.dtype, "G")
-        if G.numel() != ncell * self.n**3 * 6:
-            raise ValueError(f"G [ncell, {self.n**3}, 6] expected")
-        _lib.check(self._fn(u.data_ptr(), v.data_ptr(), None, c3.data_ptr(), c4.data_ptr(), None, b.data_ptr(), None,
-                            G.data_ptr(), None, ws.data_ptr(), self._st._dphi.data_ptr(), self.P, int(ncell), _lib.stream_ptr()),
-                   "fus_westervelt_cell_apply_planned (stiffness part)")
+        self._apply(u, v, None, c3, c4, None, b, None, (G, None), dofmap)
 
 
-class _WesterveltCellGeomOperator:
+class _WesterveltCellGeomOperator(_WesterveltCellOperator):
     """The fused Westervelt cell pass with G and detJ formed in the kernel from the cell vertices
     (csrc/westervelt_geom.hpp): ``op(u, v, c2, c3, c4, c5, b, m, x_dofs, dofmap)``.  ``x_dofs`` (int32
     [ncell, 8], dofmap cell order) is a call argument so that cell sub-ranges can be passed as views;
     ``x_g``, ``pts``, ``wts`` are fixed at construction."""
 
+    _entry_name, _strips = "westervelt_cell_apply_planned_geom", True
+
     def __init__(self, P, dphi, float_type, x_g, pts, wts):
-        self._st = _StiffnessOperator(P, float_type, dphi)
-        self.P, self.n, self.dtype = self._st.P, self._st.n, self._st.dtype
-        dev = torch.device("cuda", torch.cuda.current_device())
-        conv = lambda a: (a if isinstance(a, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(np.asarray(a)))).to(  # noqa: E731
-            device=dev, dtype=self.dtype).contiguous()
-        self.x_g, self.pts, self.wts = conv(x_g), conv(pts).reshape(-1), conv(wts).reshape(-1)
-        if self.x_g.dim() != 2 or self.x_g.shape[1] != 3 or self.pts.numel() != self.n or self.wts.numel() != self.n:
-            raise ValueError("x_g must be [nvert, 3]; pts / wts the 1-D GLL points / weights")
-        self._fn = getattr(_lib.load(), f"fus_westervelt_cell_apply_planned_geom_{_lib.suffix(self.dtype)}")
+        super().__init__(P, dphi, float_type)
+        self.x_g, self.pts, self.wts = self._geometry(x_g, pts, wts)
+
+    def _geometry_args(self, x_dofs, ncell, nd, full):
+        self._check_x_dofs(x_dofs, ncell)
+        return self.x_g.data_ptr(), x_dofs.data_ptr(), self.pts.data_ptr(), self.wts.data_ptr()
 
     def __call__(self, u, v, c2, c3, c4, c5, b, m, x_dofs, dofmap):
-        dt = self.dtype
-        for name, t in (("u", u), ("v", v), ("c2", c2), ("c3", c3), ("c4", c4), ("c5", c5), ("b", b), ("m", m)):
-            _req(t, dt, name)
-        _req(dofmap, torch.int32, "dofmap")
-        _req(x_dofs, torch.int32, "x_dofs")
-        nd = self.n**3
-        ncell = dofmap.shape[0]
-        if dofmap.dim() != 2 or dofmap.shape[1] != nd or tuple(x_dofs.shape) != (ncell, 8):
-            raise ValueError(f"dofmap [ncell, {nd}] and x_dofs [ncell, 8] expected")
-        for name, t in (("c2", c2), ("c3", c3), ("c4", c4), ("c5", c5)):
-            if t.numel() != ncell:
-                raise ValueError(f"{name} must have one value per cell")
-        if ncell == 0:
-            return
-        ws, _ = _PLANS.get(dofmap, strips=True)
-        _lib.check(
-            self._fn(u.data_ptr(), v.data_ptr(), c2.data_ptr(), c3.data_ptr(), c4.data_ptr(), c5.data_ptr(),
-                     b.data_ptr(), m.data_ptr(), self.x_g.data_ptr(), x_dofs.data_ptr(), self.pts.data_ptr(),
-                     self.wts.data_ptr(), ws.data_ptr(), self._st._dphi.data_ptr(), self.P, int(ncell), _lib.stream_ptr()),
-            "fus_westervelt_cell_apply_planned_geom",
-        )
+        self._apply(u, v, c2, c3, c4, c5, b, m, x_dofs, dofmap)
 
     def stiffness_only(self, u, v, c3, c4, b, x_dofs, dofmap):
         """As ``_WesterveltCellOperator.stiffness_only`` with G formed in the kernel from the cell vertices."""
-        ncell = _stiffness_only_ncell(self, u, v, c3, c4, b, dofmap)
-        if ncell == 0:
-            return
-        ws, _ = _PLANS.get(dofmap, strips=True)
-        _req(x_dofs, torch.int32, "x_dofs")
-        if tuple(x_dofs.shape) != (ncell, 8):
-            raise ValueError("x_dofs [ncell, 8] expected")
-        _lib.check(self._fn(u.data_ptr(), v.data_ptr(), None, c3.data_ptr(), c4.data_ptr(), None, b.data_ptr(), None,
-                            self.x_g.data_ptr(), x_dofs.data_ptr(), self.pts.data_ptr(), self.wts.data_ptr(), ws.data_ptr(),
-                            self._st._dphi.data_ptr(), self.P, int(ncell), _lib.stream_ptr()),
-                   "fus_westervelt_cell_apply_planned (stiffness part)")
+        self._apply(u, v, None, c3, c4, None, b, None, x_dofs, dofmap)
 
 
 def westervelt_cell_operator(P, dphi, float_type, geometry=None):
@@ -1056,7 +951,7 @@ def _vec(name, *tensors):
 
 
 def _axpy(alpha, x, y, n=None):
-    fn, size = _vec("axpy", x, y)
+    fn, _ = _vec("axpy", x, y)
     n = min(x.numel(), y.numel()) if n is None else int(n)
     if n > x.numel() or n > y.numel():
         raise ValueError("axpy: n exceeds the vector length")

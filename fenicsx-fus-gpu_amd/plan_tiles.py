@@ -23,7 +23,7 @@ its extrusion / sweep direction):
      of the row's k-th cell for every k;
   4. paired rows are emitted interleaved, unpaired rows as they are.
 Host numpy, once per dofmap (config 3: 0.2 s).  The result is only a candidate: the plan cache builds the plan with it and keeps
-it if its batches touch fewer distinct dofs (operators._PlanCache).
+it if its batches touch fewer distinct dofs (operators._PlanCache._build).
 """
 
 from __future__ import annotations
