@@ -127,6 +127,7 @@ TUNE_MASS_VARIANT = 3
 TUNE_PLAN_VARIANT = 4
 TUNE_PLAN_RUNS = 5
 TUNE_VECTOR_STREAM = 6
+TUNE_PLAN_ROWS = 7  # fp64 general-G apply: 1 (default) one slot per local row + compact run tables where the plan allows, 0 never
 
 ABI_VERSION = 3  # include/fus_gpu.h FUS_ABI_VERSION
 

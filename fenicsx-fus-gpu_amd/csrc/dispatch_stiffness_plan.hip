@@ -19,6 +19,25 @@ hipError_t launch_plan_f32_5w(const T* x, const T* cc, T* y, const T* G, const v
     return fus::launch_stiffness_plan<T, P, false, true, 1>(x, cc, y, G, ws, dphi, ncell, remap, s, ord, runs);
 }
 
+// Degrees whose fp64 auto build also ships as stiffness_plan_rows_kernel (one slot per local row, compact run tables): those where
+// the rows build has no scratch and the occupancy of its stiffness_plan_kernel twin (tests/test_plan_rows_isa.py).
+template <int P>
+constexpr bool plan_rows_ships() {
+  return P >= 2 && P <= 8;
+}
+// the auto build of degree P (the table in stiffness_apply_planned) as a rows launch
+template <typename T, int P>
+hipError_t launch_plan_rows_auto(const T* x, const T* cc, T* y, const T* G, const void* ws, const T* dphi, int64_t ncell, int remap,
+                                 hipStream_t s, bool ord, int run_stride) {
+  if constexpr (P <= 3)
+    return fus::launch_stiffness_plan_rows<T, P, false, true, 1>(x, cc, y, G, ws, dphi, ncell, remap, s, ord, run_stride);
+  else if constexpr (P <= 5)
+    return fus::launch_stiffness_plan_rows<T, P, true, true, 1>(x, cc, y, G, ws, dphi, ncell, remap, s, ord, run_stride);
+  else
+    return fus::launch_stiffness_plan_rows<T, P, true, (P != 8), fus::plan_ring_min_waves<P>(), fus::plan_g_ring<P>()>(
+        x, cc, y, G, ws, dphi, ncell, remap, s, ord, run_stride);
+}
+
 template <typename T>
 int stiffness_apply_planned(const T* x, const T* cc, T* y, const T* G, const void* ws, const T* dphi, int P,
                             int64_t ncell, void* stream) {
@@ -34,6 +53,13 @@ int stiffness_apply_planned(const T* x, const T* cc, T* y, const T* G, const voi
     //                                                  drops the LDS padding to fit a third workgroup per CU)
     //   30 fp32, registers allow 5 waves per SIMD     (fp32, P <= 4)
     int pv = g_plan_variant.load(std::memory_order_relaxed);
+    if constexpr (sizeof(T) == 8 && plan_rows_ships<PP>()) {
+      // auto build, run-coded launch, a plan whose header says rows_consecutive: the same build reading one slot per row
+      if (pv < 0 && runs && g_plan_rows.load(std::memory_order_relaxed) != 0) {
+        const int run_stride = plan_rows_stride(ws);
+        if (run_stride > 0) return launch_plan_rows_auto<T, PP>(x, cc, y, G, ws, dphi, ncell, remap, s, ord, run_stride);
+      }
+    }
     if (pv < 0) {
       if (sizeof(T) == 4)
         pv = (PP <= 4) ? 30 : 1;  // fp32: registers are not the limit, the whole G slab up front wins (r02y_ab_fp32.log)

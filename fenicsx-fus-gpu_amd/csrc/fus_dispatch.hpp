@@ -38,10 +38,16 @@ inline bool plan_use_runs(int ndof_per_entity, bool runs_pay = true) {
   return mode == 2 || (mode == 1 && (sizeof(T) == 8 || ndof_per_entity <= 729));
 }
 inline std::atomic<int> g_plan_variant{-1};  // -1 = auto
+// fp64 general-G apply: 1 (default) = a run-coded launch of a plan whose rows are all consecutive reads one slot per local ROW and the
+// compact run tables (stiffness_plan_rows_kernel); 0 = never (the A/B knob: the launch then runs stiffness_plan_kernel)
+inline std::atomic<int> g_plan_rows{1};
 
 // The one workspace registry of the library (plan_registry.hpp) is defined in fus_gpu.hip, where the header type of the gather plans is
 // complete.  true if ``ws`` holds a batch plan for exactly this shape; ``ordered`` out
 bool plan_check(const void* ws, int N, int epb, int64_t nent, bool* ordered, bool* exclusive = nullptr, bool* runs_pay = nullptr);
+
+// runs per batch of the compact run tables if the plan at ``ws`` says that its rows are consecutive, else 0
+int plan_rows_stride(const void* ws);
 
 inline int hip_rc(hipError_t e) { return e == hipSuccess ? FUS_OK : FUS_ERR_HIP_BASE - (int)e; }
 

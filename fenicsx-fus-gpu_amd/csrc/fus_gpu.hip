@@ -316,6 +316,11 @@ bool fus_abi::plan_check(const void* ws, int N, int epb, int64_t nent, bool* ord
   return true;
 }
 
+int fus_abi::plan_rows_stride(const void* ws) {
+  PlanInfo p;
+  return (g_registry.get(ws, &p) && p.rows_consecutive) ? p.run_stride : 0;
+}
+
 extern "C" {
 
 int fus_abi_version(void) { return FUS_ABI_VERSION; }
@@ -362,6 +367,7 @@ int fus_set_tuning(int key, int value) {
     case FUS_TUNE_MASS_VARIANT: g_mass_variant = value; return FUS_OK;
     case FUS_TUNE_PLAN_VARIANT: g_plan_variant = value; return FUS_OK;
     case FUS_TUNE_PLAN_RUNS: g_plan_runs = value; return FUS_OK;
+    case FUS_TUNE_PLAN_ROWS: g_plan_rows = value ? 1 : 0; return FUS_OK;
     case FUS_TUNE_VECTOR_STREAM:
       if (value < 0 || value > 4) return FUS_ERR_INVALID_ARGUMENT;
       fus::vector_stream_mode() = value;
@@ -377,6 +383,7 @@ int fus_get_tuning(int key) {
     case FUS_TUNE_MASS_VARIANT: return g_mass_variant;
     case FUS_TUNE_PLAN_VARIANT: return g_plan_variant;
     case FUS_TUNE_PLAN_RUNS: return g_plan_runs;
+    case FUS_TUNE_PLAN_ROWS: return g_plan_rows;
     case FUS_TUNE_VECTOR_STREAM: return fus::vector_stream_mode();
   }
   return FUS_ERR_INVALID_ARGUMENT;
@@ -473,12 +480,15 @@ int fus_plan_build_ordered(const int32_t* dofmap, const int32_t* entity_order, i
     if (e != hipSuccess) return hip_rc(e);
   }
   int64_t nbatch = 0, with_runs = 0;
+  bool rows = false;
+  int run_stride = 0;
   if (nent > 0) {
-    const hipError_t e = fus::plan_run_batches(workspace, static_cast<hipStream_t>(stream), &with_runs);
+    const hipError_t e = fus::plan_run_batches(workspace, static_cast<hipStream_t>(stream), &with_runs, &rows, &run_stride);
     if (e != hipSuccess) return hip_rc(e);
     nbatch = (nent + entities_per_batch - 1) / entities_per_batch;
   }
-  g_registry.put(workspace, PlanInfo{N, entities_per_batch, nent, entity_order != nullptr, false, 2 * with_runs >= nbatch, nbatch, with_runs});
+  g_registry.put(workspace, PlanInfo{N, entities_per_batch, nent, entity_order != nullptr, false, 2 * with_runs >= nbatch, nbatch, with_runs,
+                                     rows, fus::plan_row_len(N) > 0 ? run_stride : 0});
   return FUS_OK;
 }
 

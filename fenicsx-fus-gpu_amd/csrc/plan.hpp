@@ -27,11 +27,23 @@
 //   order  int32 [nent]             optional cell order: batch b holds the entities order[b*CPB ..]
 //                                   (set-up-time locality reordering WITHOUT moving G / detJ / constants:
 //                                   the apply kernels index those arrays through it); unused otherwise
+//   rowbase uint16[nbatch][CPB*n^2] cell plans only (N = n^3): slot of the FIRST dof of each local row (fixed ix, ty; tz = 0), entry
+//                                   (cell position, ix * n + ty).  In a structured numbering the n dofs of a row are consecutive
+//                                   integers, and so are their slots: slot(ix, ty, tz) = rowbase(ix, ty) + tz.  The header says whether
+//                                   that holds for EVERY row of the plan (rows_consecutive); a kernel that relies on it
+//                                   (stiffness_plan_rows_kernel) streams 2 n^2 bytes per cell instead of 2 n^3
+//   runs_c  int32 [nbatch][2*run_stride]  cell plans only: a second copy of the run tables at the stride the header gives (run_stride:
+//                                   the smallest power of two >= the runs of any batch; kPlanMaxRuns if a batch did not compress).
+//                                   The region is sized for kPlanMaxRuns; a speculative read of a batch's table fetches 8 run_stride
+//                                   bytes instead of 1 kB (P = 4 box meshes: 512)
 //   excl   uint32[nbatch][ceil(CPB*Nd/32)]  optional (fus_plan_mark_exclusive): bit s of batch b = the batch's distinct
 //                                   dof number s is touched by NO other batch of this plan (and by nothing else the caller
 //                                   declared): its partial sum is finished with a plain load + store instead of an atomic --
 //                                   the float-atomic request rate of the chip (~20 G 64-byte requests/s), not HBM, bounds
-//                                   the low-intensity kernels (mass: 92 % of that rate, profiles/r03_mass_counters.json)
+//                                   the low-intensity kernels (mass: 92 % of that rate, profiles/r03_mass_counters.json).
+//                                   Always the LAST region (its readers outside the library find it from the end of the workspace)
+// Header words beyond the six above (int64 each): 6 ordered, 7 batches with a run table, 8 rows_consecutive, 9 run_stride,
+// 10 / 11 the builder's scratch (a row was not consecutive; the largest run count).
 // Nd = (P+1)^3; the last batch may be ragged (cells >= ncell are never touched).
 #pragma once
 
@@ -131,6 +143,11 @@ inline LaunchSignal take_launch_signal_of(const uint64_t* flag, hipStream_t* str
 constexpr int64_t kPlanMagic = 0x46555350314c414eLL;  // "FUSP1LAN"
 constexpr int kPlanMaxRuns = 128;                      // runs of a batch: one per thread of (at least) two waves
 constexpr int kPlanHeaderBytes = 256;
+constexpr int kPlanHeaderRunBatches = 56;       // byte offsets in the plan header (int64 words 7 .. 11)
+constexpr int kPlanHeaderRowsConsecutive = 64;
+constexpr int kPlanHeaderRunStride = 72;
+constexpr int kPlanHeaderRowBroken = 80;
+constexpr int kPlanHeaderMaxRuns = 88;
 
 __host__ __device__ constexpr int next_pow2(int v) {
   int p = 1;
@@ -156,8 +173,18 @@ struct PlanView {
   int32_t* order;
   uint32_t* excl;
   int64_t excl_words;  // per batch
+  int row_len;          // n of a cell plan (N = n^3), 0 otherwise: no rowbase / runs_c regions
+  uint16_t* rowbase;
+  int32_t* runs_c;
   int64_t bytes;
 };
+
+// n if N = n^3 (a cell plan: its local rows are n dofs long), 0 otherwise
+__host__ __device__ constexpr int plan_row_len(int N) {
+  int n = 1;
+  while (n * n * n < N) ++n;
+  return n * n * n == N ? n : 0;
+}
 
 // Generic plan geometry: ``nent`` entities of ``N`` dofs each, ``epb`` entities per batch.
 inline PlanView plan_view_generic(void* workspace, int N, int epb, int64_t nent) {
@@ -176,7 +203,12 @@ inline PlanView plan_view_generic(void* workspace, int N, int epb, int64_t nent)
   off += align256(v.nbatch * v.entries * (int64_t)sizeof(uint16_t));
   v.order = reinterpret_cast<int32_t*>(base + off);
   off += align256(nent * (int64_t)sizeof(int32_t));
-  v.excl = reinterpret_cast<uint32_t*>(base + off);
+  v.row_len = plan_row_len(N);
+  v.rowbase = reinterpret_cast<uint16_t*>(base + off);
+  if (v.row_len > 0) off += align256(v.nbatch * (v.entries / v.row_len) * (int64_t)sizeof(uint16_t));
+  v.runs_c = reinterpret_cast<int32_t*>(base + off);
+  if (v.row_len > 0) off += align256(v.nbatch * (int64_t)(2 * kPlanMaxRuns) * (int64_t)sizeof(int32_t));
+  v.excl = reinterpret_cast<uint32_t*>(base + off);  // the last region
   v.excl_words = (v.entries + 31) / 32;
   off += align256(v.nbatch * v.excl_words * (int64_t)sizeof(uint32_t));
   v.bytes = off;
@@ -276,6 +308,17 @@ __device__ __forceinline__ RunWords batch_dofs_issue(const int32_t* __restrict__
       mydof[r] = ud[s < M ? s : 0];
     }
   }
+  return rw;
+}
+// The run words of a launch that reads the compact copy of the tables (runs_c: ``stride`` runs per batch, a launch argument); threads
+// beyond the stride clamp to its last entry, as batch_dofs_issue does at kPlanMaxRuns.
+__device__ __forceinline__ RunWords batch_runs_issue_compact(const int32_t* __restrict__ rn, int stride, int tid) {
+  RunWords rw;
+  const int last = 2 * stride - 1;
+  const int i0 = 2 * tid, i1 = 2 * tid + 1, i3 = 2 * tid + 3;
+  rw.d0 = rn[i0 < last ? i0 : last];
+  rw.s0 = rn[i1 < last ? i1 : last];
+  rw.s1 = rn[i3 < last ? i3 : last];
   return rw;
 }
 // nu[batch]: distinct dofs (low half) and, in a run-coded launch, runs (high half; 0 = this batch's list did not compress)

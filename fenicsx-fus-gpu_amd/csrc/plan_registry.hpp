@@ -20,6 +20,8 @@ struct PlanInfo {
   bool exclusive = false;  // fus_plan_mark_exclusive has run: the plan carries exclusive-dof marks
   bool runs_pay = true;    // at least half of the batches carry a run table (plan_use_runs)
   int64_t nbatch = 0, with_runs = 0;
+  bool rows_consecutive = false;  // the header's word: every local row of every cell is consecutive dof numbers (plan.hpp: rowbase)
+  int run_stride = 0;             // runs per batch of the compact copy of the run tables (plan.hpp: runs_c); 0: the plan has none
 };
 
 // static companion of a transposed gather plan (detJ in row order), keyed by its own workspace address

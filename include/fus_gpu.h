@@ -76,6 +76,7 @@ int fus_device_info(int device, char* name, int* compute_units, int64_t* hbm_byt
 #define FUS_TUNE_MASS_VARIANT 3       /* rows per thread of the atomic-free mass apply (fus_mass_apply_gather_*): 1, 2, 4; 0 (default) = by size and type */
 #define FUS_TUNE_PLAN_VARIANT 4      /* planned stiffness kernel build: see csrc/fus_gpu.hip */
 #define FUS_TUNE_PLAN_RUNS 5         /* which encoding of a plan's dof lists the apply kernels read: 0 the lists, 2 the run tables, 1 auto (default: fp64 run tables; fp32 run tables up to 125 dofs per entity, lists above); 0 at plan build = no run tables are built */
+#define FUS_TUNE_PLAN_ROWS 7         /* fp64 general-G planned apply on a plan whose local rows are all consecutive dof numbers (every box-mesh numbering): 1 (default) = read one 16-bit slot per local row and the compact run tables, 0 = one slot per dof and the full tables (A/B knob; same result) */
 #define FUS_TUNE_VECTOR_STREAM 6      /* non-temporal accesses in the streaming vector kernels (fus_axpy ... fus_rk4_stage_*): 0 never, 1 auto (default: non-temporal loads and stores for operands > 24 MB), 2 always, 3 / 4 the same with non-temporal stores only -- a plain store leaves its line dirty in the memory-side cache, to be written back while the NEXT kernel runs (csrc/vecops.hpp) */
 int fus_set_tuning(int key, int value);
 int fus_get_tuning(int key);
@@ -303,10 +304,16 @@ int fus_gradient_apply_planned_geom_f32(const float* x, const float* cell_consta
  * fus_stiffness_plan_build(dofmap, P, ...) == fus_plan_build(dofmap, n^3, fus_plan_entities_per_batch(n^3), ...)).
  *
  * SYNCHRONISATION: fus_plan_build / fus_plan_build_ordered / fus_stiffness_plan_build enqueue the build kernels on ``stream`` and then
- * BLOCK THE HOST until they have run (one 8-byte device-to-host copy + hipStreamSynchronize: the number of batches that carry a run
- * table decides which list encoding the applies read).  They are set-up calls: not stream-asynchronous, and NOT legal inside a hipGraph
+ * BLOCK THE HOST until they have run (one 24-byte device-to-host copy + hipStreamSynchronize: the number of batches that carry a run
+ * table decides which list encoding the applies read; whether every local row is consecutive, and the stride of the compact run
+ * tables, which kernel the fp64 general-G apply launches).  They are set-up calls: not stream-asynchronous, and NOT legal inside a hipGraph
  * stream capture (they return a HIP error there) -- build every plan before capturing (the Python side's StepGraphMixin warms its
  * plans first).
+ *
+ * WORKSPACE SIZE: always ask fus_plan_bytes / fus_stiffness_plan_bytes of THIS library.  A cell plan (N = n^3) also holds one 16-bit slot per
+ * local row of each cell and a second, compact copy of its run tables (what the fp64 general-G apply reads when every row of every cell is
+ * n consecutive dof numbers, as in any structured numbering; FUS_TUNE_PLAN_ROWS): P = 4 about 1 020 bytes per cell instead of 870.  The
+ * lists, run tables, slots and cell order are where they were; the exclusive-dof marks are still the last region.  An addition: the entry points and their meaning are unchanged, FUS_ABI_VERSION stays.
  */
 int fus_plan_entities_per_batch(int ndof_per_entity);
 int64_t fus_plan_bytes(int ndof_per_entity, int entities_per_batch, int64_t nent);

@@ -130,7 +130,7 @@ for a_ in sys.argv[3:]:
         for sub, name in (("pmc_fetch", "fetch"), ("pmc_write", "write")):
             pth = os.path.join(src, sub, f"{name}_counter_collection.csv")
             for r in csv.DictReader(open(pth)):
-                for kn in ("stiffness_plan_geom_kernel", "stiffness_plan_kernel", "westervelt_cell_geom_kernel", "westervelt_cell_kernel",
+                for kn in ("stiffness_plan_geom_kernel", "stiffness_plan_rows_kernel", "stiffness_plan_kernel", "westervelt_cell_geom_kernel", "westervelt_cell_kernel",
                            "facet_terms_kernel", "rk4_stage_nl2_kernel", "rk4_stage_kernel"):
                     if kn + "<" in r["Kernel_Name"] or r["Kernel_Name"].split("(")[0].endswith(kn):
                         per.setdefault(kn, {}).setdefault(r["Counter_Name"], []).append(float(r["Counter_Value"]))
