@@ -128,6 +128,7 @@ TUNE_PLAN_VARIANT = 4
 TUNE_PLAN_RUNS = 5
 TUNE_VECTOR_STREAM = 6
 TUNE_PLAN_ROWS = 7  # fp64 general-G apply: 1 (default) one slot per local row + compact run tables where the plan allows, 0 never
+TUNE_PLAN_XCD_GROUP = 8  # general-G planned apply: g consecutive batches per XCD label; -1 auto (default), 0 off, 2 .. 256 (a power of two) = g
 
 ABI_VERSION = 3  # include/fus_gpu.h FUS_ABI_VERSION
 

@@ -38,14 +38,31 @@ hipError_t launch_plan_rows_auto(const T* x, const T* cc, T* y, const T* G, cons
         x, cc, y, G, ws, dphi, ncell, remap, s, ord, run_stride);
 }
 
+// Group size of the batch placement (stiffness.hpp: group_block) for degree P: the knob, or in auto the size measured per degree and
+// scalar type at ~10 M dofs with tools/ab_xcd_group.py (profiles/ab_xcd_group.log: three runs on MI355X boxes, the arms alternating in one
+// process).  A degree has a size only where that size passed the bar of docs/history.md 3.2 (median below the natural order's by more
+// than three times the larger spread) in at least two of the three runs and was slower in none: fp64 P = 4 g = 32 (+0.5 / +1.5 ... 1.8 /
+// +1.1 ... 1.8 %), fp64 P = 8 g = 16 (+1.3 ... 1.5 %), fp32 P = 3 g = 16 (+2.3 ... 2.5 %).  0 = natural order: fp64 P = 3, 5 gain 0.4 ... 1.9 %
+// with g = 32 but pass in one run only, P = 2, 6, 7 gain nothing or lose from g = 16 up, the other fp32 degrees stay inside the bar.
+template <typename T, int P>
+int plan_xcd_group() {
+  const int g = g_plan_xcd_group.load(std::memory_order_relaxed);
+  if (g >= 0) return g;
+  constexpr int auto_f64[11] = {0, 0, 0, 0, 32, 0, 0, 0, 16, 0, 0};
+  constexpr int auto_f32[11] = {0, 0, 0, 16, 0, 0, 0, 0, 0, 0, 0};
+  return sizeof(T) == 8 ? auto_f64[P] : auto_f32[P];
+}
+
 template <typename T>
 int stiffness_apply_planned(const T* x, const T* cc, T* y, const T* G, const void* ws, const T* dphi, int P,
                             int64_t ncell, void* stream) {
   const bool args_ok = x && cc && y && G && dphi && !misaligned(G, 2 * sizeof(T));
   hipStream_t s = static_cast<hipStream_t>(stream);
-  const int remap = g_xcd_remap.load(std::memory_order_relaxed);
+  const int chunks = g_xcd_remap.load(std::memory_order_relaxed);
   return planned_cell_entry<T>(args_ok, ws, P, ncell, [&](auto p, bool ord, bool runs) {
     constexpr int PP = decltype(p)::value;
+    // placement of the batches on the XCDs, carried in the kernels' xcd_remap argument (stiffness.hpp: place_batch)
+    const int remap = chunks ? 1 : plan_xcd_group<T, PP>();
     // Builds (profiles/r01d_ab_alias_by_degree.log, r02*_ab_*.log; pinned by tests/test_resource_usage.py):
     //   0  three LDS cubes + own x/y buffer           (P <= 3)
     //   1  LDS-aliased, whole G slab issued up front  (P = 4, 5: 4 workgroups per CU at P = 4)

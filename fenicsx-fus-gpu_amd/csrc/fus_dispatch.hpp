@@ -14,7 +14,10 @@
 namespace fus_abi {
 
 inline std::atomic<int> g_stiffness_variant{0};
-inline std::atomic<int> g_xcd_remap{0};  // measured slower on MI355X (profiles/r01b_ab_variants.log)
+// 1 = every XCD walks one contiguous eighth of the batches (plan-free kernel and the two general-G planned kernels).  Slower on MI355X:
+// it does cut the x re-fetches (fetch bytes 1147.5 -> 1064.1 MB per launch at config 3) and is still 11 % slower, 245.9 against 221.9 us
+// (profiles/xcd_group_probe.log; 0.2582 against 0.2313 ms on the first planned kernel, profiles/r01b_ab_variants.log)
+inline std::atomic<int> g_xcd_remap{0};
 inline std::atomic<int> g_mass_variant{0};
 inline std::atomic<int> g_plan_runs{1};  // 0 never, 1 auto, 2 always
 
@@ -41,6 +44,10 @@ inline std::atomic<int> g_plan_variant{-1};  // -1 = auto
 // fp64 general-G apply: 1 (default) = a run-coded launch of a plan whose rows are all consecutive reads one slot per local ROW and the
 // compact run tables (stiffness_plan_rows_kernel); 0 = never (the A/B knob: the launch then runs stiffness_plan_kernel)
 inline std::atomic<int> g_plan_rows{1};
+// general-G planned apply, both kernels: g consecutive batches per XCD label (stiffness.hpp: group_block).  -1 = auto (the table in
+// stiffness_apply_planned), 0 = off, a power of two from 2 to 256 = g.  g_xcd_remap = 1 wins over it.
+inline std::atomic<int> g_plan_xcd_group{-1};
+inline bool plan_xcd_group_valid(int v) { return v == -1 || v == 0 || (v >= 2 && v <= 256 && (v & (v - 1)) == 0); }
 
 // The one workspace registry of the library (plan_registry.hpp) is defined in fus_gpu.hip, where the header type of the gather plans is
 // complete.  true if ``ws`` holds a batch plan for exactly this shape; ``ordered`` out

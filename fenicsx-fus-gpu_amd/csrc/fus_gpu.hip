@@ -368,6 +368,10 @@ int fus_set_tuning(int key, int value) {
     case FUS_TUNE_PLAN_VARIANT: g_plan_variant = value; return FUS_OK;
     case FUS_TUNE_PLAN_RUNS: g_plan_runs = value; return FUS_OK;
     case FUS_TUNE_PLAN_ROWS: g_plan_rows = value ? 1 : 0; return FUS_OK;
+    case FUS_TUNE_PLAN_XCD_GROUP:
+      if (!plan_xcd_group_valid(value)) return FUS_ERR_INVALID_ARGUMENT;
+      g_plan_xcd_group = value;
+      return FUS_OK;
     case FUS_TUNE_VECTOR_STREAM:
       if (value < 0 || value > 4) return FUS_ERR_INVALID_ARGUMENT;
       fus::vector_stream_mode() = value;
@@ -384,6 +388,7 @@ int fus_get_tuning(int key) {
     case FUS_TUNE_PLAN_VARIANT: return g_plan_variant;
     case FUS_TUNE_PLAN_RUNS: return g_plan_runs;
     case FUS_TUNE_PLAN_ROWS: return g_plan_rows;
+    case FUS_TUNE_PLAN_XCD_GROUP: return g_plan_xcd_group;
     case FUS_TUNE_VECTOR_STREAM: return fus::vector_stream_mode();
   }
   return FUS_ERR_INVALID_ARGUMENT;

@@ -110,6 +110,26 @@ __device__ __forceinline__ unsigned remap_block(unsigned bid, unsigned nblocks, 
   return xcd * per + (xcd < rem ? xcd : rem) + idx;
 }
 
+// Block index -> batch index in groups: of the blocks that share an XCD (label bid % 8), g = 2^s consecutive ones get g consecutive
+// batches, and the eight groups of one round of g blocks per XCD tile a window of 8 g batches ("super-group").  Neighbouring batches
+// share dofs of x (a run end, a face), so they meet in one L2, while the chip as a whole still reads ONE front of G moving through the
+// array (with remap_block's contiguous eighths it reads eight, far apart).  The blocks behind the last whole super-group keep their
+// natural place: a bijection for every nblocks; g = 0, 1 and any g with 8 g > nblocks are the natural order.  Shifts and masks only.
+__host__ __device__ __forceinline__ unsigned group_block(unsigned bid, unsigned nblocks, int g) {
+  if (g < 2) return bid;
+  const unsigned s = (unsigned)__builtin_ctz((unsigned)g);
+  const unsigned full = nblocks & ~((8u << s) - 1u);  // whole super-groups
+  if (bid >= full) return bid;
+  const unsigned m = bid >> 3, k = bid & 7u;
+  return ((m >> s) << (3 + s)) + (k << s) + (m & ((1u << s) - 1u));
+}
+
+// The planned general-G kernels carry the placement in their ``xcd_remap`` argument: 0 natural, 1 remap_block's contiguous eighths,
+// a power of two from 2 = group_block's g.
+__device__ __forceinline__ unsigned place_batch(unsigned bid, unsigned nblocks, int xcd_remap) {
+  return xcd_remap == 1 ? remap_block(bid, nblocks, 1) : group_block(bid, nblocks, xcd_remap);
+}
+
 template <typename T, int P, int CPB>
 __global__ void __launch_bounds__((col_block_threads<P, CPB>()))
     stiffness_col_kernel(const T* __restrict__ x, const T* __restrict__ cell_constants, T* __restrict__ y,

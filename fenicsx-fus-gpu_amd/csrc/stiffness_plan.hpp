@@ -196,7 +196,7 @@ __global__ void __launch_bounds__((col_block_threads<P, CPB>()), MINW)
   PlanAcc* const sy = PlanOwnAcc<T, ALIAS>::value ? sacc : reinterpret_cast<PlanAcc*>(su);  // their y partial sums
 
   const int tid = threadIdx.x;
-  const unsigned batch = remap_block(blockIdx.x, gridDim.x, xcd_remap);
+  const unsigned batch = place_batch(blockIdx.x, gridDim.x, xcd_remap);  // stiffness.hpp: natural, eighths or groups
   const int lc = tid / n2;
   const int t = tid - lc * n2;
   const int ty = t / n, tz = t - ty * n;
@@ -337,7 +337,7 @@ __global__ void __launch_bounds__((col_block_threads<P, CPB>()), MINW)
   PlanAcc* const sy = PlanOwnAcc<T, ALIAS>::value ? sacc : reinterpret_cast<PlanAcc*>(su);  // their y partial sums
 
   const int tid = threadIdx.x;
-  const unsigned batch = remap_block(blockIdx.x, gridDim.x, xcd_remap);
+  const unsigned batch = place_batch(blockIdx.x, gridDim.x, xcd_remap);  // stiffness.hpp: natural, eighths or groups
   const int lc = tid / n2;
   const int t = tid - lc * n2;
   const int ty = t / n, tz = t - ty * n;
