@@ -15,9 +15,10 @@ import numpy as np
 ROOT = os.path.abspath(os.path.join(os.path.dirname(__file__), ".."))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
+sys.path.insert(0, os.path.join(ROOT, "tools"))
 
 
-def main():
+def main(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--degree", type=int, default=4)
     ap.add_argument("--cells", type=int, default=54)
@@ -26,10 +27,11 @@ def main():
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--order", default="lex", choices=["lex", "random"])
     ap.add_argument("--variants", default="0", help="builds of the gather kernel to compare (FUS_TUNE_MASS_VARIANT: rows per thread 1, 2, 4; 0 = chosen by size and type)")
-    a = ap.parse_args()
+    a = ap.parse_args(argv)
     import torch
 
     import fusgpu_loader
+    import measure
     from conftest import build_problem
 
     lib = fusgpu_loader.submodule("_lib")
@@ -105,34 +107,24 @@ def main():
         np.add.at(ref, dmh.reshape(-1), (xh[dmh] * dJ * cch[:, None]).reshape(-1))
         print(f"gather vs numpy add.at: max abs diff {np.abs(yb.cpu().numpy() - ref).max():.3e} (ref max {np.abs(ref).max():.3e})")
 
-    def timeit(fn, y):
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        for _ in range(a.reps):
-            fn(y)
-        e1.record()
-        torch.cuda.synchronize()
-        return e0.elapsed_time(e1) / a.reps
+    def tuned(v):
+        return lambda: lib.set_tuning(lib.TUNE_MASS_VARIANT, v)
 
     variants = [int(v) for v in a.variants.split(",")]
-    res = {"plan": []}
-    res.update({f"gather:{v}": [] for v in variants})
-    if sws is not None:
-        res.update({f"static:{v}": [] for v in variants})
-    for fn in (plan, gather):
-        timeit(fn, ya)
-    for _ in range(a.rounds):
-        res["plan"].append(timeit(plan, ya))
-        for v in variants:
-            lib.set_tuning(lib.TUNE_MASS_VARIANT, v)
-            res[f"gather:{v}"].append(timeit(gather, yb))
-            if sws is not None:
-                res[f"static:{v}"].append(timeit(static, yc))
-        lib.set_tuning(lib.TUNE_MASS_VARIANT, 0)
+    arms = {"plan": (tuned(0), lambda: plan(ya))}
+    for v in variants:  # a round runs plan, then gather and static of each variant in turn
+        arms[f"gather:{v}"] = (tuned(v), lambda: gather(yb))
+        if sws is not None:
+            arms[f"static:{v}"] = (tuned(v), lambda: static(yc))
+    res = measure.interleave(arms, a.rounds, lambda fn: measure.event_time(fn, a.reps), warm=a.reps)
+    lib.set_tuning(lib.TUNE_MASS_VARIANT, 0)
+    res = {k: res[k] for k in sorted(res, key=lambda k: ("plan", "gather", "static").index(k.partition(":")[0]))}  # printed kind by kind
     for k, v in res.items():
-        med = float(np.median(v))
-        print(f"{k:9s}: median {med:.4f} ms  min {min(v):.4f} ms  {alg / med / 1e6:7.0f} GB/s algorithmic ({100 * alg / med / 1e6 / 8000:.1f} % of 8 TB/s)  "
+        med, lo = measure.stats(v).median, measure.stats(v).min
+        print(f"{k:9s}: median {med:.4f} ms  min {lo:.4f} ms  {alg / med / 1e6:7.0f} GB/s algorithmic ({100 * alg / med / 1e6 / 8000:.1f} % of 8 TB/s)  "
               f"{nd / med / 1e6:.2f} GDOF/s")
+    for line in measure.verdict_lines(res, to_us=1e3):
+        print(line)
 
 
 if __name__ == "__main__":

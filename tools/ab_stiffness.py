@@ -23,9 +23,10 @@ import numpy as np
 ROOT = os.path.abspath(os.path.join(os.path.dirname(__file__), ".."))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
+sys.path.insert(0, os.path.join(ROOT, "tools"))
 
 
-def main():
+def main(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--cells", type=int, default=54)
     ap.add_argument("--degree", type=int, default=4)
@@ -35,11 +36,12 @@ def main():
     ap.add_argument("--isolated", action="store_true", help="one event pair per launch (launches cannot overlap at their tails)")
     ap.add_argument("--order", default="lex", choices=["lex", "random", "morton"], help="cell order of the dofmap")
     ap.add_argument("configs", nargs="*", default=["plan", "plan:0", "plan:1", "plan:2"])
-    a = ap.parse_args()
+    a = ap.parse_args(argv)
     import torch
 
     import bench
     import fusgpu_loader
+    import measure
     from conftest import build_problem
 
     lib = fusgpu_loader.submodule("_lib")
@@ -71,51 +73,38 @@ def main():
         kind, _, k = c.partition(":")
         return kind, int(k) if k else -1, remap
 
-    cfgs = [parse(c) for c in a.configs]
-    times = {c: [] for c in a.configs}
-    for rnd in range(a.rounds + 1):
-        for name, (kind, k, remap) in zip(a.configs, cfgs):
+    def arm(kind, k, remap):
+        def select():
             lib.set_tuning(lib.TUNE_XCD_REMAP, int(remap))
             ops.use_plan(kind != "col")
-            fn, d_ = op, dm
             if kind == "col":
                 lib.set_tuning(lib.TUNE_STIFFNESS_VARIANT, max(k, 0))
-            elif kind == "geom":
-                fn = opg
-                lib.set_tuning(lib.TUNE_PLAN_VARIANT, k)  # geom:50 / geom:51: the flux formed in the main loop for P <= 5 too (dispatch_geometry.hip)
-            else:
+            else:  # geom:50 / geom:51: the flux formed in the main loop for P <= 5 too (dispatch_geometry.hip)
                 lib.set_tuning(lib.TUNE_PLAN_VARIANT, k)
             lib.set_tuning(lib.TUNE_PLAN_RUNS, {"raw": 0, "runs": 2}.get(kind, 1))
-            fn(x, cc, y, G, d_)
-            if a.isolated:
-                evs = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(a.reps)]
-                for e0, e1 in evs:
-                    e0.record()
-                    fn(x, cc, y, G, d_)
-                    e1.record()
-                torch.cuda.synchronize()
-                tms = float(np.mean([e0.elapsed_time(e1) for e0, e1 in evs]))
-            else:
-                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                e0.record()
-                for _ in range(a.reps):
-                    fn(x, cc, y, G, d_)
-                e1.record()
-                torch.cuda.synchronize()
-                tms = e0.elapsed_time(e1) / a.reps
-            if rnd > 0:
-                times[name].append(tms)
+
+        fn = opg if kind == "geom" else op
+        return select, lambda: fn(x, cc, y, G, dm)
+
+    arms = {(i, c): arm(*parse(c)) for i, c in enumerate(a.configs)}  # a cfg named twice is timed twice, into one list
+    event_time = measure.event_time_isolated if a.isolated else measure.event_time
+    # one untimed launch ahead of each timed region; the first round of every arm is not kept
+    times = {c: [] for c in a.configs}
+    for (_, c), v in measure.interleave(arms, a.rounds + 1, lambda fn: event_time(fn, a.reps, warm=1)).items():
+        times[c] += v[1:]
     lib.set_tuning(lib.TUNE_PLAN_VARIANT, -1)
     lib.set_tuning(lib.TUNE_PLAN_RUNS, 1)
     bpc = bench.stiffness_bytes_per_cell(a.degree, np.dtype(dt).itemsize)
     print(f"P={a.degree} cells={a.cells}^3 dtype={a.dtype} order={a.order} dofs={mesh.ndofs} lib={lib.LIB_PATH} "
           f"timing={'isolated launches' if a.isolated else 'back-to-back launches'}")
-    for name in a.configs:
-        t = np.array(times[name])
-        gbs = mesh.ncells * bpc / (np.median(t) * 1e-3) / 1e9
-        print(f"{name:12s}: median {np.median(t):.4f} ms  min {t.min():.4f} ms  {gbs:.0f} GB/s of general-G bytes "
-              f"({100 * gbs / 8000:.1f}% of 8 TB/s)  {mesh.ndofs / np.median(t) / 1e6:.2f} GDOF/s")
+    for name, t in times.items():
+        st = measure.stats(t)
+        gbs = mesh.ncells * bpc / (st.median * 1e-3) / 1e9
+        print(f"{name:12s}: median {st.median:.4f} ms  min {st.min:.4f} ms  {gbs:.0f} GB/s of general-G bytes "
+              f"({100 * gbs / 8000:.1f}% of 8 TB/s)  {mesh.ndofs / st.median / 1e6:.2f} GDOF/s")
         print(f"{'':12s}  rounds: " + " ".join(f"{v:.4f}" for v in t))
+    for line in measure.verdict_lines(times, to_us=1e3):
+        print(line)
 
 
 if __name__ == "__main__":

@@ -5,24 +5,25 @@ general G array and with G formed in the kernel -- alternating rounds in one pro
 import argparse
 import os
 import sys
-import time
 
 import numpy as np
 
 ROOT = os.path.abspath(os.path.join(os.path.dirname(__file__), ".."))
 sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tools"))
 
 
-def main():
+def main(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--cells", type=int, default=36)
     ap.add_argument("--degree", type=int, default=6)  # (config 3's shape: --degree 4 --cells 54)
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--rounds", type=int, default=4)
-    a = ap.parse_args()
+    a = ap.parse_args(argv)
     import torch
 
     import fusgpu_loader
+    import measure
 
     torch.cuda.set_device(0)
     boxmesh, ls, nls = (fusgpu_loader.submodule(m) for m in ("boxmesh", "linear_solver", "nonlinear_solver"))
@@ -45,18 +46,20 @@ def main():
             s.init()
             s.rk4(0.0, tf, dt, max_steps=3)
             variants[f"{'in-kernel geometry' if geo else 'general G'}, {'two gathers' if two else 'single gather (w = u + kappa v)'}"] = s
-    res = {k: [] for k in variants}
-    t = 3 * dt
-    for _ in range(a.rounds):
-        for k, s in variants.items():
-            torch.cuda.synchronize()
-            t0 = time.perf_counter()
-            s.rk4(t, tf, dt, max_steps=a.steps)
-            torch.cuda.synchronize()
-            res[k].append((time.perf_counter() - t0) / a.steps * 1e3)
-        t += a.steps * dt
+
+    def steps(s, t=3 * dt):  # every solver goes on from where its last round ended
+        def run():
+            nonlocal t
+            t, _ = s.rk4(t, tf, dt, max_steps=a.steps)
+
+        return run
+
+    arms = {k: steps(s) for k, s in variants.items()}
+    res = measure.interleave(arms, a.rounds, lambda fn: measure.host_time(fn, a.steps))
     for k, v in res.items():
-        print(f"P={P} {a.cells}^3 cells  {k:58s} {np.median(v):.4f} ms/step   rounds {' '.join(f'{x:.4f}' for x in v)}", flush=True)
+        print(f"P={P} {a.cells}^3 cells  {k:58s} {measure.stats(v).median:.4f} ms/step   rounds {' '.join(f'{x:.4f}' for x in v)}", flush=True)
+    for line in measure.verdict_lines(res, to_us=1e3):
+        print(line, flush=True)
 
 
 if __name__ == "__main__":

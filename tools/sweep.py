@@ -10,6 +10,7 @@ import numpy as np
 ROOT = os.path.abspath(os.path.join(os.path.dirname(__file__), ".."))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
+sys.path.insert(0, os.path.join(ROOT, "tools"))
 
 
 def mass_bytes_per_cell(P, T):
@@ -17,32 +18,26 @@ def mass_bytes_per_cell(P, T):
     return n**3 * T + 4 * n**3 + 3 * T * P**3 + T
 
 
-def main():
+def main(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--dofs", type=float, default=10e6)
     ap.add_argument("--degrees", default="2,3,4,5,6,8")
     ap.add_argument("--dtypes", default="f64,f32")
     ap.add_argument("--reps", type=int, default=100)
     ap.add_argument("--affine", action="store_true")
-    a = ap.parse_args()
+    a = ap.parse_args(argv)
     import torch
 
     import bench
     import fusgpu_loader
+    import measure
     from conftest import build_problem
 
     ops = fusgpu_loader.submodule("operators")
     dev = torch.device("cuda", 0)
 
-    def timeit(fn):
-        fn()
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        for _ in range(a.reps):
-            fn()
-        e1.record()
-        torch.cuda.synchronize()
-        return e0.elapsed_time(e1) / a.reps
+    def timeit(fn, warm=1):
+        return measure.event_time(fn, a.reps, warm=warm)
 
     for P in [int(v) for v in a.degrees.split(",")]:
         N = max(2, int(round((a.dofs ** (1 / 3) - 1) / P)))
@@ -76,9 +71,8 @@ def main():
             gll = fusgpu_loader.submodule("gll")
             pts1, wts1 = gll.gll_points_weights(P)
             opg = ops.stiffness_operator(P, pb["D"].flatten(), dt, geometry=(mesh.x_dofs, mesh.x_g, pts1, wts1))
-            for _ in range(100):  # the in-kernel-geometry kernel needs the steady state (profiles/r05d_geom_variance_probe.log)
-                opg(x, cc, y, None, dm)
-            t = timeit(lambda: opg(x, cc, y, None, dm))
+            # the in-kernel-geometry kernel needs the steady state (profiles/r05d_geom_variance_probe.log): 100 launches more
+            t = timeit(lambda: opg(x, cc, y, None, dm), warm=1 + 100)
             gbs = mesh.ncells * bench.geom_bytes_per_cell(P, T) / (t * 1e-3) / 1e9
             res.append(f"K[in-kernel geometry] {t:.4f} ms {mesh.ndofs / t / 1e6:6.2f} GDOF/s {100 * gbs / 8000:5.1f}% of its own contract")
             mops = ops.mass_operator((P + 1) ** 3, dt, static_detJ=True)

@@ -13,47 +13,37 @@ Times: HIP events around back-to-back launches (a); wall clock around synchronis
 import argparse
 import os
 import sys
-import time
 
 import numpy as np
 
 ROOT = os.path.abspath(os.path.join(os.path.dirname(__file__), ".."))
 sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tools"))
+import measure  # noqa: E402  (no torch at its module level)
 
 N_DOFS = 217**3
 # vector touches per dof with pr and s on (LAST: + cem43 read and written as doubles, tmax read and written)
 TOUCHES = {"FIRST": (5 + 3, 0), "MIDDLE": (7 + 3, 0), "LAST": (6 + 2 + 2, 2)}  # (of the field type, of double)
 
 
-def main():
+def main(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--parts", default="ab")
     ap.add_argument("--log", default=os.path.join(ROOT, "profiles", "time_bioheat.log"))
     ap.add_argument("--rounds", type=int, default=5)
-    a = ap.parse_args()
-    lines = []
+    a = ap.parse_args(argv)
+    with measure.Log("time_bioheat", a.log) as log:
+        run(a, log)
 
-    def log(s):
-        print(s, flush=True)
-        lines.append(s)
 
+def run(a, log):
     import torch
 
     import fusgpu_loader
 
     torch.cuda.set_device(0)
     boxmesh, ls, bh, lib = (fusgpu_loader.submodule(m) for m in ("boxmesh", "linear_solver", "bioheat", "_lib"))
-    log(f"# tools/time_bioheat.py on {torch.cuda.get_device_name(0)}, {time.strftime('%Y-%m-%d %H:%M:%S')}")
-
-    def ev_time(fn, reps):
-        s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        torch.cuda.synchronize()
-        s.record()
-        for _ in range(reps):
-            fn()
-        e.record()
-        e.synchronize()
-        return s.elapsed_time(e) / reps
+    log.header()
 
     if "a" in a.parts:
         log(f"(a) one stage launch over {N_DOFS} dofs: event pair around 200 launches after 100 untimed, median of {a.rounds} rounds, "
@@ -77,20 +67,13 @@ def main():
             for kind, name in enumerate(("FIRST", "MIDDLE", "LAST")):
                 nt, nd = TOUCHES[name]
                 cases.append((f"bioheat {name}", N_DOFS * (nt * ts + nd * 8), lambda kind=kind: bioheat_pass(kind)))
-            res = {name: [] for name, _, _ in cases}
-            for _, _, one in cases:
-                for _ in range(100):
-                    one()
-            for _ in range(a.rounds):
-                for name, _, one in cases:
-                    res[name].append(ev_time(one, 200))
+            res = measure.interleave({name: one for name, _, one in cases}, a.rounds, lambda fn: measure.event_time(fn, 200), warm=100)
             ref = None
             for name, nb, _ in cases:
-                ms = sorted(res[name])
-                med = ms[len(ms) // 2]
-                bw = nb / (med * 1e-3) / 1e12
+                st = measure.stats(res[name])
+                bw = nb / (st.median * 1e-3) / 1e12
                 ref = bw if ref is None else ref
-                log(f"  {np.dtype(dt_np).name} {name:16s} {med * 1e3:7.1f} us (min {ms[0] * 1e3:.1f}, max {ms[-1] * 1e3:.1f})  model {nb / 1e6:7.1f} MB"
+                log(f"  {np.dtype(dt_np).name} {name:16s} {st.median * 1e3:7.1f} us (min {st.min * 1e3:.1f}, max {st.max * 1e3:.1f})  model {nb / 1e6:7.1f} MB"
                     f"  {bw:.2f} TB/s  = {bw / ref:.3f} x the rk4 stage pass")
             del vec, cem, cases
             torch.cuda.empty_cache()
@@ -110,24 +93,21 @@ def main():
         log(f"  stable_time_step() = {dt_t:.4g} s (lambda_max {th.lambda_max:.4g} 1/s), wave dt = {dt_w:.4g} s")
         wave.rk4(0.0, 1.0, dt_w, max_steps=3)
         th.advance(0.0, 3 * dt_t, dt_t)
-        res, tw, tt = {"linear rk4_step": [], "bioheat step": []}, 3 * dt_w, 3 * dt_t
-        for _ in range(a.rounds):
-            torch.cuda.synchronize()
-            t0 = time.perf_counter()
+        tw, tt = 3 * dt_w, 3 * dt_t
+
+        def wave_steps():
+            nonlocal tw
             tw, _ = wave.rk4(tw, 1.0, dt_w, max_steps=K)
-            torch.cuda.synchronize()
-            res["linear rk4_step"].append((time.perf_counter() - t0) / K * 1e3)
-            t0 = time.perf_counter()
+
+        def thermal_steps():
+            nonlocal tt
             tt, _ = th.advance(tt, 1e9, dt_t, max_steps=K)
-            torch.cuda.synchronize()
-            res["bioheat step"].append((time.perf_counter() - t0) / K * 1e3)
-        base = np.median(res["linear rk4_step"])
+
+        res = measure.interleave({"linear rk4_step": wave_steps, "bioheat step": thermal_steps}, a.rounds, lambda fn: measure.host_time(fn, K))
+        base = measure.stats(res["linear rk4_step"]).median
         for kind, v in res.items():
-            log(f"  {kind:16s} {np.median(v):.3f} ms/step  (rounds {', '.join(f'{x:.3f}' for x in v)})  -> {np.median(v) / base:.3f} x the linear step")
-    if a.log:
-        os.makedirs(os.path.dirname(os.path.abspath(a.log)), exist_ok=True)
-        with open(a.log, "a") as f:
-            f.write("\n".join(lines) + "\n")
+            med = measure.stats(v).median
+            log(f"  {kind:16s} {med:.3f} ms/step  (rounds {', '.join(f'{x:.3f}' for x in v)})  -> {med / base:.3f} x the linear step")
 
 
 if __name__ == "__main__":

@@ -20,12 +20,13 @@ import csv
 import glob
 import os
 import sys
-import time
 
 import numpy as np
 
 ROOT = os.path.abspath(os.path.join(os.path.dirname(__file__), ".."))
 sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tools"))
+import measure  # noqa: E402  (no torch at its module level)
 
 N_DOFS = 217**3
 VARIANTS = (("peak", dict(peak=True)),
@@ -56,35 +57,26 @@ def pmc_summary(pmc_dir, log):
                 per.setdefault(r["Kernel_Name"].split("(")[0], {}).setdefault(r["Counter_Name"], []).append(float(r["Counter_Value"]))
     log(f"(p) HBM bytes per launch from {os.path.basename(os.path.normpath(pmc_dir))}: (2 FETCH_SIZE + WRITE_SIZE) x 1024, n = {N_DOFS}")
     for k, c in sorted(per.items()):
-        fetch, write = np.median(c.get("FETCH_SIZE", [np.nan])), np.median(c.get("WRITE_SIZE", [np.nan]))
+        fetch, write = (measure.stats(c.get(counter, [np.nan])).median for counter in ("FETCH_SIZE", "WRITE_SIZE"))
         log(f"  {k.replace('void fus::', '')}: {len(c.get('FETCH_SIZE', []))} launches, read {2 * fetch * 1024 / 1e6:.1f} MB, "
             f"written {write * 1024 / 1e6:.1f} MB, total {(2 * fetch + write) * 1024 / 1e6:.1f} MB")
 
 
-def main():
+def main(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--parts", default="abc")
     ap.add_argument("--log", default=os.path.join(ROOT, "profiles", "time_field_monitor.log"))
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--pmc-dir", default=None)
-    a = ap.parse_args()
-    lines = []
+    a = ap.parse_args(argv)
+    with measure.Log("time_field_monitor", a.log) as log:
+        if a.pmc_dir:
+            pmc_summary(a.pmc_dir, log)
+        if a.parts:
+            run(a, log)
 
-    def log(s):
-        print(s, flush=True)
-        lines.append(s)
 
-    def finish():
-        if a.log:
-            os.makedirs(os.path.dirname(os.path.abspath(a.log)), exist_ok=True)
-            with open(a.log, "a") as f:
-                f.write("\n".join(lines) + "\n")
-
-    if a.pmc_dir:
-        pmc_summary(a.pmc_dir, log)
-    if not a.parts:
-        finish()
-        return
+def run(a, log):
     import torch
 
     import fusgpu_loader
@@ -92,18 +84,8 @@ def main():
     torch.cuda.set_device(0)
     boxmesh, ls, nls, fm, lib, sens = (fusgpu_loader.submodule(m) for m in ("boxmesh", "linear_solver", "nonlinear_solver", "field_monitor",
                                                                              "_lib", "sensors"))
-    log(f"# tools/time_field_monitor.py on {torch.cuda.get_device_name(0)}, {time.strftime('%Y-%m-%d %H:%M:%S')}")
+    log.header()
     L = 0.12
-
-    def ev_time(fn, reps):
-        s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        torch.cuda.synchronize()
-        s.record()
-        for _ in range(reps):
-            fn()
-        e.record()
-        e.synchronize()
-        return s.elapsed_time(e) / reps
 
     def launches(dt_np):
         """[(name, model bytes, callable)] of the monitor variants on random fields of N_DOFS values."""
@@ -145,35 +127,26 @@ def main():
                 lib.check(stage(1e-9, 1e-9, 0, *(x.data_ptr() for x in vec), N_DOFS, N_DOFS, lib.stream_ptr()), "fus_rk4_stage")
 
             cases = [("rk4 stage pass", 12 * N_DOFS * ts, stage_pass)] + launches(dt_np)
-            res = {name: [] for name, _, _ in cases}
-            for name, _, one in cases:
-                for _ in range(100):
-                    one()
-            for _ in range(a.rounds):
-                for name, _, one in cases:
-                    res[name].append(ev_time(one, 200))
+            res = measure.interleave({name: one for name, _, one in cases}, a.rounds, lambda fn: measure.event_time(fn, 200), warm=100)
             ref = None
             for name, nb, _ in cases:
-                ms = sorted(res[name])
-                med = ms[len(ms) // 2]
-                bw = nb / (med * 1e-3) / 1e12
+                st = measure.stats(res[name])
+                bw = nb / (st.median * 1e-3) / 1e12
                 ref = bw if ref is None else ref
-                log(f"  {np.dtype(dt_np).name} {name:30s} {med * 1e3:7.1f} us (min {ms[0] * 1e3:.1f}, max {ms[-1] * 1e3:.1f})  model {nb / 1e6:7.1f} MB"
+                log(f"  {np.dtype(dt_np).name} {name:30s} {st.median * 1e3:7.1f} us (min {st.min * 1e3:.1f}, max {st.max * 1e3:.1f})  model {nb / 1e6:7.1f} MB"
                     f"  {bw:.2f} TB/s  = {bw / ref:.3f} x the stage pass")
             del vec, cases
             torch.cuda.empty_cache()
 
     def step_rounds(solver, dt, monitor, K, rounds, t):
-        res = {"plain": [], "monitor": []}
-        for _ in range(rounds):
-            for kind in res:
-                monitor.reset()
-                torch.cuda.synchronize()
-                t0 = time.perf_counter()
-                t, _ = solver.rk4(t, 1.0, dt, max_steps=K, monitor=monitor if kind == "monitor" else None)
-                torch.cuda.synchronize()
-                res[kind].append((time.perf_counter() - t0) / K * 1e3)
-        return res, t
+        def steps(m):
+            def go():
+                nonlocal t
+                t, _ = solver.rk4(t, 1.0, dt, max_steps=K, monitor=m)
+
+            return monitor.reset, go
+
+        return measure.interleave({"plain": steps(None), "monitor": steps(monitor)}, rounds, lambda fn: measure.host_time(fn, K)), t
 
     if "b" in a.parts:
         K = 20
@@ -188,10 +161,11 @@ def main():
             m = fm.FieldMonitor(solver.nlocal, np.float64, peak=True, mean_square=("u", "v"), harmonics=(1, 2), frequency=f0)
             solver.rk4(0.0, 1.0, dt, max_steps=3)
             res, _ = step_rounds(solver, dt, m, K, a.rounds, 3 * dt)
-            mp, mw = np.median(res["plain"]), np.median(res["monitor"])
+            mp, mw = measure.stats(res["plain"]).median, measure.stats(res["monitor"]).median
             log(f"  {which:10s} plain   {mp:.3f} ms/step  (rounds {', '.join(f'{x:.3f}' for x in res['plain'])})")
             log(f"  {which:10s} monitor {mw:.3f} ms/step  (rounds {', '.join(f'{x:.3f}' for x in res['monitor'])})  -> {mw / mp:.4f} x, "
                 f"+{(mw - mp) * 1e3:.0f} us")
+            log(*measure.verdict_lines(res, to_us=1e3, indent=f"  {which:10s} "))
             del solver, m, mesh
             torch.cuda.empty_cache()
 
@@ -216,21 +190,22 @@ def main():
         m = fm.FieldMonitor(solver.nlocal, np.float64, peak=True, mean_square=("u", "v"), harmonics=(1, 2), frequency=1.1e6)
         solver.rk4(0.0, 1.0, dt, max_steps=3)
         res, t = step_rounds(solver, dt, m, W, a.rounds, 3 * dt)
-        res["host loop"] = []
-        for _ in range(2):  # the host loop leaves the device idle most of the time (its clocks drop): a block of its own, last
-            torch.cuda.synchronize()
-            t0 = time.perf_counter()
-            for _ in range(W):  # what a caller without a monitor does per step of the window to see the whole field
+
+        def host_loop():  # what a caller without a monitor does per step of the window to see the whole field
+            nonlocal t
+            for _ in range(W):
                 t, _ = solver.rk4(t, 1.0, dt, max_steps=1)
                 _ = solver.u_sol()
-            torch.cuda.synchronize()
-            res["host loop"].append((time.perf_counter() - t0) / W * 1e3)
-        base = np.median(res["plain"])
+
+        # the host loop leaves the device idle most of the time (its clocks drop): a block of its own, last
+        res.update(measure.interleave({"host loop": host_loop}, 2, lambda fn: measure.host_time(fn, W)))
+        med = {kind: measure.stats(v).median for kind, v in res.items()}
         for kind, v in res.items():
-            log(f"  {kind:10s} {np.median(v):.3f} ms/step  (rounds {', '.join(f'{x:.3f}' for x in v)})  -> {np.median(v) / base:.3f} x plain")
-        log(f"  host loop / monitor = {np.median(res['host loop']) / np.median(res['monitor']):.2f} x  "
+            log(f"  {kind:10s} {med[kind]:.3f} ms/step  (rounds {', '.join(f'{x:.3f}' for x in v)})  -> {med[kind] / med['plain']:.3f} x plain")
+        for line in measure.verdict_lines(res, to_us=1e3):
+            log(line)
+        log(f"  host loop / monitor = {med['host loop'] / med['monitor']:.2f} x  "
             f"(field: {mesh.nlocal * 8 / 1e6:.1f} MB per u_sol() copy; steps per period {spp})")
-    finish()
 
 
 if __name__ == "__main__":

@@ -20,12 +20,12 @@ at the same shape, although it issues 3 x the global atomics and far fewer fp64 
 import argparse
 import os
 import sys
-import time
 
 import numpy as np
 
 ROOT = os.path.abspath(os.path.join(os.path.dirname(__file__), ".."))
 sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tools"))
 
 
 def model_bytes(P, ncell, ndofs, ts, components):
@@ -33,79 +33,51 @@ def model_bytes(P, ncell, ndofs, ts, components):
     return ncell * (2 * Nd + 4 * Nd + 32 + ts + Nd * ts) + components * 2 * ts * ndofs
 
 
-def main():
+def main(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--configs", default="4:54,6:36", help="P:cells-per-direction, comma separated")
     ap.add_argument("--log", default=os.path.join(ROOT, "profiles", "time_gradient.log"))
     ap.add_argument("--rounds", type=int, default=5)
-    a = ap.parse_args()
-    lines = []
-
-    def log(s):
-        print(s, flush=True)
-        lines.append(s)
-
+    a = ap.parse_args(argv)
     import torch
 
     import fusgpu_loader
+    import measure
 
     torch.cuda.set_device(0)
-    boxmesh, gll, ops, lib = (fusgpu_loader.submodule(m) for m in ("boxmesh", "gll", "operators", "_lib"))
-    log(f"# tools/time_gradient.py on {torch.cuda.get_device_name(0)}, {time.strftime('%Y-%m-%d %H:%M:%S')}")
-    log(f"one launch, event pair around 200 launches after 100 untimed, median of {a.rounds} rounds, the two kernels alternating; "
-        "model: ncell (plan bytes + x read) + C y read-modify-write (see the tool's docstring)")
-
-    def ev_time(fn, reps):
-        s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        torch.cuda.synchronize()
-        s.record()
-        for _ in range(reps):
-            fn()
-        e.record()
-        e.synchronize()
-        return s.elapsed_time(e) / reps
-
-    for cfg in a.configs.split(","):
-        P, N = (int(v) for v in cfg.split(":"))
-        mesh = boxmesh.BoxMesh(P, N, perturb=0.16, seed=0)
-        dm = torch.from_numpy(np.ascontiguousarray(mesh.dofmap)).cuda()
-        for dt_np in (np.float64, np.float32):
-            ts = np.dtype(dt_np).itemsize
-            pts, wts, D = gll.tabulate_1d(P, dt_np)
-            geometry = (mesh.x_dofs, mesh.x_g, pts, wts)
-            tdt = lib.torch_dtype(dt_np)
-            x = torch.rand(mesh.ndofs, dtype=torch.float64, device="cuda").to(tdt)
-            cc = (0.5 + torch.rand(mesh.ncells, dtype=torch.float64, device="cuda")).to(tdt)
-            y = torch.zeros(mesh.ndofs, dtype=tdt, device="cuda")
-            y3 = torch.zeros((3, mesh.ndofs), dtype=tdt, device="cuda")
-            stiff = ops.stiffness_operator(P, D.flatten(), dt_np, geometry=geometry)
-            grad = ops.gradient_operator(P, D.flatten(), dt_np, geometry=geometry)
-            stiff.prepare(dm)
-            grad.prepare(dm)  # the same cache entry: one plan for both
-            cases = [("stiffness_plan_geom", 1, lambda: stiff(x, cc, y, None, dm)), ("gradient_plan_geom", 3, lambda: grad(x, cc, y3, dm))]
-            res = {name: [] for name, _, _ in cases}
-            for _, _, one in cases:
-                for _ in range(100):
-                    one()
-            for _ in range(a.rounds):
-                for name, _, one in cases:
-                    res[name].append(ev_time(one, 200))
-            base = None
-            for name, comps, _ in cases:
-                ms = sorted(res[name])
-                med = ms[len(ms) // 2]
-                nb = model_bytes(P, mesh.ncells, mesh.ndofs, ts, comps)
-                base = med if base is None else base
-                log(f"  P={P} {N}^3 {np.dtype(dt_np).name} {name:20s} {med * 1e3:7.1f} us (min {ms[0] * 1e3:.1f}, max {ms[-1] * 1e3:.1f})  "
-                    f"model {nb / 1e6:7.1f} MB  {nb / (med * 1e-3) / 1e12:.2f} TB/s  = {med / base:.3f} x the stiffness apply")
-            del x, cc, y, y3, stiff, grad, cases
-        ops._PLANS.clear()
-        del dm, mesh
-        torch.cuda.empty_cache()
-    if a.log:
-        os.makedirs(os.path.dirname(os.path.abspath(a.log)), exist_ok=True)
-        with open(a.log, "a") as f:
-            f.write("\n".join(lines) + "\n")
+    gll, ops, lib = (fusgpu_loader.submodule(m) for m in ("gll", "operators", "_lib"))
+    with measure.Log("time_gradient", a.log) as log:
+        log.header()
+        log(f"one launch, event pair around 200 launches after 100 untimed, median of {a.rounds} rounds, the two kernels alternating; "
+            "model: ncell (plan bytes + x read) + C y read-modify-write (see the tool's docstring)")
+        for cfg in a.configs.split(","):
+            P, N = (int(v) for v in cfg.split(":"))
+            pb = measure.device_problem(P, N, np.float64)
+            mesh, dm = pb.mesh, pb.dm
+            for dt_np in (np.float64, np.float32):
+                ts = np.dtype(dt_np).itemsize
+                pts, wts, D = gll.tabulate_1d(P, dt_np)
+                geometry = (mesh.x_dofs, mesh.x_g, pts, wts)
+                tdt = lib.torch_dtype(dt_np)
+                x, cc, y = pb.x.to(tdt), pb.cc.to(tdt), pb.y.to(tdt)
+                y3 = torch.zeros((3, mesh.ndofs), dtype=tdt, device="cuda")
+                stiff = ops.stiffness_operator(P, D.flatten(), dt_np, geometry=geometry)
+                grad = ops.gradient_operator(P, D.flatten(), dt_np, geometry=geometry)
+                stiff.prepare(dm)
+                grad.prepare(dm)  # the same cache entry: one plan for both
+                comps = {"stiffness_plan_geom": 1, "gradient_plan_geom": 3}
+                arms = {"stiffness_plan_geom": lambda: stiff(x, cc, y, None, dm), "gradient_plan_geom": lambda: grad(x, cc, y3, dm)}
+                res = measure.interleave(arms, a.rounds, lambda fn: measure.event_time(fn, 200), warm=100)
+                base = measure.stats(res["stiffness_plan_geom"]).median
+                for name, v in res.items():
+                    st = measure.stats(v)
+                    nb = model_bytes(P, mesh.ncells, mesh.ndofs, ts, comps[name])
+                    log(f"  P={P} {N}^3 {np.dtype(dt_np).name} {name:20s} {st.median * 1e3:7.1f} us (min {st.min * 1e3:.1f}, max {st.max * 1e3:.1f}, spread {st.spread * 1e3:.2f})  "
+                        f"model {nb / 1e6:7.1f} MB  {nb / (st.median * 1e-3) / 1e12:.2f} TB/s  = {st.median / base:.3f} x the stiffness apply")
+                del x, cc, y, y3, stiff, grad, arms
+            ops._PLANS.clear()
+            del dm, mesh, pb
+            torch.cuda.empty_cache()
 
 
 if __name__ == "__main__":

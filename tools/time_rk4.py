@@ -4,25 +4,26 @@ the reference's launch sequence vs the fused stage."""
 import argparse
 import os
 import sys
-import time
 
 import numpy as np
 
 ROOT = os.path.abspath(os.path.join(os.path.dirname(__file__), ".."))
 sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tools"))
 
 
-def main():
+def main(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--cells", type=int, default=54)
     ap.add_argument("--degree", type=int, default=4)
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--westervelt", action="store_true")
     ap.add_argument("--no-affine", action="store_true", help="general per-quadrature-point G even on the affine box")
-    a = ap.parse_args()
+    a = ap.parse_args(argv)
     import torch
 
     import fusgpu_loader
+    import measure
 
     torch.cuda.set_device(0)
     if os.environ.get("FUS_VECTOR_STREAM") is not None:  # A/B: non-temporal accesses in the vector kernels off (0) / auto (1) / always (2)
@@ -39,11 +40,7 @@ def main():
         s = nls.WesterveltSpectral3D(mesh, np.float64, fused=fused) if a.westervelt else ls.LinearSpectral3D(mesh, np.float64, fused=fused, affine=False if a.no_affine else "auto")
         s.init()
         s.rk4(0.0, tf, dt, max_steps=3)
-        torch.cuda.synchronize()
-        t0 = time.perf_counter()
-        s.rk4(3 * dt, tf, dt, max_steps=a.steps)
-        torch.cuda.synchronize()
-        el = (time.perf_counter() - t0) / a.steps
+        el = measure.host_time(lambda: s.rk4(3 * dt, tf, dt, max_steps=a.steps), a.steps) * 1e-3  # s per step
         print(f"{'fused' if fused else 'reference sequence'}: {el * 1e3:.3f} ms/step  "
               f"({mesh.ndofs / el / 1e9:.2f} GDOF-steps/s; full run of {nstep} steps = {el * nstep:.1f} s)", flush=True)
         del s

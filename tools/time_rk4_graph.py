@@ -4,22 +4,21 @@ where the launches, not the kernels, bound the step (small meshes) the graph rem
 import argparse
 import os
 import sys
-import time
 
 import numpy as np
 
 ROOT = os.path.abspath(os.path.join(os.path.dirname(__file__), ".."))
 sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tools"))
 
 
-def main():
+def main(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--cases", default="2:18,4:12,4:25,4:54", help="P:N,...")
     ap.add_argument("--steps", type=int, default=40)
-    a = ap.parse_args()
-    import torch
-
+    a = ap.parse_args(argv)
     import fusgpu_loader
+    import measure
 
     boxmesh, ls = fusgpu_loader.submodule("boxmesh"), fusgpu_loader.submodule("linear_solver")
     L = 0.12
@@ -35,11 +34,8 @@ def main():
             s.init()
             fn = getattr(s, name)
             t, _ = fn(0.0, tf, dt, max_steps=steps)  # warm-up (and capture)
-            torch.cuda.synchronize()
-            t0 = time.perf_counter()
-            t, done = fn(t, tf, dt, max_steps=steps)
-            torch.cuda.synchronize()
-            res[name] = (time.perf_counter() - t0) / done * 1e3
+            out = []  # (t, steps taken) of the timed call
+            res[name] = measure.host_time(lambda: out.append(fn(t, tf, dt, max_steps=steps))) / out[0][1]
         print(f"P={P} N={N} dofs={mesh.ndofs}: rk4 {res['rk4']:.4f} ms/step   rk4_graph {res['rk4_graph']:.4f} ms/step   "
               f"({res['rk4'] / res['rk4_graph']:.2f}x)", flush=True)
 

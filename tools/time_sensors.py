@@ -22,6 +22,8 @@ import numpy as np
 
 ROOT = os.path.abspath(os.path.join(os.path.dirname(__file__), ".."))
 sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tools"))
+import measure  # noqa: E402  (no torch at its module level)
 
 
 def plane_points(L, nx=141, nz=241):
@@ -30,37 +32,35 @@ def plane_points(L, nx=141, nz=241):
     return np.stack([X.reshape(-1), np.full(X.size, 0.5 * L), Z.reshape(-1)], axis=1)
 
 
-def main():
+def main(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--parts", default="abc")
     ap.add_argument("--log", default=os.path.join(ROOT, "profiles", "time_sensors.log"))
     ap.add_argument("--rounds", type=int, default=7)
-    a = ap.parse_args()
+    a = ap.parse_args(argv)
+    with measure.Log("time_sensors", a.log) as log:
+        run(a, log)
+
+
+def step_lines(log, res, width, what):
+    base = measure.stats(next(iter(res.values()))).median
+    for kind, v in res.items():
+        med = measure.stats(v).median
+        log(f"  {kind:{width}s} {med:.3f} ms/step  (rounds {', '.join(f'{x:.3f}' for x in v)})  -> {med / base:.4f} x {what}")
+    for line in measure.verdict_lines(res, to_us=1e3):
+        log(line)
+
+
+def run(a, log):
     import torch
 
     import fusgpu_loader
 
     torch.cuda.set_device(0)
     boxmesh, ls, nls, sens = (fusgpu_loader.submodule(m) for m in ("boxmesh", "linear_solver", "nonlinear_solver", "sensors"))
-    lines = []
-
-    def log(s):
-        print(s, flush=True)
-        lines.append(s)
-
-    log(f"# tools/time_sensors.py on {torch.cuda.get_device_name(0)}, {time.strftime('%Y-%m-%d %H:%M:%S')}")
+    log.header()
     L = 0.12
     pts = plane_points(L)
-
-    def ev_time(fn, reps):
-        s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        torch.cuda.synchronize()
-        s.record()
-        for _ in range(reps):
-            fn()
-        e.record()
-        e.synchronize()
-        return s.elapsed_time(e) / reps
 
     if "a" in a.parts:
         log("(a) one sensor launch, 34081 points, series + peaks + harmonics 1, 2 (event pair around 200 launches, median of rounds)")
@@ -80,12 +80,10 @@ def main():
                     t[0] += 1e-7
                     s.record(u, t[0])
 
-                for _ in range(20):
-                    one()
-                ms = sorted(ev_time(one, 200) for _ in range(a.rounds))
+                st = measure.stats(measure.interleave({"launch": one}, a.rounds, lambda fn: measure.event_time(fn, 200), warm=20)["launch"])
                 nb = s.m * 3 * (P + 1) * s.tdt_np.itemsize + s._rows.numel() * 4 + s._rows.numel() * s.tdt_np.itemsize
                 log(f"  P={P} {cells}^3 {np.dtype(dt_np).name}: {s.m} points in {s._rows.shape[0]} cells, "
-                    f"{ms[len(ms) // 2] * 1e3:.1f} us per launch (min {ms[0] * 1e3:.1f}, max {ms[-1] * 1e3:.1f}); "
+                    f"{st.median * 1e3:.1f} us per launch (min {st.min * 1e3:.1f}, max {st.max * 1e3:.1f}); "
                     f"distinct input ~{nb / 1e6:.2f} MB; host set-up {t_setup:.2f} s (mesh {t_mesh:.1f} s)")
                 del s, u
             del mesh
@@ -102,18 +100,15 @@ def main():
         s = sens.PointSensors(mesh, pts, np.float64, capacity=K, peak=True, harmonics=(1, 2), frequency=0.5e6)
         solver.rk4(0.0, tf, dt, max_steps=3)
         t = 3 * dt
-        res = {"plain": [], "sensors": []}
-        for r in range(a.rounds):
-            for kind in ("plain", "sensors"):
-                s.reset()
-                torch.cuda.synchronize()
-                t0 = time.perf_counter()
-                t, _ = solver.rk4(t, tf * 100, dt, max_steps=K, sensors=s if kind == "sensors" else None)
-                torch.cuda.synchronize()
-                res[kind].append((time.perf_counter() - t0) / K * 1e3)
-        mp, mswith = np.median(res["plain"]), np.median(res["sensors"])
-        log(f"  plain   {mp:.3f} ms/step  (rounds {', '.join(f'{x:.3f}' for x in res['plain'])})")
-        log(f"  sensors {mswith:.3f} ms/step  (rounds {', '.join(f'{x:.3f}' for x in res['sensors'])})  -> {mswith / mp:.4f} x")
+
+        def steps(sensors):
+            def go():
+                nonlocal t
+                t, _ = solver.rk4(t, tf * 100, dt, max_steps=K, sensors=sensors)
+
+            return s.reset, go
+
+        step_lines(log, measure.interleave({"plain": steps(None), "sensors": steps(s)}, a.rounds, lambda fn: measure.host_time(fn, K)), 7, "plain")
         del solver, s
         torch.cuda.empty_cache()
 
@@ -143,31 +138,34 @@ def main():
         s0 = sens.PointSensors(mesh, pts, np.float64, capacity=W, peak=True)  # no harmonics: no per-step coefficient copy
         solver.rk4(0.0, 1.0, dt, max_steps=3)
         t = 3 * dt
-        res = {"plain": [], "sensors": [], "sensors, no harmonics": [], "host loop": []}
-        # the host loop leaves the device idle most of the time (its clocks drop): it runs in a block of its own after the others
-        for _, kind in [(r, k) for r in range(a.rounds) for k in list(res)[:3]] + [(r, "host loop") for r in range(2)]:
+
+        def between():  # untimed steps between the variants
+            nonlocal t
             s.reset()
             s0.reset()
-            t, _ = solver.rk4(t, 1.0, dt, max_steps=5)  # untimed steps between the variants
-            torch.cuda.synchronize()
-            t0 = time.perf_counter()
-            if kind == "host loop":  # what demo_nonlinear_bowl.py does per step of its window without --sensor-plane
-                for _ in range(W):
-                    t, _ = solver.rk4(t, 1.0, dt, max_steps=1)
-                    _ = solver.u_sol()[on_plane]
-            else:
-                t, _ = solver.rk4(t, 1.0, dt, max_steps=W, sensors={"plain": None, "sensors": s}.get(kind, s0))
-            torch.cuda.synchronize()
-            res[kind].append((time.perf_counter() - t0) / W * 1e3)
-        base = np.median(res["plain"])
-        for kind, v in res.items():
-            log(f"  {kind:21s} {np.median(v):.3f} ms/step  (rounds {', '.join(f'{x:.3f}' for x in v)})  -> {np.median(v) / base:.3f} x plain")
-        log(f"  (field: {mesh.nlocal * 8 / 1e6:.1f} MB per u_sol() copy; {s.m} sensor points; steps per period {spp})")
+            t, _ = solver.rk4(t, 1.0, dt, max_steps=5)
 
-    if a.log:
-        os.makedirs(os.path.dirname(os.path.abspath(a.log)), exist_ok=True)
-        with open(a.log, "a") as f:
-            f.write("\n".join(lines) + "\n")
+        def steps(sensors):
+            def go():
+                nonlocal t
+                t, _ = solver.rk4(t, 1.0, dt, max_steps=W, sensors=sensors)
+
+            return between, go
+
+        def host_loop():  # what demo_nonlinear_bowl.py does per step of its window without --sensor-plane
+            nonlocal t
+            for _ in range(W):
+                t, _ = solver.rk4(t, 1.0, dt, max_steps=1)
+                _ = solver.u_sol()[on_plane]
+
+        def timer(fn):
+            return measure.host_time(fn, W)
+
+        res = measure.interleave({"plain": steps(None), "sensors": steps(s), "sensors, no harmonics": steps(s0)}, a.rounds, timer)
+        # the host loop leaves the device idle most of the time (its clocks drop): it runs in a block of its own after the others
+        res.update(measure.interleave({"host loop": (between, host_loop)}, 2, timer))
+        step_lines(log, res, 21, "plain")
+        log(f"  (field: {mesh.nlocal * 8 / 1e6:.1f} MB per u_sol() copy; {s.m} sensor points; steps per period {spp})")
 
 
 if __name__ == "__main__":

@@ -17,33 +17,33 @@ constructor's ``source=`` binds), so the cell launches, the plans and the memory
 import argparse
 import os
 import sys
-import time
 
 import numpy as np
 
 ROOT = os.path.abspath(os.path.join(os.path.dirname(__file__), ".."))
 sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tools"))
+import measure  # noqa: E402  (no torch at its module level)
 
 
-def main():
+def main(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--parts", default="ab")
     ap.add_argument("--log", default=os.path.join(ROOT, "profiles", "time_sources.log"))
     ap.add_argument("--rounds", type=int, default=7)
-    a = ap.parse_args()
+    a = ap.parse_args(argv)
+    with measure.Log("time_sources", a.log) as log:
+        run(a, log)
+
+
+def run(a, log):
     import torch
 
     import fusgpu_loader
 
     torch.cuda.set_device(0)
     boxmesh, ls, src, ops = (fusgpu_loader.submodule(m) for m in ("boxmesh", "linear_solver", "sources", "operators"))
-    lines = []
-
-    def log(s):
-        print(s, flush=True)
-        lines.append(s)
-
-    log(f"# tools/time_sources.py on {torch.cuda.get_device_name(0)}, {time.strftime('%Y-%m-%d %H:%M:%S')}")
+    log.header()
     L, P, c0, f0 = 0.12, 4, 1500.0, 0.5e6
     mesh = boxmesh.BoxMesh(P, 54, length=L, perturb=0.16, seed=0)
     h = ls.time_step_parameters(mesh, P, c0, f0, L)
@@ -65,16 +65,6 @@ def main():
              "256 elements": bind(grid(16)), "1024 elements": bind(grid(32))}
     log(f"config 3: P={P}, 54^3 perturbed cells, {mesh.ndofs} dofs, fp64, fused; {bd1.shape[0]} source facets, dt {dt:.4e} s")
 
-    def ev_time(fn, reps):
-        s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        torch.cuda.synchronize()
-        s.record()
-        for _ in range(reps):
-            fn()
-        e.record()
-        e.synchronize()
-        return s.elapsed_time(e) / reps
-
     t_stage = 30.0 / f0  # every element past its delay: the ramp / plateau branch of the kernel
     if "a" in a.parts:
         log("(a) the facet launch alone (source + absorbing sets in one launch), event pair around 200 launches, median of rounds")
@@ -89,40 +79,31 @@ def main():
             stage = ba.stage_scalars(t_stage)
             return lambda: ops.facet_source_terms(b, ba, field, stage=stage)
 
-        fns = {k: launch(k) for k in cases}
-        for f in fns.values():
-            for _ in range(20):
-                f()
-        res = {k: [] for k in cases}
-        for _ in range(a.rounds):
-            for k, f in fns.items():
-                res[k].append(ev_time(f, 200) * 1e3)
+        res = measure.interleave({k: launch(k) for k in cases}, a.rounds, lambda fn: measure.event_time(fn, 200) * 1e3, warm=20)  # us
         for k, v in res.items():
-            log(f"  {k:14s} {np.median(v):6.2f} us per launch  (rounds {', '.join(f'{x:.2f}' for x in v)})")
+            log(f"  {k:14s} {measure.stats(v).median:6.2f} us per launch  (rounds {', '.join(f'{x:.2f}' for x in v)})")
+        for line in measure.verdict_lines(res):
+            log(line)
 
     if "b" in a.parts:
         K = 20
         log(f"(b) the step: rk4 over {K} steps per case, the cases interleaved round by round")
         solver.rk4(0.0, tf, dt, max_steps=3)
         t = t_stage
-        res = {k: [] for k in cases}
-        for _ in range(a.rounds):
-            for k, ba in cases.items():
-                solver.source = ba
-                torch.cuda.synchronize()
-                t0 = time.perf_counter()
-                t, _ = solver.rk4(t, tf * 100, dt, max_steps=K)
-                torch.cuda.synchronize()
-                res[k].append((time.perf_counter() - t0) / K * 1e3)
-        solver.source = None
-        base = np.median(res["scalar"])
-        for k, v in res.items():
-            log(f"  {k:14s} {np.median(v):.4f} ms/step  (rounds {', '.join(f'{x:.4f}' for x in v)})  -> {np.median(v) / base:.4f} x scalar")
 
-    if a.log:
-        os.makedirs(os.path.dirname(os.path.abspath(a.log)), exist_ok=True)
-        with open(a.log, "a") as f:
-            f.write("\n".join(lines) + "\n")
+        def steps():
+            nonlocal t
+            t, _ = solver.rk4(t, tf * 100, dt, max_steps=K)
+
+        res = measure.interleave({k: (lambda ba=ba: setattr(solver, "source", ba), steps) for k, ba in cases.items()}, a.rounds,
+                                 lambda fn: measure.host_time(fn, K))
+        solver.source = None
+        base = measure.stats(res["scalar"]).median
+        for k, v in res.items():
+            med = measure.stats(v).median
+            log(f"  {k:14s} {med:.4f} ms/step  (rounds {', '.join(f'{x:.4f}' for x in v)})  -> {med / base:.4f} x scalar")
+        for line in measure.verdict_lines(res, to_us=1e3):
+            log(line)
 
 
 if __name__ == "__main__":
