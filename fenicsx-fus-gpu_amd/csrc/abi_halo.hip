@@ -25,13 +25,15 @@ struct fus_halo {
 
 static std::string g_comm_error;  // errors that happen before a communicator exists
 
+static bool rccl_loaded() {
+  if (!fus::rccl().load()) g_comm_error = fus::rccl().error;
+  return fus::rccl().handle != nullptr;
+}
+
 int fus_comm_unique_id(void* id) {
   if (!id) return FUS_ERR_INVALID_ARGUMENT;
+  if (!rccl_loaded()) return FUS_ERR_COMM;
   fus::RcclApi& api = fus::rccl();
-  if (!api.load()) {
-    g_comm_error = api.error;
-    return FUS_ERR_COMM;
-  }
   ncclUniqueId uid;
   static_assert(sizeof(uid) == FUS_UNIQUE_ID_BYTES, "unique id size");
   const ncclResult_t r = api.GetUniqueId(&uid);
@@ -43,29 +45,46 @@ int fus_comm_unique_id(void* id) {
   return FUS_OK;
 }
 
-int fus_comm_create(const void* id, int nranks, int rank, fus_comm_t* out) {
-  if (!id || !out || nranks < 1 || rank < 0 || rank >= nranks) return FUS_ERR_INVALID_ARGUMENT;
-  fus::RcclApi& api = fus::rccl();
-  if (!api.load()) {
-    g_comm_error = api.error;
-    return FUS_ERR_COMM;
-  }
+// Release whatever of a communicator exists: both streams (drained first), the fork / join words, the RCCL communicator.
+// fus_comm_destroy and every failure path of the creators end here.
+static void comm_release(fus_comm* comm) {
+  fus::Comm& c = comm->c;
+  (void)fus::comm_flush_attached(&c);  // a fork signal still waiting for a launch to carry it must not outlive its flag
+  if (c.stream) (void)hipStreamSynchronize(c.stream);
+  if (c.stream2) (void)hipStreamSynchronize(c.stream2);
+  if (c.nccl) (void)fus::rccl().CommDestroy(c.nccl);
+  if (c.stream2 && c.stream2 != c.stream) (void)hipStreamDestroy(c.stream2);
+  if (c.stream) (void)hipStreamDestroy(c.stream);
+  if (c.sync_words) (void)hipFree(c.sync_words);
+  delete comm;
+}
+
+// *out: a communicator of ``kind`` with its stream(s) and fork / join words; on failure nothing is left behind or written
+static int comm_new(fus::Comm::Kind kind, int nranks, int rank, fus_comm** out) {
   auto* c = new fus_comm;
-  c->c.kind = fus::Comm::RCCL;
+  c->c.kind = kind;
   c->c.rank = rank;
   c->c.nranks = nranks;
-  hipError_t e = fus::comm_make_stream_and_sync(&c->c);
-  if (e != hipSuccess) {
-    delete c;
-    return hip_rc(e);
-  }
+  hipError_t e = fus::comm_make_stream(&c->c);
+  if (e == hipSuccess) e = fus::comm_sync_init(&c->c);
+  if (e == hipSuccess) *out = c;
+  else comm_release(c);
+  return hip_rc(e);
+}
+
+int fus_comm_create(const void* id, int nranks, int rank, fus_comm_t* out) {
+  if (!id || !out || nranks < 1 || rank < 0 || rank >= nranks) return FUS_ERR_INVALID_ARGUMENT;
+  if (!rccl_loaded()) return FUS_ERR_COMM;
+  fus::RcclApi& api = fus::rccl();
+  fus_comm* c = nullptr;
+  if (const int rc = comm_new(fus::Comm::RCCL, nranks, rank, &c); rc != FUS_OK) return rc;
   ncclUniqueId uid;
   std::memcpy(&uid, id, sizeof(uid));
   const ncclResult_t r = api.CommInitRank(&c->c.nccl, nranks, uid, rank);
   if (r != ncclSuccess) {
     g_comm_error = std::string("ncclCommInitRank: ") + api.GetErrorString(r);
-    (void)hipStreamDestroy(c->c.stream);
-    delete c;
+    c->c.nccl = nullptr;
+    comm_release(c);
     return FUS_ERR_COMM;
   }
   *out = c;
@@ -74,18 +93,7 @@ int fus_comm_create(const void* id, int nranks, int rank, fus_comm_t* out) {
 
 int fus_comm_create_peer(int nranks, int rank, fus_comm_t* out) {
   if (!out || nranks < 1 || rank < 0 || rank >= nranks) return FUS_ERR_INVALID_ARGUMENT;
-  auto* c = new fus_comm;
-  c->c.kind = fus::Comm::PEER;
-  c->c.rank = rank;
-  c->c.nranks = nranks;
-  hipError_t e = fus::comm_make_stream_and_sync(&c->c);
-  if (e != hipSuccess) {
-    if (c->c.stream) (void)hipStreamDestroy(c->c.stream);
-    delete c;
-    return hip_rc(e);
-  }
-  *out = c;
-  return FUS_OK;
+  return comm_new(fus::Comm::PEER, nranks, rank, out);
 }
 
 int fus_comm_create_local(int world_id, int nranks, int rank, fus_comm_t* out) {
@@ -100,18 +108,9 @@ int fus_comm_create_local(int world_id, int nranks, int rank, fus_comm_t* out) {
     worlds[world_id] = w;
   }
   if (w->nranks != nranks) return FUS_ERR_INVALID_ARGUMENT;
-  auto* c = new fus_comm;
-  c->c.kind = fus::Comm::LOCAL;
-  c->c.rank = rank;
-  c->c.nranks = nranks;
-  c->c.world = w;
-  hipError_t e = fus::comm_make_stream_and_sync(&c->c);
-  if (e != hipSuccess) {
-    delete c;
-    return hip_rc(e);
-  }
-  *out = c;
-  return FUS_OK;
+  const int rc = comm_new(fus::Comm::LOCAL, nranks, rank, out);
+  if (rc == FUS_OK) (*out)->c.world = w;
+  return rc;
 }
 
 int fus_comm_rank(fus_comm_t comm) { return comm ? comm->c.rank : FUS_ERR_INVALID_ARGUMENT; }
@@ -130,15 +129,9 @@ int fus_comm_fork_ex(fus_comm_t comm, void* stream, int flags) {
   if (flags & ~(FUS_FORK_LAZY | FUS_FORK_ATTACH)) return FUS_ERR_INVALID_ARGUMENT;
   return comm_fork_join_rc(comm, stream, 0, (flags & FUS_FORK_LAZY) != 0, (flags & FUS_FORK_ATTACH) != 0);
 }
-int fus_comm_fork_flush(fus_comm_t comm) {
-  if (!comm) return FUS_ERR_INVALID_ARGUMENT;
-  return hip_rc(fus::comm_flush_attached(&comm->c));
-}
+int fus_comm_fork_flush(fus_comm_t comm) { return comm ? hip_rc(fus::comm_flush_attached(&comm->c)) : FUS_ERR_INVALID_ARGUMENT; }
 int fus_comm_join(fus_comm_t comm, void* stream) { return comm_fork_join_rc(comm, stream, 1, false); }
-int fus_comm_arm_join(fus_comm_t comm) {
-  if (!comm) return FUS_ERR_INVALID_ARGUMENT;
-  return hip_rc(fus::comm_arm_join(&comm->c));
-}
+int fus_comm_arm_join(fus_comm_t comm) { return comm ? hip_rc(fus::comm_arm_join(&comm->c)) : FUS_ERR_INVALID_ARGUMENT; }
 int fus_comm_health(fus_comm_t comm, int64_t* failures) {
   if (!comm || !failures) return FUS_ERR_INVALID_ARGUMENT;
   return fus::comm_health(&comm->c, failures) == 0 ? FUS_OK : FUS_ERR_COMM;
@@ -159,25 +152,35 @@ int fus_comm_sync_timeouts(fus_comm_t comm, int64_t* out) {
   return hip_rc(e);
 }
 
-const char* fus_comm_last_error(fus_comm_t comm) {
-  return comm ? comm->c.last_error.c_str() : g_comm_error.c_str();
-}
+const char* fus_comm_last_error(fus_comm_t comm) { return comm ? comm->c.last_error.c_str() : g_comm_error.c_str(); }
 
 int fus_comm_destroy(fus_comm_t comm) {
   if (!comm) return FUS_OK;
-  if (comm->c.nhalos > 0) {  // a halo holds a pointer to its communicator: destroy the halos first
-    comm->c.last_error = "fus_comm_destroy: " + std::to_string(comm->c.nhalos) + " halo object(s) of this communicator are still alive";
+  if (!comm->c.halos.empty()) {  // a halo holds a pointer to its communicator: destroy the halos first
+    comm->c.last_error = "fus_comm_destroy: " + std::to_string(comm->c.halos.size()) + " halo object(s) of this communicator are still alive";
     return FUS_ERR_COMM;
   }
-  (void)fus::comm_flush_attached(&comm->c);  // a fork signal still waiting for a launch to carry it must not outlive its flag
-  if (comm->c.stream) (void)hipStreamSynchronize(comm->c.stream);
-  if (comm->c.stream2) (void)hipStreamSynchronize(comm->c.stream2);
-  if (comm->c.nccl) (void)fus::rccl().CommDestroy(comm->c.nccl);
-  if (comm->c.stream2 && comm->c.stream2 != comm->c.stream) (void)hipStreamDestroy(comm->c.stream2);
-  if (comm->c.stream) (void)hipStreamDestroy(comm->c.stream);
-  if (comm->c.sync_words) (void)hipFree(comm->c.sync_words);
-  delete comm;
+  comm_release(comm);
   return FUS_OK;
+}
+
+// Elements of one side of a plan, or -1: no rank or size list, a negative size, a neighbour rank outside the communicator, no index list,
+// an index outside [0, bound) (it would fault in the pack / unpack kernels: checked here, once).  *identity: idx[i] == i, side not empty.
+static int64_t side_check(int n, const int32_t* ranks, const int64_t* sizes, int nranks, const int64_t* idx, int64_t bound,
+                          bool* identity) {
+  int64_t total = 0;
+  if (n > 0 && (!ranks || !sizes)) return -1;
+  for (int i = 0; i < n; ++i) {
+    if (sizes[i] < 0 || ranks[i] < 0 || ranks[i] >= nranks) return -1;
+    total += sizes[i];
+  }
+  if (total > 0 && !idx) return -1;
+  *identity = total > 0;
+  for (int64_t i = 0; i < total; ++i) {
+    if (idx[i] < 0 || idx[i] >= bound) return -1;
+    if (idx[i] != i) *identity = false;
+  }
+  return total;
 }
 
 int fus_halo_create(fus_comm_t comm, int elem_bytes, int64_t nlocal, int64_t nghost, int n_owner_ranks,
@@ -187,26 +190,10 @@ int fus_halo_create(fus_comm_t comm, int elem_bytes, int64_t nlocal, int64_t ngh
   if (!comm || !out || (elem_bytes != 4 && elem_bytes != 8) || nlocal < 0 || nghost < 0 || n_owner_ranks < 0 ||
       n_ghost_ranks < 0)
     return FUS_ERR_INVALID_ARGUMENT;
-  if ((n_owner_ranks > 0 && (!owner_ranks || !owner_sizes)) || (n_ghost_ranks > 0 && (!ghost_ranks || !ghost_sizes)))
-    return FUS_ERR_INVALID_ARGUMENT;
-  int64_t no = 0, ng = 0;
-  for (int i = 0; i < n_owner_ranks; ++i) {
-    if (owner_sizes[i] < 0 || owner_ranks[i] < 0 || owner_ranks[i] >= comm->c.nranks) return FUS_ERR_INVALID_ARGUMENT;
-    no += owner_sizes[i];
-  }
-  for (int i = 0; i < n_ghost_ranks; ++i) {
-    if (ghost_sizes[i] < 0 || ghost_ranks[i] < 0 || ghost_ranks[i] >= comm->c.nranks) return FUS_ERR_INVALID_ARGUMENT;
-    ng += ghost_sizes[i];
-  }
-  if (no > nghost || (no > 0 && !owners_idx) || (ng > 0 && !ghosts_idx)) return FUS_ERR_INVALID_ARGUMENT;
-  // out-of-range indices would fault in the pack / unpack kernels: check them here, once
-  bool direct = no > 0;
-  for (int64_t i = 0; i < no; ++i) {
-    if (owners_idx[i] < 0 || owners_idx[i] >= nghost) return FUS_ERR_INVALID_ARGUMENT;
-    if (owners_idx[i] != i) direct = false;
-  }
-  for (int64_t i = 0; i < ng; ++i)
-    if (ghosts_idx[i] < 0 || ghosts_idx[i] >= nlocal) return FUS_ERR_INVALID_ARGUMENT;
+  bool direct = false, unused = false;
+  const int64_t no = side_check(n_owner_ranks, owner_ranks, owner_sizes, comm->c.nranks, owners_idx, nghost, &direct);
+  const int64_t ng = side_check(n_ghost_ranks, ghost_ranks, ghost_sizes, comm->c.nranks, ghosts_idx, nlocal, &unused);
+  if (no < 0 || ng < 0 || no > nghost) return FUS_ERR_INVALID_ARGUMENT;
   auto* hh = new fus_halo;
   fus::Halo& h = hh->h;
   h.comm = &comm->c;
@@ -214,7 +201,6 @@ int fus_halo_create(fus_comm_t comm, int elem_bytes, int64_t nlocal, int64_t ngh
   h.nlocal = nlocal;
   h.nghost = nghost;
   h.direct = direct;
-  ++comm->c.nhalos;
   comm->c.halos.push_back(&h);
   const bool peer = comm->c.kind == fus::Comm::PEER;
   hipError_t e = fus::side_init(h.owners, n_owner_ranks, owner_ranks, owner_sizes, owners_idx, comm->c.stream);
@@ -242,21 +228,18 @@ int fus_halo_create(fus_comm_t comm, int elem_bytes, int64_t nlocal, int64_t ngh
 int fus_halo_destroy(fus_halo_t halo) {
   if (!halo) return FUS_OK;
   fus::Halo& h = halo->h;
-  if (h.comm && h.comm->stream) (void)hipStreamSynchronize(h.comm->stream);
-  if (h.comm && h.comm->stream2) (void)hipStreamSynchronize(h.comm->stream2);
-  if (h.comm && h.comm->kind == fus::Comm::LOCAL && h.comm->world) {
+  fus::Comm& c = *h.comm;  // (set before anything of a halo can fail)
+  if (c.stream) (void)hipStreamSynchronize(c.stream);
+  if (c.stream2) (void)hipStreamSynchronize(c.stream2);
+  if (c.kind == fus::Comm::LOCAL && c.world) {
     std::lock_guard<std::mutex> lock(fus::local_worlds_mutex());
-    auto& mine = h.comm->world->halos[h.comm->rank];
+    auto& mine = c.world->halos[c.rank];
     if (h.index < (int)mine.size() && mine[h.index] == &h) mine[h.index] = nullptr;
   }
-  if (h.comm) {
-    --h.comm->nhalos;
-    auto& hv = h.comm->halos;
-    hv.erase(std::remove(hv.begin(), hv.end(), &h), hv.end());
-    if (h.comm->join_halo == &h) {
-      h.comm->join_halo = nullptr;
-      h.comm->join_armed = false;
-    }
+  c.halos.erase(std::remove(c.halos.begin(), c.halos.end(), &h), c.halos.end());
+  if (c.join_halo == &h) {
+    c.join_halo = nullptr;
+    c.join_armed = false;
   }
   fus::halo_ipc_free(&h);
   fus::side_free(h.owners);
@@ -298,8 +281,8 @@ int fus_halo_reverse_begin(fus_halo_t halo, void* buffer, void* stream) { return
 int fus_halo_reverse_end(fus_halo_t halo, void* buffer, void* stream) { return halo_op(fus::halo_end, halo, buffer, stream, 1); }
 
 static int halo_group_rc(const fus_halo_t* halos, void* const* buffers, int n, void* stream, int dir) {
-  if (n < 0 || n > 8 || (n > 0 && (!halos || !buffers))) return FUS_ERR_INVALID_ARGUMENT;
-  fus::Halo* hs[8];
+  if (n < 0 || n > fus::kHaloGroupMax || (n > 0 && (!halos || !buffers))) return FUS_ERR_INVALID_ARGUMENT;
+  fus::Halo* hs[fus::kHaloGroupMax];
   for (int k = 0; k < n; ++k) {
     if (!halos[k] || !buffers[k]) return FUS_ERR_INVALID_ARGUMENT;
     hs[k] = &halos[k]->h;
@@ -313,19 +296,7 @@ int fus_halo_reverse_begin_group(const fus_halo_t* halos, void* const* buffers, 
   return halo_group_rc(halos, buffers, n, stream, 1);
 }
 
-int fus_halo_forward(fus_halo_t halo, void* buffer, void* stream) {
-  if (!halo || !buffer) return FUS_ERR_INVALID_ARGUMENT;
-  const int r = fus::halo_exchange_inline(&halo->h, buffer, static_cast<hipStream_t>(stream), 0);  // PEER: on the caller's stream
-  if (r <= 0) return r == 0 ? FUS_OK : FUS_ERR_COMM;
-  const int rc = fus_halo_forward_begin(halo, buffer, stream);
-  return rc != FUS_OK ? rc : fus_halo_forward_end(halo, buffer, stream);
-}
-int fus_halo_reverse(fus_halo_t halo, void* buffer, void* stream) {
-  if (!halo || !buffer) return FUS_ERR_INVALID_ARGUMENT;
-  const int r = fus::halo_exchange_inline(&halo->h, buffer, static_cast<hipStream_t>(stream), 1);
-  if (r <= 0) return r == 0 ? FUS_OK : FUS_ERR_COMM;
-  const int rc = fus_halo_reverse_begin(halo, buffer, stream);
-  return rc != FUS_OK ? rc : fus_halo_reverse_end(halo, buffer, stream);
-}
+int fus_halo_forward(fus_halo_t halo, void* buffer, void* stream) { return halo_op(fus::halo_exchange, halo, buffer, stream, 0); }
+int fus_halo_reverse(fus_halo_t halo, void* buffer, void* stream) { return halo_op(fus::halo_exchange, halo, buffer, stream, 1); }
 
 }  // extern "C"

@@ -9,9 +9,9 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-namespace fus {
+#include "halo_layout.hpp"  // HaloMode
 
-enum HaloMode { PACK = 0, UNPACK_SET = 1, UNPACK_ADD = 2 };
+namespace fus {
 
 template <typename T, int MODE>
 __global__ void __launch_bounds__(256)

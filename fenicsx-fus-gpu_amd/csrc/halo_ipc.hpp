@@ -1,7 +1,6 @@
 // PEER transport of the ghost-dof halo exchange: no RCCL kernel, no copy engine call, no host in the loop.
 //
-// Replaces the same closures as halo_comm.hpp (cuda/scatterer.py:104-188 scatter_reverse, :191-277 scatter_forward:
-// pack kernel -> device synchronise -> MPI Isend/Irecv on device pointers -> wait -> unpack kernel -> synchronise).
+// This file is the device code; the host side (arenas, chunk tables, blobs, posting) is halo_peer.hpp.
 //
 // Why (profiles/r02z_overlap_probe.log, r03a_*): RCCL's send/recv kernel needs 264 VGPRs per lane and is not scheduled
 // next to an operator launch that holds every vector register of every CU, so an exchange posted "under" interior cells
@@ -40,17 +39,12 @@
 
 #include <hip/hip_runtime.h>
 #include <stdint.h>
-#include <unistd.h>
 
-#include <algorithm>
-#include <chrono>
-#include <cstdio>
 #include <cstdlib>
-#include <cstring>
-#include <string>
-#include <vector>
 
+#include "flag_wait.hpp"    // stream_flag_wait: the fork flag, waited for by the first send kernel of an apply itself
 #include "halo.hpp"
+#include "halo_layout.hpp"  // IpcChunk, IpcPeer, the flag and status words
 
 namespace fus {
 
@@ -75,28 +69,7 @@ inline int ipc_chunk() {
   static const int c = ipc_env_int("FUS_IPC_CHUNK", 1024, 64, ipc_threads() * kIpcEpt);
   return c;
 }
-constexpr int kIpcFlagStride = 64;  // bytes between two flags: one flag per 64-byte line
-constexpr uint32_t kIpcMagic = 0x46555349u;  // "FUSI"
 constexpr uint64_t kIpcPoison = 1ull << 63;  // in a flag: the publisher's halo has failed (time-out here or upstream)
-
-// flag kinds inside an arena; slot = index of the neighbour in the owners-side (kinds 0, 1) or ghosts-side (2, 3) list
-enum IpcFlag { ARRIVED_FWD = 0, CREDIT_REV = 1, ARRIVED_REV = 2, CREDIT_FWD = 3 };
-enum IpcStatus { ST_TIMEOUTS = 0, ST_DEAD = 1, ST_POISONED = 2, ST_WORDS = 8 };
-
-struct IpcChunk {
-  int32_t nbr;    // neighbour slot on the side the kernel walks
-  int32_t count;  // elements in this chunk
-  int64_t start;  // element offset inside the side's concatenated index list
-};
-
-struct IpcPeer {       // one per neighbour slot and kernel role, in device memory
-  char* data;          // send: my segment inside the neighbour's receive buffer (mapped); recv: my receive buffer
-  uint64_t* flag_out;  // send: neighbour's "arrived" flag (mapped);  recv: neighbour's credit flag (mapped)
-  uint64_t* flag_in;   // send: my credit flag;                         recv: my "arrived" flag
-  int64_t seg_off;     // first element of the neighbour's segment in my concatenated list
-  int32_t nchunks;     // workgroups of this neighbour's segment
-  int32_t pad_;
-};
 
 // Memory ordering without fences.  A release / acquire fence at agent or system scope is an L2 write-back / invalidate on
 // gfx942 / gfx950 (buffer_wbl2 / buffer_inv): issued by every workgroup of an exchange next to an operator launch whose
@@ -148,22 +121,6 @@ __device__ inline int ipc_wait(const uint64_t* flag, uint64_t want, uint64_t* st
       return 0;
     }
     v = ipc_load_flag(flag);
-  }
-}
-
-// Wait (bounded) for a flag of THIS device (agent scope): the fork flag of the communicator, folded into the first send
-// kernel of an apply instead of a wait kernel of its own (halo_comm.hpp comm_fork_join).
-__device__ inline void ipc_wait_gate(const uint64_t* gate, uint64_t want, uint64_t* gate_status, uint64_t budget) {
-  if (__hip_atomic_load(gate, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) >= want) return;
-  if (__hip_atomic_load(&gate_status[ST_DEAD], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) return;
-  const uint64_t t0 = wall_clock64();
-  while (__hip_atomic_load(gate, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < want) {
-    __builtin_amdgcn_s_sleep(2);
-    if (wall_clock64() - t0 > budget) {
-      atomicAdd((unsigned long long*)&gate_status[ST_TIMEOUTS], 1ull);
-      __hip_atomic_store(&gate_status[ST_DEAD], (uint64_t)1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      return;
-    }
   }
 }
 
@@ -240,7 +197,7 @@ __global__ void __launch_bounds__(kIpcMaxThreads)
   const IpcPeer p = peers[c.nbr];
   __shared__ int ok;
   if (threadIdx.x == 0) {
-    if (gate.flag) ipc_wait_gate(gate.flag, gate.seq, gate.status, budget);  // the caller's stream has produced the vector
+    if (gate.flag) stream_flag_wait(gate.flag, gate.seq, gate.status, budget);  // the caller's stream has produced the vector
     ok = ipc_wait(p.flag_in, seq - 1, status, budget);                       // the neighbour has consumed message seq-1
   }
   __syncthreads();
@@ -322,153 +279,6 @@ __global__ void __launch_bounds__(kIpcMaxThreads)
     ipc_segment_done(&counters[c.nbr], p.nchunks, p.flag_out, seq, status);
     ipc_kernel_done(join);
   }
-}
-
-// ------------------------------------------------------------------------------------------- host side
-struct IpcSideInfo {  // what a peer needs to know about one side of my plan
-  std::vector<int32_t> ranks;
-  std::vector<int64_t> counts, offsets;
-};
-
-struct IpcRole {  // device tables of one kernel role (send or recv) over one side
-  IpcChunk* chunks = nullptr;
-  IpcPeer* peers = nullptr;
-  unsigned* counters = nullptr;
-  int nchunks = 0, nnbr = 0;
-  std::vector<IpcPeer> host_peers;
-};
-
-constexpr int32_t kIpcBlobVersion = 2;
-
-// Identity of THIS process, drawn once: a pid alone does not identify an address space (ranks in different PID namespaces
-// -- one container per rank -- can share a pid, and the importer would then dereference a foreign virtual address).
-struct IpcProcessToken {
-  uint64_t w[2];
-};
-inline const IpcProcessToken& ipc_process_token() {
-  static const IpcProcessToken tok = [] {
-    IpcProcessToken t{{0, 0}};
-    if (FILE* f = std::fopen("/dev/urandom", "rb")) {
-      if (std::fread(&t, sizeof t, 1, f) != 1) t = IpcProcessToken{{0, 0}};
-      std::fclose(f);
-    }
-    if (!t.w[0] && !t.w[1]) {  // no /dev/urandom: pid + a high-resolution clock + an address of this image
-      t.w[0] = ((uint64_t)getpid() << 32) ^ (uint64_t)(uintptr_t)&ipc_process_token;
-      t.w[1] = (uint64_t)std::chrono::steady_clock::now().time_since_epoch().count();
-    }
-    t.w[0] |= 1;  // never all-zero
-    return t;
-  }();
-  return tok;
-}
-
-struct IpcBlobHeader {
-  uint32_t magic;
-  int32_t version;
-  int32_t rank;
-  int32_t elem_bytes;
-  int64_t pid;    // informational (error messages); the address space is identified by ``token``
-  IpcProcessToken token;
-  char pci_bus_id[32];  // of the exporter's device: ordinals are process-local (HIP_VISIBLE_DEVICES per rank)
-  uint64_t base;  // arena address in the exporting process (used directly when importer == exporter process)
-  hipIpcMemHandle_t handle;
-  int64_t arena_bytes;
-  int64_t off_flags, off_recv_fwd, off_recv_rev;
-  int32_t n_owner, n_ghost, nmax, device;
-  // followed by n_owner x (int64 rank, count, offset), then n_ghost x the same
-};
-
-struct IpcState {
-  char* arena = nullptr;  // fine-grained device memory: flags, forward receive buffer, reverse receive buffer
-  int64_t arena_bytes = 0, off_flags = 0, off_recv_fwd = 0, off_recv_rev = 0;
-  int nmax = 1;
-  uint64_t* status = nullptr;  // ST_WORDS words, ordinary device memory
-  bool connected = false;
-  std::vector<void*> opened;  // peer arenas mapped with hipIpcOpenMemHandle
-  IpcRole send_fwd, recv_fwd, send_rev, recv_rev;
-  uint64_t seq[2] = {0, 0};
-  // A receive kernel that waits occupies its hardware queue, and one process has only a few of them (4 by default) for
-  // all its streams.  One process per rank: every rank's send precedes its receive, no cycle.  Several ranks in ONE
-  // process (tests): rank A's waiting receive can sit in front of rank B's send in a shared queue.  There the receive
-  // kernel is posted by *_end, under the in-process contract of the LOCAL transport (every rank's *_begin before any
-  // rank's *_end), so it never waits for a send that has not been queued.
-  bool defer_recv = false;
-  uint64_t pending[2] = {0, 0};
-  uint64_t budget = 0;
-  hipEvent_t ev_sent = nullptr;
-  bool sent_recorded = false, done_recorded = false;  // the events of the exchange in flight were recorded (caller not on the communicator's stream)
-  unsigned* join_counter = nullptr;  // workgroups of a receive kernel that have finished (ipc_kernel_done)
-  int memory_kind = 0;  // 0 fine-grained, 1 uncached, 2 ordinary
-  int fenced = 0;       // FUS_IPC_FENCED=1 at creation: system-scope release / acquire around the flags (ipc_release_system)
-};
-
-inline int64_t ipc_align(int64_t v, int64_t a) { return (v + a - 1) / a * a; }
-
-inline uint64_t* ipc_flag_ptr(char* arena, int64_t off_flags, int nmax, int kind, int slot) {
-  return reinterpret_cast<uint64_t*>(arena + off_flags + ((int64_t)kind * nmax + slot) * kIpcFlagStride);
-}
-
-inline void ipc_role_free(IpcRole& r) {
-  if (r.chunks) (void)hipFree(r.chunks);
-  if (r.peers) (void)hipFree(r.peers);
-  if (r.counters) (void)hipFree(r.counters);
-  r = IpcRole();
-}
-
-// chunk table of one side: every neighbour's segment cut into pieces of kIpcChunk elements
-inline hipError_t ipc_role_init(IpcRole& r, const std::vector<int64_t>& counts, const std::vector<int64_t>& offsets) {
-  std::vector<IpcChunk> ch;
-  r.nnbr = (int)counts.size();
-  r.host_peers.assign(r.nnbr, IpcPeer());
-  for (int k = 0; k < r.nnbr; ++k) {
-    int n = 0;
-    const int chunk = ipc_chunk();
-    for (int64_t s = 0; s < counts[k]; s += chunk, ++n)
-      ch.push_back(IpcChunk{k, (int32_t)std::min<int64_t>(chunk, counts[k] - s), offsets[k] + s});
-    r.host_peers[k].nchunks = n;
-    r.host_peers[k].seg_off = offsets[k];
-  }
-  r.nchunks = (int)ch.size();
-  if (r.nchunks == 0) return hipSuccess;
-  hipError_t e = hipMalloc(&r.chunks, ch.size() * sizeof(IpcChunk));
-  if (e == hipSuccess) e = hipMemcpy(r.chunks, ch.data(), ch.size() * sizeof(IpcChunk), hipMemcpyHostToDevice);
-  if (e == hipSuccess) e = hipMalloc(&r.peers, r.nnbr * sizeof(IpcPeer));
-  if (e == hipSuccess) e = hipMalloc(&r.counters, r.nnbr * sizeof(unsigned));
-  if (e == hipSuccess) e = hipMemset(r.counters, 0, r.nnbr * sizeof(unsigned));
-  return e;
-}
-
-inline hipError_t ipc_role_upload(IpcRole& r) {
-  if (r.nchunks == 0) return hipSuccess;
-  return hipMemcpy(r.peers, r.host_peers.data(), r.nnbr * sizeof(IpcPeer), hipMemcpyHostToDevice);
-}
-
-inline hipError_t ipc_arena_alloc(IpcState& st, int64_t bytes) {
-  // Arena memory: UNCACHED device memory first (what RCCL gives its own peer-to-peer flag / LL buffers on gfx942 / gfx950;
-  // every access of the exchange kernels bypasses the caches anyway, and nothing else may ever find a stale line of it),
-  // then fine-grained, then ordinary memory.  FUS_IPC_MEMORY = uncached | finegrained | coarse picks the first choice
-  // (all three export / open through HIP IPC and pass the two-process probe: profiles/r03a_ipc_probe.log).
-  const char* force = std::getenv("FUS_IPC_MEMORY");
-  const int first = force ? (!std::strcmp(force, "finegrained") ? 0 : !std::strcmp(force, "coarse") ? 2 : 1) : 1;
-  const int order[3] = {first, first == 1 ? 0 : 1, first == 2 ? 0 : 2};
-  hipError_t e = hipErrorOutOfMemory;
-  for (int i = 0; i < 3; ++i) {
-    const int kind = order[i];
-    if (i > 0 && kind == order[0]) continue;
-    void* p = nullptr;
-    e = kind == 0   ? hipExtMallocWithFlags(&p, bytes, hipDeviceMallocFinegrained)
-        : kind == 1 ? hipExtMallocWithFlags(&p, bytes, hipDeviceMallocUncached)
-                    : hipMalloc(&p, bytes);
-    if (e == hipSuccess) {
-      st.arena = static_cast<char*>(p);
-      st.memory_kind = kind;
-      break;
-    }
-    (void)hipGetLastError();
-  }
-  if (e != hipSuccess) return e;
-  st.arena_bytes = bytes;
-  return hipMemset(st.arena, 0, bytes);
 }
 
 }  // namespace fus

@@ -730,6 +730,56 @@ def test_grouped_exchange_two_vectors_in_process_ranks(gpu, ghost_order, transpo
             assert np.allclose(dv[r].cpu().numpy(), ev[r], rtol=0, atol=1e-13)
 
 
+@pytest.mark.parametrize("transport", TRANSPORTS)
+def test_grouped_exchange_mixes_the_cases_of_the_exchange_rule(gpu, transport):
+    """ONE ``begin_group`` per rank whose three halos take different cases of the exchange rule (csrc/halo_layout.hpp
+    ``exchange_ends``): fp64 with ghosts numbered owner by owner (direct: the ghost block is the message), fp64 with permuted
+    ghosts, fp32 with permuted ghosts.  Two in-process ranks; rank 0 ghosts 1 dof of rank 1 and rank 1 ghosts ipc_chunk() + 1 =
+    1025 dofs of rank 0, so every rank has a one-element segment (a one-element chunk) and a 1025-element one (a full chunk and
+    a second chunk of one element).  Forward, then reverse, against numpy; all ranks' begins before any rank's end."""
+    torch = gpu
+    scat = pkg("scatterer")
+    rng = np.random.default_rng(33)
+    R, nlocal = 2, 3000
+    count = {(0, 1): 1, (1, 0): 1025}  # (q, r): q ghosts ``count`` dofs of r
+    picks = {qr: rng.choice(nlocal, size=n, replace=False).astype(np.int64) for qr, n in count.items()}
+    kinds = [(np.float64, False), (np.float64, True), (np.float32, True)]  # (dtype, ghosts permuted)
+    wid = next(_world_ids)
+    comms = [_local_comm(scat, wid, R, r, transport) for r in range(R)]
+    pos, fwd, rev = {}, [], []  # pos[(q, k)]: where the ghosts of rank q's halo k sit in its ghost block
+    for q in range(R):
+        r = 1 - q
+        ng, nown = count[(q, r)], count[(r, q)]
+        plans = []
+        for k, (dt, permuted) in enumerate(kinds):
+            pos[(q, k)] = (rng.permutation(ng) if permuted else np.arange(ng)).astype(np.int64)
+            plans.append(([pos[(q, k)], np.array([ng], dtype=np.int64), np.array([0, ng], dtype=np.int64), np.array([r], dtype=np.int32)],
+                          [picks[(r, q)], np.array([nown], dtype=np.int64), np.array([0, nown], dtype=np.int64), np.array([r], dtype=np.int32)], dt))
+        fwd.append([scat.scatter_forward(comms[q], od, gd, nlocal, dt) for od, gd, dt in plans])
+        rev.append([scat.scatter_reverse(comms[q], od, gd, nlocal, dt) for od, gd, dt in plans])
+    assert [f.direct for f in fwd[1]] == [True, False, False]  # the group of the rank with 1025 ghosts mixes direct and permuted
+    dev = torch.device("cuda", 0)
+    host = [[rng.standard_normal(nlocal + count[(q, 1 - q)]).astype(dt) for dt, _ in kinds] for q in range(R)]
+    for closures, reverse in ((fwd, False), (rev, True)):
+        bufs = [[torch.from_numpy(h).to(dev) for h in host[q]] for q in range(R)]
+        pending = [scat.begin_all([(closures[q][k], bufs[q][k]) for k in range(len(kinds))]) for q in range(R)]
+        for p in pending:
+            for sc, vec, wk in p:
+                sc.end(vec, wk)
+        torch.cuda.synchronize()
+        for q in range(R):
+            r = 1 - q
+            for k, (dt, _) in enumerate(kinds):
+                ref, got = host[q][k].copy(), bufs[q][k].cpu().numpy()
+                if not reverse:  # my ghosts <- their owners' values: pure copies, exact
+                    ref[nlocal + pos[(q, k)]] = host[r][k][picks[(q, r)]]
+                    assert np.array_equal(got, ref), f"forward, rank {q}, halo {k}"
+                else:  # my owned dofs += the values of rank r's ghosts of them
+                    np.add.at(ref, picks[(r, q)], host[r][k][nlocal + pos[(r, k)]])
+                    assert np.allclose(got, ref, rtol=0, atol=1e-14 if dt == np.float64 else 1e-6), f"reverse, rank {q}, halo {k}"
+    assert all(sc.status()["timeouts"] == 0 for q in range(R) for sc in fwd[q] + rev[q])
+
+
 def test_peer_failed_exchange_poisons_the_neighbour(gpu, monkeypatch):
     """In-process world of two ranks.  The ghosting rank posts its forward exchange alone: its receive gives up after
     FUS_IPC_SPIN_SECONDS (time-out, halo dead) and the credit it returns is POISONED.  When the owner posts later, its send
