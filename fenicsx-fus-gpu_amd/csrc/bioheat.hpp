@@ -15,19 +15,18 @@
 // exp2((43 - T) log2 R) in double for an fp32 field too; log2 R is -1 or -2 exactly.  A null pr, s, cem43 or tmax switches the term
 // off (uniform over the launch); ``init`` on LAST WRITES cem43 and tmax instead of updating them, as the monitors' first record.
 //
-// Access shape: field_monitor.hpp (its ld_chunk / st_chunk: one 16-byte access per thread and array, 32-bit offsets from uniform
-// bases, a launch per 2^27 dofs), grid-strided over at most 2048 workgroups, a scalar tail, and the scalar kernel (W = 1) where an
-// operand is not 16-byte aligned.  LAST of an fp32 field takes 2 dofs per thread (8-byte accesses of the field, one 16-byte access
+// Access shape: ld_chunk / st_chunk of vecops.hpp on the device (one 16-byte access per thread and array, 32-bit offsets from uniform
+// bases), stream_shape.hpp on the host (alignment, grid, a launch per 2^27 dofs, the streaming policy): grid-strided over at most
+// 2048 workgroups, a scalar tail, and the scalar kernel (W = 1) where an operand is not 16-byte aligned.  LAST of an fp32 field takes 2 dofs per thread (8-byte accesses of the field, one 16-byte access
 // of the double dose: launch_bioheat_stage).  LAST is a kernel of its own (template parameter): with the three kinds in one kernel
 // the aligned fp64 instantiation needs 103 scalar registers and loses its eighth wave per SIMD.  Updates run over [0, nlocal), b is
-// re-zeroed over [0, ntotal) (owned + ghosts: the next apply adds into it).  vecops.hpp vector_stream decides non-temporal
+// re-zeroed over [0, ntotal) (owned + ghosts: the next apply adds into it).  vector_stream decides non-temporal
 // access.  A dof belongs to one thread: no atomics.
 #pragma once
 
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include "field_monitor.hpp"
 #include "vecops.hpp"
 
 namespace fus {
@@ -147,48 +146,21 @@ inline hipError_t launch_bioheat_stage(T bw, T aw, int kind, T gate, T Ta, doubl
   // (with 4 dofs it is two accesses per lane at a 32-byte stride, each touching half of every cache line); the field arrays then
   // go in 8-byte accesses, still 512 contiguous bytes per wave and instruction.
   constexpr int WLAST = sizeof(T) == 4 ? 2 : W;
-  const bool last = kind == kBioheatLast;
-  if (!last) cem43 = nullptr, tmax = nullptr;
-  uintptr_t bits = 0;
-  for (const void* p : {(const void*)minv, (const void*)pr, (const void*)s, (const void*)b, (const void*)T0, (const void*)Tn,
-                        (const void*)acc, (const void*)cem43, (const void*)tmax})
-    bits |= reinterpret_cast<uintptr_t>(p);
-  const bool aligned = (bits & 15u) == 0;
+  if (kind != kBioheatLast) cem43 = nullptr, tmax = nullptr;
+  const bool aligned = aligned16({minv, pr, s, b, T0, Tn, acc, cem43, tmax});
   const int nt = vector_stream(ntotal * (int64_t)sizeof(T));
-#define FUS_BH_K(W_, NT_, LAST_) \
-  hipLaunchKernelGGL((bioheat_stage_kernel<T, W_, NT_, LAST_>), dim3((unsigned)nblocks), dim3(256), 0, stream, a, (uint32_t)nloc, (uint32_t)len)
-#define FUS_BH(W_, NT_)       \
-  if (last)                   \
-    FUS_BH_K(((W_) == W ? WLAST : (W_)), NT_, true);  \
-  else                        \
-    FUS_BH_K(W_, NT_, false)
-#define FUS_BH_NT(W_) \
-  if (nt == 1) {      \
-    FUS_BH(W_, 1);    \
-  } else if (nt == 2) { \
-    FUS_BH(W_, 2);    \
-  } else {            \
-    FUS_BH(W_, 0);    \
-  }
-  // one launch per kFieldLaunchDofs dofs (a multiple of W: the pieces keep the alignment): the kernel's offsets are 32-bit
-  for (int64_t at = 0; at < ntotal; at += kFieldLaunchDofs) {
-    const int64_t len = ntotal - at < kFieldLaunchDofs ? ntotal - at : kFieldLaunchDofs;
-    const int64_t nloc = nlocal <= at ? 0 : (nlocal - at < len ? nlocal - at : len);
-    const int wl = last ? WLAST : W;
-    const int64_t work = aligned ? (len + wl - 1) / wl : len;
-    int64_t nblocks = (work + 255) / 256;
-    if (nblocks > 2048) nblocks = 2048;
-    const BioheatStageArgs<T> a{bw, aw, gate, Ta, dt / 60.0, minv + at, pr ? pr + at : pr, s ? s + at : s, b + at, T0 + at, Tn + at,
-                                acc + at, cem43 ? cem43 + at : cem43, tmax ? tmax + at : tmax, kind, (int)init};
-    if (aligned) {
-      FUS_BH_NT(W)
-    } else {
-      FUS_BH_NT(1)
-    }
-  }
-#undef FUS_BH_NT
-#undef FUS_BH
-#undef FUS_BH_K
+  flag_dispatch(kind == kBioheatLast, [&](auto last) {  // one launch per kLaunchDofs dofs: the kernel's offsets are 32-bit
+    constexpr bool LAST = decltype(last)::value;
+    for_each_piece(ntotal, kLaunchDofs, [&](int64_t at, int64_t len) {
+      const int64_t nloc = nlocal <= at ? 0 : (nlocal - at < len ? nlocal - at : len);
+      const BioheatStageArgs<T> a{bw, aw, gate, Ta, dt / 60.0, minv + at, piece_of(pr, at), piece_of(s, at), b + at, T0 + at, Tn + at,
+                                  acc + at, piece_of(cem43, at), piece_of(tmax, at), kind, (int)init};
+      shape_dispatch<(LAST ? WLAST : W)>(aligned, nt, [&](auto w, auto t) {
+        hipLaunchKernelGGL((bioheat_stage_kernel<T, decltype(w)::value, decltype(t)::value, LAST>),
+                           dim3(stream_blocks(len, decltype(w)::value, kStreamGridCap)), dim3(256), 0, stream, a, (uint32_t)nloc, (uint32_t)len);
+      });
+    });
+  });
   return hipGetLastError();
 }
 

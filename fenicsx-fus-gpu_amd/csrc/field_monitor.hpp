@@ -10,11 +10,12 @@
 // pointer switches an output off.  ``init`` WRITES the accumulators (pmax = pmin = u, usq = u^2, ...) instead of updating
 // them: the first record of a window needs no fill launches and reads no stale accumulator.
 //
-// Access shape: rk4.hpp / vecops.hpp.  One 16-byte access per thread and array (W = 2 doubles or 4 floats of the field; the
+// Access shape: ld_chunk / st_chunk of vecops.hpp on the device, stream_shape.hpp on the host (alignment, grid, pieces, the
+// streaming policy).  One 16-byte access per thread and array (W = 2 doubles or 4 floats of the field; the
 // double accumulators of an fp32 field are two 16-byte accesses, handled as two halves of 2 dofs so that the fp32 kernel holds
 // no more accumulators in registers than the fp64 one: 8 waves per SIMD at H = 4 for both), grid-strided over at most 2048
 // workgroups (one launch per 2^27 dofs), a scalar tail, and the scalar kernel (W = 1) for operands that are not 16-byte aligned.  Within a half every
-// accumulator load is issued before the first FMA.  Streaming policy: vecops.hpp vector_stream -- above 24 MB every access is
+// accumulator load is issued before the first FMA.  Streaming policy: vector_stream -- above 24 MB every access is
 // non-temporal (nothing is re-read before ~1 GB of other data has passed, and a plain store would leave dirty lines in the
 // memory-side cache that are written back while the next operator runs).  A dof belongs to one thread: no atomics.
 #pragma once
@@ -25,39 +26,6 @@
 #include "vecops.hpp"
 
 namespace fus {
-
-// K consecutive values of S from element ``o`` of ``p`` as one access (K = 1: scalar; K * sizeof(S) = 16 otherwise).  ``p`` is uniform
-// and the byte offset is formed in 32 bits (a launch covers at most kFieldLaunchDofs dofs), so the access is scalar base + one
-// offset register that every array of the same element size shares: 64-bit per-lane addresses of up to 12 arrays would cost the
-// H = 4 kernels their eighth wave per SIMD.
-constexpr int64_t kFieldLaunchDofs = 1ll << 27;
-template <typename S, int K, int NT>
-__device__ __forceinline__ void ld_chunk(const S* p, uint32_t o, S (&r)[K]) {
-  uint32_t ob = o * (uint32_t)sizeof(S);
-  asm volatile("" : "+v"(ob));
-  const char* q = reinterpret_cast<const char*>(p) + ob;
-  if constexpr (K == 1) {
-    r[0] = ld_stream<NT>(reinterpret_cast<const S*>(q));
-  } else {
-    typedef S VN __attribute__((ext_vector_type(K)));
-    const VN t = ld_stream<NT>(reinterpret_cast<const VN*>(q));
-    __builtin_memcpy(r, &t, sizeof(VN));
-  }
-}
-template <typename S, int K, int NT>
-__device__ __forceinline__ void st_chunk(S* p, uint32_t o, const S (&r)[K]) {
-  uint32_t ob = o * (uint32_t)sizeof(S);
-  asm volatile("" : "+v"(ob));
-  char* q = reinterpret_cast<char*>(p) + ob;
-  if constexpr (K == 1) {
-    st_stream<NT>(reinterpret_cast<S*>(q), r[0]);
-  } else {
-    typedef S VN __attribute__((ext_vector_type(K)));
-    VN t;
-    __builtin_memcpy(&t, r, sizeof(VN));
-    st_stream<NT>(reinterpret_cast<VN*>(q), t);
-  }
-}
 
 struct FieldAccumulators {
   double *usq, *vsq, *hre, *him;
@@ -160,47 +128,27 @@ inline hipError_t launch_field_accumulate(const T* u, const T* v, int64_t n, T* 
                                           double* him, int64_t hstride, const double* coef, int H, bool init, hipStream_t stream) {
   if (n <= 0) return hipSuccess;
   constexpr int W = 16 / (int)sizeof(T);
-  uintptr_t bits = 0;
-  for (const void* p : {(const void*)u, (const void*)(vsq ? v : nullptr), (const void*)pmax, (const void*)pmin, (const void*)usq,
-                        (const void*)vsq, (const void*)(H ? hre : nullptr), (const void*)(H ? him : nullptr)})
-    bits |= reinterpret_cast<uintptr_t>(p);
-  const bool aligned = (bits & 15u) == 0 && (H == 0 || (hstride & 1) == 0);  // every row of hre / him 16-byte aligned
+  const bool aligned = aligned16({u, vsq ? v : nullptr, pmax, pmin, usq, vsq, H ? hre : nullptr, H ? him : nullptr}) &&
+                       (H == 0 || (hstride & 1) == 0);  // every row of hre / him 16-byte aligned
   const int nt = vector_stream(n * (int64_t)sizeof(T));
-#define FUS_FM(H_, W_, NT_)                                                                                                              \
-  hipLaunchKernelGGL((field_accumulate_kernel<T, H_, W_, NT_>), dim3((unsigned)nblocks), dim3(256), 0, stream, u + at, vsq ? v + at : v, \
-                     (uint32_t)len, pmax ? pmax + at : pmax, pmin ? pmin + at : pmin, a, coef, (int)init)
-#define FUS_FM_NT(H_, W_) \
-  if (nt == 1)            \
-    FUS_FM(H_, W_, 1);    \
-  else if (nt == 2)       \
-    FUS_FM(H_, W_, 2);    \
-  else                    \
-    FUS_FM(H_, W_, 0)
-#define FUS_FM_W(H_)   \
-  if (aligned) {       \
-    FUS_FM_NT(H_, W);  \
-  } else {             \
-    FUS_FM_NT(H_, 1);  \
+  auto launch = [&](auto h) {  // one launch per kLaunchDofs dofs: the kernel's offsets are 32-bit
+    for_each_piece(n, kLaunchDofs, [&](int64_t at, int64_t len) {
+      const FieldAccumulators a{piece_of(usq, at), piece_of(vsq, at), H ? hre + at : hre, H ? him + at : him, hstride};
+      shape_dispatch<W>(aligned, nt, [&](auto w, auto t) {
+        hipLaunchKernelGGL((field_accumulate_kernel<T, decltype(h)::value, decltype(w)::value, decltype(t)::value>),
+                           dim3(stream_blocks(len, decltype(w)::value, kStreamGridCap)), dim3(256), 0, stream, u + at, vsq ? v + at : v,
+                           (uint32_t)len, piece_of(pmax, at), piece_of(pmin, at), a, coef, (int)init);
+      });
+    });
+  };
+  switch (H) {
+    case 0: launch(std::integral_constant<int, 0>{}); break;
+    case 1: launch(std::integral_constant<int, 1>{}); break;
+    case 2: launch(std::integral_constant<int, 2>{}); break;
+    case 3: launch(std::integral_constant<int, 3>{}); break;
+    case 4: launch(std::integral_constant<int, 4>{}); break;
+    default: return hipErrorInvalidValue;
   }
-  // one launch per kFieldLaunchDofs dofs (a multiple of W: the pieces keep the alignment): the kernel's offsets are 32-bit
-  for (int64_t at = 0; at < n; at += kFieldLaunchDofs) {
-    const int64_t len = n - at < kFieldLaunchDofs ? n - at : kFieldLaunchDofs;
-    const int64_t work = aligned ? (len + W - 1) / W : len;
-    int64_t nblocks = (work + 255) / 256;
-    if (nblocks > 2048) nblocks = 2048;
-    const FieldAccumulators a{usq ? usq + at : usq, vsq ? vsq + at : vsq, H ? hre + at : hre, H ? him + at : him, hstride};
-    switch (H) {
-      case 0: FUS_FM_W(0) break;
-      case 1: FUS_FM_W(1) break;
-      case 2: FUS_FM_W(2) break;
-      case 3: FUS_FM_W(3) break;
-      case 4: FUS_FM_W(4) break;
-      default: return hipErrorInvalidValue;
-    }
-  }
-#undef FUS_FM_W
-#undef FUS_FM_NT
-#undef FUS_FM
   return hipGetLastError();
 }
 

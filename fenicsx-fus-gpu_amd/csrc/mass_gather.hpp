@@ -451,83 +451,52 @@ inline hipError_t gather_static_build(const void* ws, const GatherHeader& h, con
   return hipGetLastError();
 }
 
-template <typename T, int R>
-inline hipError_t launch_mass_gather_static_r(const T* x, const T* cc, T* y, const GatherView& v, const GatherHeader& h, const GatherStatic& gs,
-                                              hipStream_t stream) {
+// ``variant`` (FUS_TUNE_MASS_VARIANT): rows per thread (1, 2, 4; anything else: chosen by size and type)
+template <typename T>
+inline int gather_rows_per_thread(int variant, int64_t nrows) {
+  if (variant == 1 || variant == 2 || variant == 4) return variant;
+  // measured (profiles/r04t_ab_mass_gather.log): below ~0.5 M dofs one row per thread fills the chip best; fp64 two rows
+  // (0.100 ms at config 3, four rows the same, one row 0.117); fp32 four rows from a few M dofs (0.070 against 0.075)
+  return nrows < (1 << 19) ? 1 : ((sizeof(T) == 4 && nrows >= (1 << 22)) ? 4 : 2);
+}
+
+// Non-temporal x / y only where the policy says loads AND stores (NT = 1).
+template <typename T, int R, bool STATIC>
+inline hipError_t launch_mass_gather_r(const T* x, const T* cc, T* y, const T* detJ, const GatherView& v, const GatherHeader& h,
+                                       const GatherStatic& gs, hipStream_t stream) {
   const int64_t nkb = (h.nrows + (int64_t)kGatherThreads * R - 1) / ((int64_t)kGatherThreads * R);
-  const int chunk = (int)((nkb + 7) / 8);
-  const dim3 grid((unsigned)(chunk * 8)), block(kGatherThreads);
-  const int nt = vector_stream(h.nrows * (int64_t)sizeof(T)) == 1 ? 1 : 0;
-#define FUS_GS(NT_, DENSE_) \
-  hipLaunchKernelGGL((mass_gather_kernel<T, NT_, DENSE_, R, true>), grid, block, 0, stream, x, cc, y, (const T*)nullptr, v, 0.0, chunk, nkb, gs)
-  if (h.dense) {
-    if (nt) FUS_GS(1, true);
-    else FUS_GS(0, true);
-  } else {
-    if (nt) FUS_GS(1, false);
-    else FUS_GS(0, false);
-  }
-#undef FUS_GS
+  const int chunk = (int)((nkb + 7) / 8);  // blocks of one XCD
+  const double inv_n = STATIC ? 0.0 : 1.0 / (double)h.N;
+  flag_dispatch(vector_stream(h.nrows * (int64_t)sizeof(T)) == 1, [&](auto nt) {
+    flag_dispatch(h.dense != 0, [&](auto dense) {
+      hipLaunchKernelGGL((mass_gather_kernel<T, decltype(nt)::value, decltype(dense)::value, R, STATIC>), dim3((unsigned)(chunk * 8)),
+                         dim3(kGatherThreads), 0, stream, x, cc, y, detJ, v, inv_n, chunk, nkb, gs);
+    });
+  });
   return hipGetLastError();
+}
+// STATIC: the companion at ``sws`` instead of ``detJ`` (null then)
+template <typename T, bool STATIC>
+inline hipError_t launch_mass_gather_any(const T* x, const T* cc, T* y, const T* detJ, const void* ws, const GatherHeader& h, void* sws,
+                                         hipStream_t stream, int variant) {
+  if (h.nrows == 0) return hipSuccess;
+  const GatherView v = gather_view_of(ws, h);
+  const GatherStatic gs = STATIC ? gather_static_of(sws, h, (int)sizeof(T)) : GatherStatic{nullptr, nullptr, nullptr};
+  switch (gather_rows_per_thread<T>(variant, h.nrows)) {
+    case 1: return launch_mass_gather_r<T, 1, STATIC>(x, cc, y, detJ, v, h, gs, stream);
+    case 4: return launch_mass_gather_r<T, 4, STATIC>(x, cc, y, detJ, v, h, gs, stream);
+    default: return launch_mass_gather_r<T, 2, STATIC>(x, cc, y, detJ, v, h, gs, stream);
+  }
 }
 template <typename T>
 inline hipError_t launch_mass_gather_static(const T* x, const T* cc, T* y, const void* ws, const GatherHeader& h, void* sws, hipStream_t stream,
                                             int variant = 0) {
-  if (h.nrows == 0) return hipSuccess;
-  const GatherView v = gather_view_of(ws, h);
-  const GatherStatic gs = gather_static_of(sws, h, (int)sizeof(T));
-  int rows_per_thread = variant;
-  if (rows_per_thread != 1 && rows_per_thread != 2 && rows_per_thread != 4)
-    rows_per_thread = h.nrows < (1 << 19) ? 1 : ((sizeof(T) == 4 && h.nrows >= (1 << 22)) ? 4 : 2);
-  switch (rows_per_thread) {
-    case 1: return launch_mass_gather_static_r<T, 1>(x, cc, y, v, h, gs, stream);
-    case 4: return launch_mass_gather_static_r<T, 4>(x, cc, y, v, h, gs, stream);
-    default: return launch_mass_gather_static_r<T, 2>(x, cc, y, v, h, gs, stream);
-  }
+  return launch_mass_gather_any<T, true>(x, cc, y, nullptr, ws, h, sws, stream, variant);
 }
-
-template <typename T, int R>
-inline hipError_t launch_mass_gather_r(const T* x, const T* cc, T* y, const T* detJ, const GatherView& v, const GatherHeader& h,
-                                       hipStream_t stream) {
-  const int64_t nkb = (h.nrows + (int64_t)kGatherThreads * R - 1) / ((int64_t)kGatherThreads * R);
-  const int chunk = (int)((nkb + 7) / 8);  // blocks of one XCD
-  const dim3 grid((unsigned)(chunk * 8)), block(kGatherThreads);
-  const double inv_n = 1.0 / (double)h.N;
-  const int nt = vector_stream(h.nrows * (int64_t)sizeof(T)) == 1 ? 1 : 0;
-  if (h.dense) {
-    if (nt)
-      hipLaunchKernelGGL((mass_gather_kernel<T, 1, true, R>), grid, block, 0, stream, x, cc, y, detJ, v, inv_n, chunk, nkb, GatherStatic{nullptr, nullptr, nullptr});
-    else
-      hipLaunchKernelGGL((mass_gather_kernel<T, 0, true, R>), grid, block, 0, stream, x, cc, y, detJ, v, inv_n, chunk, nkb, GatherStatic{nullptr, nullptr, nullptr});
-  } else {
-    if (nt)
-      hipLaunchKernelGGL((mass_gather_kernel<T, 1, false, R>), grid, block, 0, stream, x, cc, y, detJ, v, inv_n, chunk, nkb, GatherStatic{nullptr, nullptr, nullptr});
-    else
-      hipLaunchKernelGGL((mass_gather_kernel<T, 0, false, R>), grid, block, 0, stream, x, cc, y, detJ, v, inv_n, chunk, nkb, GatherStatic{nullptr, nullptr, nullptr});
-  }
-  return hipGetLastError();
-}
-
-// ``variant`` (FUS_TUNE_MASS_VARIANT): rows per thread (1, 2, 4; anything else: chosen by size and type)
 template <typename T>
 inline hipError_t launch_mass_gather(const T* x, const T* cc, T* y, const T* detJ, const void* ws, const GatherHeader& h,
                                      hipStream_t stream, int variant = 0) {
-  if (h.nrows == 0) return hipSuccess;
-  const char* w = static_cast<const char*>(ws);
-  const GatherView v{h.nrows, h.nblocks, h.dense ? nullptr : reinterpret_cast<const int32_t*>(w + h.off_rows),
-                     reinterpret_cast<const uint8_t*>(w + h.off_len), reinterpret_cast<const int32_t*>(w + h.off_base),
-                     reinterpret_cast<const int32_t*>(w + h.off_entries)};
-  int rows_per_thread = variant;
-  if (rows_per_thread != 1 && rows_per_thread != 2 && rows_per_thread != 4) {
-    // measured (profiles/r04t_ab_mass_gather.log): below ~0.5 M dofs one row per thread fills the chip best; fp64 two rows
-    // (0.100 ms at config 3, four rows the same, one row 0.117); fp32 four rows from a few M dofs (0.070 against 0.075)
-    rows_per_thread = h.nrows < (1 << 19) ? 1 : ((sizeof(T) == 4 && h.nrows >= (1 << 22)) ? 4 : 2);
-  }
-  switch (rows_per_thread) {
-    case 1: return launch_mass_gather_r<T, 1>(x, cc, y, detJ, v, h, stream);
-    case 4: return launch_mass_gather_r<T, 4>(x, cc, y, detJ, v, h, stream);
-    default: return launch_mass_gather_r<T, 2>(x, cc, y, detJ, v, h, stream);
-  }
+  return launch_mass_gather_any<T, false>(x, cc, y, detJ, ws, h, nullptr, stream, variant);
 }
 
 }  // namespace fus

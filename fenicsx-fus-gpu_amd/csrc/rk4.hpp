@@ -19,8 +19,6 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include <type_traits>
-
 #include "vecops.hpp"
 
 namespace fus {
@@ -128,7 +126,7 @@ __device__ __forceinline__ Rk4Out<T> rk4_update(int kind, T bw, T aw, const Rk4I
 }
 
 // W dofs per thread as ONE 16-byte access per array where the arrays are 16-byte aligned (W = 2 doubles / 4 floats), scalar
-// otherwise.  NT (vectors far larger than the caches: vecops.hpp vector_stream): EVERY access non-temporal.  The loads: the
+// otherwise.  NT (vectors far larger than the caches: stream_shape.hpp vector_stream): EVERY access non-temporal.  The loads: the
 // pass re-reads nothing before ~1 GB of other data has gone through the caches.  The stores -- un, ku and b included, although
 // the next kernel reads them: a line written with a plain store stays dirty in the memory-side Infinity Cache and is written
 // back WHILE THE OPERATOR RUNS (its launch takes 251-272 us after a plain-store vector pass against 219-222 us after a busy
@@ -138,52 +136,38 @@ __global__ void __launch_bounds__(256)
     rk4_stage_kernel(T bw, T aw, int kind, const T* __restrict__ minv, T* __restrict__ b, T* __restrict__ u,
                      T* __restrict__ v, T* __restrict__ u0, T* __restrict__ v0, T* __restrict__ ku,
                      T* __restrict__ un, int64_t nlocal, int64_t ntotal) {
-  typedef T VW __attribute__((ext_vector_type(W)));  // native vector: what the non-temporal builtins take
-  using V = typename std::conditional<W == 1, T, VW>::type;
   const int64_t stride = (int64_t)gridDim.x * 256 * W;
   for (int64_t i = ((int64_t)blockIdx.x * 256 + threadIdx.x) * W; i < ntotal; i += stride) {
     if (i + W <= nlocal) {
       T rb[W], rm[W], ru[W], rv[W], ru0[W], rv0[W], rku[W];
-      auto ld = [&](const T* p, T(&r)[W], bool nt) {
-        V t = (NT == 1 && nt) ? __builtin_nontemporal_load(reinterpret_cast<const V*>(p + i)) : *reinterpret_cast<const V*>(p + i);
-        __builtin_memcpy(r, &t, sizeof(V));
-      };
-      ld(b, rb, true);
-      ld(minv, rm, true);
+      ld_vec<T, W, NT>(b + i, rb);
+      ld_vec<T, W, NT>(minv + i, rm);
       const Rk4Access a = rk4_access(kind);
-      if (a.rd_u) ld(u, ru, true);
-      if (a.rd_v) ld(v, rv, true);
+      if (a.rd_u) ld_vec<T, W, NT>(u + i, ru);
+      if (a.rd_v) ld_vec<T, W, NT>(v + i, rv);
       if (a.rd_0) {
-        ld(u0, ru0, true);
-        ld(v0, rv0, true);
+        ld_vec<T, W, NT>(u0 + i, ru0);
+        ld_vec<T, W, NT>(v0 + i, rv0);
       }
-      if (a.rd_ku) ld(ku, rku, true);
+      if (a.rd_ku) ld_vec<T, W, NT>(ku + i, rku);
       T ou[W], ov[W], ou0[W], ov0[W], oun[W], oku[W];
 #pragma unroll
       for (int k = 0; k < W; ++k) {
         const Rk4Out<T> o = rk4_update<T>(kind, bw, aw, Rk4In<T>{rb[k], rm[k], ru[k], rv[k], ru0[k], rv0[k], rku[k]});
         ou[k] = o.u, ov[k] = o.v, ou0[k] = o.u0, ov0[k] = o.v0, oun[k] = o.un, oku[k] = o.ku;
       }
-      auto st = [&](T* p, const T(&r)[W], bool nt) {
-        V t;
-        __builtin_memcpy(&t, r, sizeof(V));
-        if (NT != 0 && nt)
-          __builtin_nontemporal_store(t, reinterpret_cast<V*>(p + i));
-        else
-          *reinterpret_cast<V*>(p + i) = t;
-      };
-      if (a.wr_u) st(u, ou, true);
-      if (a.wr_v) st(v, ov, true);
+      if (a.wr_u) st_vec<T, W, NT>(u + i, ou);
+      if (a.wr_v) st_vec<T, W, NT>(v + i, ov);
       if (a.wr_n) {
-        st(un, oun, true);
-        st(ku, oku, true);
+        st_vec<T, W, NT>(un + i, oun);
+        st_vec<T, W, NT>(ku + i, oku);
       }
-      if (a.wr_u0) st(u0, ou0, true);
-      if (a.wr_v0) st(v0, ov0, true);
+      if (a.wr_u0) st_vec<T, W, NT>(u0 + i, ou0);
+      if (a.wr_v0) st_vec<T, W, NT>(v0 + i, ov0);
       T z[W];
 #pragma unroll
       for (int k = 0; k < W; ++k) z[k] = T(0);
-      st(b, z, true);
+      st_vec<T, W, NT>(b + i, z);
     } else {  // the last owned dofs (nlocal not a multiple of W) and the ghost block of b
       for (int64_t j = i; j < i + W && j < ntotal; ++j) {
         if (j < nlocal) {
@@ -206,25 +190,12 @@ template <typename T>
 inline hipError_t launch_rk4_stage(T bw, T aw, int new_step, const T* minv, T* b, T* u, T* v, T* u0, T* v0, T* ku,
                                    T* un, int64_t nlocal, int64_t ntotal, hipStream_t stream) {
   if (ntotal <= 0) return hipSuccess;
-  constexpr int W = 16 / (int)sizeof(T);
-  uintptr_t bits = 0;
-  for (const void* p : {(const void*)minv, (const void*)b, (const void*)u, (const void*)v, (const void*)u0, (const void*)v0, (const void*)ku,
-                        (const void*)un})
-    bits |= reinterpret_cast<uintptr_t>(p);
-  const bool aligned = (bits & 15u) == 0;
-  const int64_t work = aligned ? (ntotal + W - 1) / W : ntotal;
-  int64_t nblocks = (work + 255) / 256;
-  if (nblocks > 4096) nblocks = 4096;
-  const int nt = vector_stream(ntotal * (int64_t)sizeof(T));
-#define FUS_RK4(W_, NT_) \
-  hipLaunchKernelGGL((rk4_stage_kernel<T, W_, NT_>), dim3((unsigned)nblocks), dim3(256), 0, stream, bw, aw, new_step, minv, b, u, v, \
-                     u0, v0, ku, un, nlocal, ntotal)
-  if (aligned) {
-    if (nt == 1) FUS_RK4(W, 1); else if (nt == 2) FUS_RK4(W, 2); else FUS_RK4(W, 0);
-  } else {
-    if (nt == 1) FUS_RK4(1, 1); else if (nt == 2) FUS_RK4(1, 2); else FUS_RK4(1, 0);
-  }
-#undef FUS_RK4
+  const bool aligned = aligned16({minv, b, u, v, u0, v0, ku, un});
+  shape_dispatch<16 / (int)sizeof(T)>(aligned, vector_stream(ntotal * (int64_t)sizeof(T)), [&](auto w, auto nt) {
+    constexpr int W = decltype(w)::value;
+    hipLaunchKernelGGL((rk4_stage_kernel<T, W, decltype(nt)::value>), dim3(stream_blocks(ntotal, W, kStageGridCap)), dim3(256), 0, stream, bw,
+                       aw, new_step, minv, b, u, v, u0, v0, ku, un, nlocal, ntotal);
+  });
   return hipGetLastError();
 }
 

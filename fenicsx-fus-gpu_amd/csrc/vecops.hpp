@@ -6,29 +6,12 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "stream_shape.hpp"
+
 namespace fus {
 
-// Streaming accesses.  A vector kernel on operands far larger than the caches re-reads nothing it touches, and -- what
-// matters -- every line it WRITES with a plain store stays dirty in the 256 MB memory-side Infinity Cache and is written
-// back while the NEXT kernel runs: the headline apply takes 219-222 us after nothing / a busy wait / a 1 GiB read-only
-// stream, 287 us after a 1 GiB fill, 263 us after a 1 GiB copy, 251-272 us after the RK4 vector pass
-// (tools/interleave_probe.py, profiles/r04i_interleave_probe.log).  Non-temporal stores go to memory without lingering.
-// Loads too: most of these kernels update in place (u += ..., y += w x), and a non-temporal store to a line the kernel's own
-// plain load has just brought into the cache hits there and leaves it dirty all the same -- fused RK4 step on one box: cached
-// 1.621 ms, non-temporal stores only 1.569, loads and stores 1.484 (profiles/r04k_ab_vector_stream_policy.log).
-// Kernel template parameter NT: 0 cached accesses, 1 non-temporal loads AND stores, 2 non-temporal stores only.
-// mode (fus_set_tuning FUS_TUNE_VECTOR_STREAM): 0 never; 1 auto = loads and stores for operands > kStreamBytes (default);
-// 2 always loads and stores; 3 auto, stores only; 4 always, stores only
-constexpr int64_t kStreamBytes = 24ll << 20;
-inline int& vector_stream_mode() {
-  static int m = 1;
-  return m;
-}
-inline int vector_stream(int64_t operand_bytes) {
-  const int m = vector_stream_mode();
-  const bool on = m == 2 || m == 4 || ((m == 1 || m == 3) && operand_bytes > kStreamBytes);
-  return !on ? 0 : (m >= 3 ? 2 : 1);
-}
+// Streaming policy (template parameter NT: 0 cached accesses, 1 non-temporal loads AND stores, 2 non-temporal stores only) and the
+// host side of every launch: stream_shape.hpp.
 template <int NT, typename V>
 __device__ __forceinline__ V ld_stream(const V* p) {
   if constexpr (NT == 1)
@@ -44,18 +27,43 @@ __device__ __forceinline__ void st_stream(V* p, V v) {
     *p = v;
 }
 
-template <typename T>
-struct vec16;
-template <>
-struct vec16<double> {
-  using type = double2;
-  static constexpr int W = 2;
-};
-template <>
-struct vec16<float> {
-  using type = float4;
-  static constexpr int W = 4;
-};
+// K consecutive values of S at ``q`` as ONE access (K = 1: scalar; K * sizeof(S) = 16, or 8, otherwise), in registers as an array
+template <typename S, int K, int NT>
+__device__ __forceinline__ void ld_vec(const S* q, S (&r)[K]) {
+  if constexpr (K == 1) {
+    r[0] = ld_stream<NT>(q);
+  } else {
+    typedef S VN __attribute__((ext_vector_type(K)));  // native vector: what the non-temporal builtins take
+    const VN t = ld_stream<NT>(reinterpret_cast<const VN*>(q));
+    __builtin_memcpy(r, &t, sizeof(VN));
+  }
+}
+template <typename S, int K, int NT>
+__device__ __forceinline__ void st_vec(S* q, const S (&r)[K]) {
+  if constexpr (K == 1) {
+    st_stream<NT>(q, r[0]);
+  } else {
+    typedef S VN __attribute__((ext_vector_type(K)));
+    VN t;
+    __builtin_memcpy(&t, r, sizeof(VN));
+    st_stream<NT>(reinterpret_cast<VN*>(q), t);
+  }
+}
+// The same from element ``o`` of ``p``.  ``p`` is uniform and the byte offset is formed in 32 bits (a launch covers at most kLaunchDofs
+// dofs, stream_shape.hpp), so the access is scalar base + one offset register that every array of the same element size shares: 64-bit
+// per-lane addresses of up to 12 arrays would cost the H = 4 kernels of field_monitor.hpp their eighth wave per SIMD.
+template <typename S, int K, int NT>
+__device__ __forceinline__ void ld_chunk(const S* p, uint32_t o, S (&r)[K]) {
+  uint32_t ob = o * (uint32_t)sizeof(S);
+  asm volatile("" : "+v"(ob));
+  ld_vec<S, K, NT>(reinterpret_cast<const S*>(reinterpret_cast<const char*>(p) + ob), r);
+}
+template <typename S, int K, int NT>
+__device__ __forceinline__ void st_chunk(S* p, uint32_t o, const S (&r)[K]) {
+  uint32_t ob = o * (uint32_t)sizeof(S);
+  asm volatile("" : "+v"(ob));
+  st_vec<S, K, NT>(reinterpret_cast<S*>(reinterpret_cast<char*>(p) + ob), r);
+}
 
 template <typename T>
 struct OpAxpy {  // y = alpha x + y
@@ -85,43 +93,22 @@ struct OpSquare {  // out = a * a
   __device__ __forceinline__ T operator()(T a, T) const { return a * a; }
 };
 
-template <typename Op>
-__device__ __forceinline__ double2 apply2(const double2& a, const double2& b, const Op& op) {
-  return double2{op(a.x, b.x), op(a.y, b.y)};
-}
-template <typename Op>
-__device__ __forceinline__ float4 apply2(const float4& a, const float4& b, const Op& op) {
-  return float4{op(a.x, b.x), op(a.y, b.y), op(a.z, b.z), op(a.w, b.w)};
-}
-
 // out[i] = op(a[i], b[i]);  USE_A / USE_B say which inputs are actually read.  NT: streaming (non-temporal) accesses.
 template <typename T, typename Op, bool USE_A, bool USE_B, bool VEC, int NT>
 __global__ void __launch_bounds__(256)
     ew_kernel(const T* __restrict__ a, const T* __restrict__ b, T* __restrict__ out, int64_t n, Op op) {
-  using V = typename vec16<T>::type;
-  constexpr int W = vec16<T>::W;
-  typedef T VN __attribute__((ext_vector_type(W)));  // native vector: what the non-temporal builtins take
+  constexpr int W = 16 / (int)sizeof(T);
   const int64_t stride = (int64_t)gridDim.x * 256;
   const int64_t gid = (int64_t)blockIdx.x * 256 + threadIdx.x;
   if constexpr (VEC) {
     const int64_t nv = n / W;
-    const VN* av = reinterpret_cast<const VN*>(a);
-    const VN* bv = reinterpret_cast<const VN*>(b);
-    VN* ov = reinterpret_cast<VN*>(out);
     for (int64_t i = gid; i < nv; i += stride) {
-      V va{}, vb{};
-      if constexpr (USE_A) {
-        const VN t = ld_stream<NT>(av + i);
-        __builtin_memcpy(&va, &t, sizeof(V));
-      }
-      if constexpr (USE_B) {
-        const VN t = ld_stream<NT>(bv + i);
-        __builtin_memcpy(&vb, &t, sizeof(V));
-      }
-      const V r = apply2(va, vb, op);
-      VN t;
-      __builtin_memcpy(&t, &r, sizeof(V));
-      st_stream<NT>(ov + i, t);
+      T ra[W] = {}, rb[W] = {}, ro[W];
+      if constexpr (USE_A) ld_vec<T, W, NT>(a + i * W, ra);
+      if constexpr (USE_B) ld_vec<T, W, NT>(b + i * W, rb);
+#pragma unroll
+      for (int k = 0; k < W; ++k) ro[k] = op(ra[k], rb[k]);
+      st_vec<T, W, NT>(out + i * W, ro);
     }
     const int64_t i = nv * W + gid;  // tail
     if (i < n) {
@@ -146,8 +133,8 @@ __global__ void __launch_bounds__(256)
 // 47.6 B/dof of gather / scatter.  Opt-in (operators.diagonal_mass_operator), its own bytes contract.
 template <typename T, bool VEC, int NT>
 __global__ void __launch_bounds__(256) muladd_kernel(const T* __restrict__ w, const T* __restrict__ x, T* __restrict__ y, int64_t n) {
-  constexpr int W = vec16<T>::W;
-  typedef T VN __attribute__((ext_vector_type(W)));
+  constexpr int W = 16 / (int)sizeof(T);
+  typedef T VN __attribute__((ext_vector_type(W)));  // arithmetic on the native vector: with ld_vec's arrays fp32 loses its packed FMAs
   const int64_t stride = (int64_t)gridDim.x * 256;
   const int64_t gid = (int64_t)blockIdx.x * 256 + threadIdx.x;
   if constexpr (VEC) {
@@ -168,51 +155,27 @@ __global__ void __launch_bounds__(256) muladd_kernel(const T* __restrict__ w, co
   }
 }
 
+// Both launchers: VEC where every operand that is read or written is 16-byte aligned, at most kStreamGridCap workgroups.
 template <typename T>
 inline hipError_t launch_muladd(const T* w, const T* x, T* y, int64_t n, hipStream_t stream) {
   if (n <= 0) return hipSuccess;
-  constexpr int W = vec16<T>::W;
-  const bool aligned = ((reinterpret_cast<uintptr_t>(w) | reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(y)) & 15u) == 0;
-  const int64_t work = aligned ? (n + W - 1) / W : n;
-  int64_t nblocks = (work + 255) / 256;
-  if (nblocks > 2048) nblocks = 2048;
-  const int nt = vector_stream(n * (int64_t)sizeof(T));
-#define FUS_MA(VEC_, NT_) hipLaunchKernelGGL((muladd_kernel<T, VEC_, NT_>), dim3((unsigned)nblocks), dim3(256), 0, stream, w, x, y, n)
-  if (aligned) {
-    if (nt == 1) FUS_MA(true, 1); else if (nt == 2) FUS_MA(true, 2); else FUS_MA(true, 0);
-  } else {
-    if (nt == 1) FUS_MA(false, 1); else if (nt == 2) FUS_MA(false, 2); else FUS_MA(false, 0);
-  }
-#undef FUS_MA
+  shape_dispatch<16 / (int)sizeof(T)>(aligned16({w, x, y}), vector_stream(n * (int64_t)sizeof(T)), [&](auto wd, auto nt) {
+    constexpr int W = decltype(wd)::value;
+    hipLaunchKernelGGL((muladd_kernel<T, (W > 1), decltype(nt)::value>), dim3(stream_blocks(n, W, kStreamGridCap)), dim3(256), 0, stream, w, x,
+                       y, n);
+  });
   return hipGetLastError();
 }
 
 template <typename T, typename Op, bool USE_A, bool USE_B>
 inline hipError_t launch_ew(const T* a, const T* b, T* out, int64_t n, Op op, hipStream_t stream) {
   if (n <= 0) return hipSuccess;
-  constexpr int W = vec16<T>::W;
-  const bool aligned = ((reinterpret_cast<uintptr_t>(out) | (USE_A ? reinterpret_cast<uintptr_t>(a) : 0) |
-                         (USE_B ? reinterpret_cast<uintptr_t>(b) : 0)) & 15u) == 0;
-  const int64_t work = aligned ? (n + W - 1) / W : n;
-  int64_t nblocks = (work + 255) / 256;
-  if (nblocks > 2048) nblocks = 2048;
-  const int nt = vector_stream(n * (int64_t)sizeof(T));
-#define FUS_EW(VEC_, NT_) \
-  hipLaunchKernelGGL((ew_kernel<T, Op, USE_A, USE_B, VEC_, NT_>), dim3((unsigned)nblocks), dim3(256), 0, stream, a, b, out, n, op)
-#define FUS_EW3(VEC_) \
-  if (nt == 1)        \
-    FUS_EW(VEC_, 1);  \
-  else if (nt == 2)   \
-    FUS_EW(VEC_, 2);  \
-  else                \
-    FUS_EW(VEC_, 0)
-  if (aligned) {
-    FUS_EW3(true);
-  } else {
-    FUS_EW3(false);
-  }
-#undef FUS_EW3
-#undef FUS_EW
+  const bool aligned = aligned16({out, USE_A ? a : nullptr, USE_B ? b : nullptr});
+  shape_dispatch<16 / (int)sizeof(T)>(aligned, vector_stream(n * (int64_t)sizeof(T)), [&](auto wd, auto nt) {
+    constexpr int W = decltype(wd)::value;
+    hipLaunchKernelGGL((ew_kernel<T, Op, USE_A, USE_B, (W > 1), decltype(nt)::value>), dim3(stream_blocks(n, W, kStreamGridCap)), dim3(256), 0,
+                       stream, a, b, out, n, op);
+  });
   return hipGetLastError();
 }
 

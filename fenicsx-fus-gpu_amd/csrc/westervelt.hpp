@@ -387,14 +387,11 @@ inline hipError_t launch_rk4_stage_nl2(T bw, T aw, int kind, const T* m0, const 
                                        T* u0, T* v0, T* ku, T* un, T kappa, T* w, int64_t nlocal, int64_t ntotal,
                                        hipStream_t stream) {
   if (ntotal <= 0) return hipSuccess;
-  int64_t nblocks = (ntotal + 255) / 256;
-  if (nblocks > 4096) nblocks = 4096;
-  const int nt = vector_stream(ntotal * (int64_t)sizeof(T));
-#define FUS_NL2(NT_) \
-  hipLaunchKernelGGL((rk4_stage_nl2_kernel<T, NT_>), dim3((unsigned)nblocks), dim3(256), 0, stream, bw, aw, kind, m0, w2, w5, b, u, v, \
-                     u0, v0, ku, un, kappa, w, nlocal, ntotal)
-  if (nt == 1) FUS_NL2(1); else if (nt == 2) FUS_NL2(2); else FUS_NL2(0);
-#undef FUS_NL2
+  const unsigned nblocks = stream_blocks(ntotal, 1, kStageGridCap);
+  nt_dispatch(vector_stream(ntotal * (int64_t)sizeof(T)), [&](auto nt) {
+    hipLaunchKernelGGL((rk4_stage_nl2_kernel<T, decltype(nt)::value>), dim3(nblocks), dim3(256), 0, stream, bw, aw, kind, m0, w2, w5, b, u,
+                       v, u0, v0, ku, un, kappa, w, nlocal, ntotal);
+  });
   return hipGetLastError();
 }
 
@@ -402,10 +399,8 @@ template <typename T>
 inline hipError_t launch_rk4_stage_nl(T bw, T aw, int new_step, const T* m0, T* m, T* b, T* u, T* v, T* u0, T* v0,
                                       T* ku, T* un, int64_t nlocal, int64_t ntotal, hipStream_t stream) {
   if (ntotal <= 0) return hipSuccess;
-  int64_t nblocks = (ntotal + 255) / 256;
-  if (nblocks > 4096) nblocks = 4096;
-  hipLaunchKernelGGL((rk4_stage_nl_kernel<T>), dim3((unsigned)nblocks), dim3(256), 0, stream, bw, aw, new_step, m0, m,
-                     b, u, v, u0, v0, ku, un, nlocal, ntotal);
+  hipLaunchKernelGGL((rk4_stage_nl_kernel<T>), dim3(stream_blocks(ntotal, 1, kStageGridCap)), dim3(256), 0, stream, bw, aw, new_step, m0,
+                     m, b, u, v, u0, v0, ku, un, nlocal, ntotal);
   return hipGetLastError();
 }
 

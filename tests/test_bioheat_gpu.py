@@ -106,7 +106,7 @@ def test_stage_kernel_against_numpy(kind, dtype, shift):
 
 
 def test_stage_kernel_streaming_size():
-    """3 276 800 fp64 dofs (26.2 MB per operand, above vecops.hpp's 24 MB threshold): the non-temporal instantiation."""
+    """3 276 800 fp64 dofs (26.2 MB per operand, above stream_shape.hpp's 24 MB threshold): the non-temporal instantiation."""
     _stage_case(2, np.float64, 0, 3_276_800, 3_276_800 - 1001, True, True, True, True, False, seed=9)
 
 
