@@ -233,6 +233,11 @@ inline hipError_t launch_westervelt_cell(const T* u, const T* v, const T* c2, co
 
 // Fused RK4 stage vector kernel of the Westervelt solver: as rk4_stage_kernel (rk4.hpp) but the
 // lumped mass changes every stage, so kv = b / m and m is reset to its steady part m0.
+// This kernel and rk4_stage_nl2_kernel below still state the kinds of rk4_table.hpp inline, with every product inside its kind's branch
+// (all FMAs under -ffp-contract=fast; rk4_stage_kernel rounds bw * kv first in its aligned build: test_rk4_stage_roundings).  Versions
+// that call rk4_update by rk4_westervelt_access's flags gave the same bits but were 1 - 6 % slower in several fp32 cases at 10 M dofs
+// (docs/history.md, "The RK4 stage kinds, one table"): the table describes these kernels (tests/host/rk4_table_check.cpp,
+// test_rk4_stage_kinds_equal_the_numpy_table) but they do not call it yet.
 template <typename T>
 __global__ void __launch_bounds__(256)
     rk4_stage_nl_kernel(T bw, T aw, int kind, const T* __restrict__ m0, T* __restrict__ m, T* __restrict__ b,
@@ -242,7 +247,7 @@ __global__ void __launch_bounds__(256)
   for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < ntotal; i += stride) {
     if (i < nlocal) {
       const T kv = b[i] / m[i];
-      if (kind == 2) {  // FIRST (see rk4_stage_kernel, rk4.hpp)
+      if (kind == 2) {  // FIRST (the kinds: rk4_table.hpp)
         const T u0i = u0[i], v0i = v0[i];
         u[i] = u0i + bw * v0i;
         v[i] = v0i + bw * kv;
@@ -302,7 +307,7 @@ __global__ void __launch_bounds__(256)
     if (i < nlocal) {
       T un_new, vn_new;
       if (kind >= 4) {
-        // LEAN set (rk4.hpp: kinds 4, 5, 6, 7 = the four passes of a step; bw = dt / 6, aw = dt / 2): u's accumulator runs one pass
+        // LEAN set (rk4_table.hpp: kinds 4, 5, 6, 7 = the four passes of a step; bw = dt / 6, aw = dt / 2): u's accumulator runs one pass
         // ahead (its increments are the vn's), pass 1 writes no accumulator, pass 3 writes the new u into u0: 46 vector touches per
         // step instead of 52
         const T b2 = bw + bw, a4 = aw + aw;

@@ -145,7 +145,7 @@ for a_ in sys.argv[3:]:
         import bench as bench_py
 
         geo = "geometry" in key
-        files = ("plan.hpp", "stiffness.hpp", "stiffness_plan.hpp") + (("stiffness_geom.hpp",) if geo else ()) + ("mass.hpp", "rk4.hpp", "vecops.hpp")
+        files = ("plan.hpp", "stiffness.hpp", "stiffness_plan.hpp") + (("stiffness_geom.hpp",) if geo else ()) + ("mass.hpp", "rk4.hpp", "rk4_table.hpp", "stream_shape.hpp", "vecops.hpp")
         if key.startswith("westervelt_step"):
             files = files + ("westervelt.hpp",) + (("westervelt_geom.hpp",) if geo else ())
         latest_path = os.path.join(out, "traffic_latest.json")

@@ -4,6 +4,8 @@ own tests (cuda/test_operators.py:213-356: mass, stiffness, boundary-facet mass,
 rel-l2 against a trusted assembly) with the dolfinx assembly replaced by the
 oracle / golden data."""
 
+from fractions import Fraction
+
 import numpy as np
 import pytest
 
@@ -1597,3 +1599,156 @@ def test_lean_rk4_stage_kinds_equal_the_reference_sequence(gpu, dtype, westervel
     x = t(rhs[0])
     assert getattr(lib, f"fus_rk4_stage_{suf}")(0.1, 0.1, 8, x.data_ptr(), x.data_ptr(), x.data_ptr(), x.data_ptr(), x.data_ptr(), x.data_ptr(), x.data_ptr(),
                                             x.data_ptr(), nl, n, None) == -1
+
+
+def _rk4_table_numpy(kind, bw, aw, kv, x):
+    """The stage kinds of csrc/rk4_table.hpp, stated again in numpy in the field's dtype: {vector: new values} of what kind ``kind`` writes
+    (b's zeroing apart) from the vectors ``x`` and this stage's kv."""
+    u, v, u0, v0, ku = x["u"], x["v"], x["u0"], x["v0"], x["ku"]
+    b2, a4 = bw + bw, aw + aw
+    if kind in (0, 1):  # MIDDLE; legacy: the new (u, v) also become (u0, v0)
+        un, vn = u + bw * ku, v + bw * kv
+        s0, t0 = (un, vn) if kind == 1 else (u0, v0)
+        out = {"u": un, "v": vn, "un": s0 + aw * ku, "ku": t0 + aw * kv}
+        return dict(out, u0=un, v0=vn) if kind == 1 else out
+    if kind == 2:  # FIRST
+        return {"u": u0 + bw * v0, "v": v0 + bw * kv, "un": u0 + aw * v0, "ku": v0 + aw * kv}
+    if kind == 3:  # LAST
+        return {"u0": u + bw * ku, "v0": v + bw * kv}
+    if kind == 4:
+        return {"un": u0 + aw * v0, "ku": v0 + aw * kv}
+    if kind == 5:
+        vn3 = v0 + aw * kv
+        return {"v": (v0 + (ku - v0) * (bw / aw)) + b2 * kv, "u": ((u0 + bw * v0) + b2 * ku) + b2 * vn3, "un": u0 + aw * ku, "ku": vn3}
+    if kind == 6:
+        vn4 = v0 + a4 * kv
+        return {"v": v + b2 * kv, "u0": u + bw * vn4, "un": u0 + a4 * ku, "ku": vn4}
+    return {"v0": v + bw * kv}  # 7
+
+
+@pytest.mark.parametrize("entry", ["stage", "nl2", "nl2_w", "nl"])
+@pytest.mark.parametrize("dtype", [np.float64, np.float32], ids=["f64", "f32"])
+def test_rk4_stage_kinds_equal_the_numpy_table(gpu, dtype, entry):
+    """Every stage kind of every entry point (``fus_rk4_stage_*`` 0 ... 7, ``fus_rk4_stage_nl2_*`` 0 ... 7 without and with the ``w`` output,
+    ``fus_rk4_stage_nl_*`` 0 ... 3) through the C ABI against a numpy statement of the kind in the field's dtype, to 1e-14 / 1e-6 of the output vector's
+    largest magnitude (the kernels contract a * b + c to one FMA and round the quotient their own way: a few ulp of the terms).  Every input is drawn from
+    [0.5, 1.5) and both coefficients are positive, so no output is a difference of its terms and the few-ulp bound holds for the single dof of n = 1 as
+    well.  Sizes: below, at and above one 16-byte group and one block, a scalar tail of the owned range and a ghost block of ``b``; operands 16-byte aligned
+    and shifted by one element (the scalar build of ``rk4_stage_kernel``).  What a kind does not write is bitwise untouched, also beyond nlocal and
+    outside the operand; ``b`` is zero over [0, n); ``m`` is m0 over the owned range and 0 beyond."""
+    import torch
+
+    lib_mod = pkg("_lib")
+    lib = lib_mod.load()
+    suf = "f64" if dtype == np.float64 else "f32"
+    tol = 1e-14 if dtype == np.float64 else 1e-6
+    rng = np.random.default_rng(29)
+    bw, aw, kappa = dtype(0.3), dtype(0.7), dtype(0.25)
+    mass = {"stage": ["minv"], "nl": ["m0", "m"]}.get(entry, ["m0", "w2", "w5"])
+    names = mass + ["b", "u", "v", "u0", "v0", "ku", "un"] + (["w"] if entry.startswith("nl2") else [])
+    for n in (1, 2, 3, 255, 257, 4099):
+        nl = n - min(n // 7, 5)
+        for off in (0, 1):
+            for kind in range(4 if entry == "nl" else 8):
+                host = {k: rng.uniform(0.5, 1.5, n + off + 1).astype(dtype) for k in names}  # one element before (off = 1) and one after the operand
+                if "w2" in host:
+                    host["w2"] *= dtype(0.01)
+                dev = {k: torch.from_numpy(a).cuda() for k, a in host.items()}
+                p = {k: t[off:].data_ptr() for k, t in dev.items()}
+                vecs = [p[k] for k in ("b", "u", "v", "u0", "v0", "ku", "un")]
+                if entry == "stage":
+                    rc = getattr(lib, f"fus_rk4_stage_{suf}")(bw, aw, kind, p["minv"], *vecs, nl, n, lib_mod.stream_ptr())
+                elif entry == "nl":
+                    rc = getattr(lib, f"fus_rk4_stage_nl_{suf}")(bw, aw, kind, p["m0"], p["m"], *vecs, nl, n, lib_mod.stream_ptr())
+                else:
+                    rc = getattr(lib, f"fus_rk4_stage_nl2_{suf}")(bw, aw, kind, p["m0"], p["w2"], p["w5"], *vecs, kappa, p["w"] if entry == "nl2_w" else None,
+                                                               nl, n, lib_mod.stream_ptr())
+                assert rc == 0
+                x = {k: a[off:off + nl] for k, a in host.items()}  # the owned range
+                if entry == "stage":
+                    kv = x["b"] * x["minv"]
+                elif entry == "nl":
+                    kv = x["b"] / x["m"]
+                else:  # (u_n, v_n): the stage's inputs
+                    s, t = (x["u0"], x["v0"]) if kind in (2, 4) else (x["un"], x["ku"])
+                    kv = (x["b"] + x["w5"] * t * t) / (x["m0"] + x["w2"] * s)
+                new = _rk4_table_numpy(kind, bw, aw, kv, x)
+                assert all(a.dtype == dtype for a in new.values())
+                if entry == "nl2_w":  # the next stage's inputs
+                    s, t = (new["u0"], new["v0"]) if kind == 3 else (x["u0"], new["v0"]) if kind == 7 else (new["un"], new["ku"])
+                    new["w"] = s + kappa * t
+                for k in names:
+                    where = f"{entry} {suf} kind {kind} n {n} offset {off}: {k}"
+                    got, want = dev[k].cpu().numpy(), host[k].copy()
+                    if k == "b":
+                        want[off:off + n] = 0
+                    elif k == "m":
+                        want[off:off + nl], want[off + nl:off + n] = host["m0"][off:off + nl], 0
+                    elif k in new:
+                        err = float(np.abs(got[off:off + nl].astype(np.float64) - new[k].astype(np.float64)).max())
+                        assert err <= tol * float(np.abs(new[k]).max()), f"{where}: {err:.3e} of {float(np.abs(new[k]).max()):.3e}"
+                        want[off:off + nl] = got[off:off + nl]
+                    assert np.array_equal(got, want), where
+
+
+def _round_exact(x, dtype):
+    """The exact rational ``x`` rounded to nearest in ``dtype``, or None where ``x`` lies half way between two neighbours."""
+    c = dtype(float(x))
+    d = abs(Fraction(float(c)) - x)
+    others = [abs(Fraction(float(np.nextafter(c, dtype(s) * np.inf))) - x) for s in (-1, 1)]
+    return c if d < min(others) else None
+
+
+@pytest.mark.parametrize("dtype", [np.float64, np.float32], ids=["f64", "f32"])
+def test_rk4_stage_roundings(gpu, dtype):
+    """Which rounding of ``v + bw * kv`` (kinds 0 ... 3; kind 2: ``v0 + bw * kv``, kind 3 writes it to ``v0``) each entry point gives.  The library is
+    built with -ffp-contract=fast, and what contracts is decided by the shape of the compiled code: the Westervelt passes hold every product inside the
+    branch of its kind and form ONE FMA; in the linear pass the compiler may hoist the product that kinds 0 ... 3 share above the kind branches, where it
+    is rounded before the sum (seen on an MI355X: its 16-byte build does so in all four kinds, its scalar build for shifted operands fuses kind 0).
+    Results of earlier versions are reproduced bit for bit only while this holds, so a Westervelt pass that stops fusing fails here, and so does
+    the linear pass's 16-byte build if it stops rounding the product first; of its scalar build (kinds 1 ... 3 not recorded) the test asks that it
+    takes ONE of the two roundings in every dof, and prints which.  kv is made exact (minv = m = m0 = 1, w2 = w5 = 0:
+    kv = b), both roundings are worked out in exact rational arithmetic, dofs where they agree (or where an exact value is a tie) say nothing and
+    are left out."""
+    import torch
+
+    lib_mod = pkg("_lib")
+    lib = lib_mod.load()
+    suf = "f64" if dtype == np.float64 else "f32"
+    rng = np.random.default_rng(41)
+    n, bw, aw = 1027, dtype(0.3), dtype(0.7)
+    for off in (0, 1):
+        for kind in range(4):
+            # the two roundings differ where the rounding error of the product moves the sum across a rounding boundary: a product of the sum's
+            # magnitude and a much smaller v (about a quarter of the dofs tell)
+            host = {k: (rng.uniform(0.5, 1.5, n + off) * (8.0 if k == "b" else 1 / 64)).astype(dtype) for k in ("b", "u", "v", "u0", "v0", "ku", "un")}
+            base = host["v0"] if kind == 2 else host["v"]
+            fused, split = [], []
+            for x, kv in zip(base[off:], host["b"][off:]):
+                prod = Fraction(float(bw)) * Fraction(float(kv))
+                fused.append(_round_exact(Fraction(float(x)) + prod, dtype))
+                p = _round_exact(prod, dtype)
+                split.append(None if p is None else _round_exact(Fraction(float(x)) + Fraction(float(p)), dtype))
+            tell = np.array([f is not None and s is not None and f != s for f, s in zip(fused, split)])
+            assert tell.sum() > n // 20, "the inputs must distinguish the two roundings"
+            fused, split = (np.array([dtype(0) if x is None else x for x in r])[tell] for r in (fused, split))
+            one, zero = (torch.full((n + off,), c, dtype=torch.from_numpy(base).dtype, device="cuda") for c in (1.0, 0.0))
+            for entry, want in (("stage", split if off == 0 else None), ("nl", fused), ("nl2", fused)):
+                dev = {k: torch.from_numpy(a).cuda() for k, a in host.items()}
+                m = one.clone()
+                p = {k: t[off:].data_ptr() for k, t in dev.items()}
+                vecs = [p[k] for k in ("b", "u", "v", "u0", "v0", "ku", "un")]
+                o, z = one[off:].data_ptr(), zero[off:].data_ptr()
+                if entry == "stage":
+                    rc = getattr(lib, f"fus_rk4_stage_{suf}")(bw, aw, kind, o, *vecs, n, n, lib_mod.stream_ptr())
+                elif entry == "nl":
+                    rc = getattr(lib, f"fus_rk4_stage_nl_{suf}")(bw, aw, kind, o, m[off:].data_ptr(), *vecs, n, n, lib_mod.stream_ptr())
+                else:
+                    rc = getattr(lib, f"fus_rk4_stage_nl2_{suf}")(bw, aw, kind, o, z, z, *vecs, dtype(0), None, n, n, lib_mod.stream_ptr())
+                assert rc == 0
+                got = dev["v0" if kind == 3 else "v"].cpu().numpy()[off:][tell]
+                print(f"{entry} {suf} kind {kind} offset {off}: {int(tell.sum())} telling dofs, {int((got == fused).sum())} fused, {int((got == split).sum())} product rounded first")
+                if want is None:  # the linear pass's scalar build: one rounding or the other, the same in every dof
+                    assert np.array_equal(got, fused) or np.array_equal(got, split), f"{entry} {suf} kind {kind} offset {off}"
+                else:
+                    assert np.array_equal(got, want), f"{entry} {suf} kind {kind} offset {off}"

@@ -94,12 +94,16 @@ def main(argv=None):
                 case(f"{tag} copy", [al[1]], lambda L: f(L, "copy")(p[0], p[1], n, sp()), reps)
                 case(f"{tag} fill", [al[1]], lambda L: f(L, "fill")(1.0, p[1], n, sp()), reps, host=host)
                 case(f"{tag} muladd", [al[2]], lambda L: f(L, "muladd")(p[0], p[1], p[2], n, sp()), reps)
-                for kind in (0, 4, 7):
+                for kind in range(8):
                     case(f"{tag} rk4_stage kind {kind}", al[1:8], lambda L: f(L, "rk4_stage")(1e-9, 1e-9, kind, *p[:8], n - 7, n, sp()), reps, host=host and kind == 0)
                 case(f"{tag} rk4_stage kind 0, shifted operands", sh[1:8], lambda L: f(L, "rk4_stage")(1e-9, 1e-9, 0, *q[:8], n - 7, n, sp()), reps)
-                case(f"{tag} rk4_stage_nl2 kind 0", al[3:11], lambda L: f(L, "rk4_stage_nl2")(1e-9, 1e-9, 0, *p[:10], 0.25, p[10], n - 7, n, sp()), reps,
-                     host=host)
-                case(f"{tag} rk4_stage_nl kind 0", al[1:9], lambda L: f(L, "rk4_stage_nl")(1e-9, 1e-9, 0, *p[:9], n - 7, n, sp()), reps, host=host)
+                for kind in range(8):
+                    case(f"{tag} rk4_stage_nl2 kind {kind}", al[3:11], lambda L: f(L, "rk4_stage_nl2")(1e-9, 1e-9, kind, *p[:10], 0.25, p[10], n - 7, n, sp()), reps,
+                         host=host and kind == 0)
+                    case(f"{tag} rk4_stage_nl2 kind {kind}, no w", al[3:11], lambda L: f(L, "rk4_stage_nl2")(1e-9, 1e-9, kind, *p[:10], 0.25, None, n - 7, n, sp()), reps)
+                case(f"{tag} rk4_stage_nl2 kind 0, shifted operands", sh[3:11], lambda L: f(L, "rk4_stage_nl2")(1e-9, 1e-9, 0, *q[:10], 0.25, q[10], n - 7, n, sp()), reps)
+                for kind in range(4):
+                    case(f"{tag} rk4_stage_nl kind {kind}", al[1:9], lambda L: f(L, "rk4_stage_nl")(1e-9, 1e-9, kind, *p[:9], n - 7, n, sp()), reps, host=host and kind == 0)
                 # bioheat: minv pr s b T0 Tn acc | cem43 tmax
                 cem = torch.zeros(n, dtype=torch.float64, device="cuda")
                 for kind, nm in ((0, "FIRST"), (2, "LAST")):
