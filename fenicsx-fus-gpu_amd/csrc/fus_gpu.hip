@@ -20,6 +20,7 @@
 #include "probe.hpp"
 #include "rk4.hpp"
 #include "source_array.hpp"
+#include "sponge.hpp"
 #include "stiffness.hpp"
 #include "vecops.hpp"
 #include "westervelt.hpp"
@@ -236,6 +237,18 @@ int facet_terms(T* y, const T* cA1, T sA1, const T* cA2, T sA2, const T* scalars
   if (nentB > 0 && (!xB || !cB || !detJB || !dmB)) return FUS_ERR_INVALID_ARGUMENT;
   return hip_rc(fus::launch_facet_terms<T>(y, cA1, sA1, cA2, sA2, detJA, dmA, nentA, xB, cB, detJB, dmB, nentB, N,
                                            static_cast<hipStream_t>(stream), dev ? scalars : nullptr));
+}
+
+// sponge-layer damping terms of a stage (csrc/sponge.hpp): every check before any device work; n == 0 is a no-op
+template <typename T>
+int sponge_terms(T* y, const T* u, const T* v, const int32_t* idx, const T* cu, const T* cv, int64_t n, void* stream) {
+  if (n < 0) return FUS_ERR_INVALID_ARGUMENT;
+  if (n == 0) return FUS_OK;
+  if (!y || !u || !v || !idx || !cu || !cv) return FUS_ERR_INVALID_ARGUMENT;
+  if (misaligned(y, sizeof(T)) || misaligned(u, sizeof(T)) || misaligned(v, sizeof(T)) || misaligned(idx, sizeof(int32_t)) ||
+      misaligned(cu, sizeof(T)) || misaligned(cv, sizeof(T)))
+    return FUS_ERR_INVALID_ARGUMENT;
+  return hip_rc(fus::launch_sponge_terms<T>(y, u, v, idx, cu, cv, n, static_cast<hipStream_t>(stream)));
 }
 
 template <typename T>
@@ -639,6 +652,9 @@ int fus_plan_mark_exclusive(void* workspace, int N, int entities_per_batch, int6
   int fus_rk4_stage_nl2_##SUF(T bw, T aw, int new_step, const T* m0, const T* w2, const T* w5, T* b, T* u, T* v, T* u0, T* v0, T* ku,      \
                               T* un, T kappa, T* w, int64_t nlocal, int64_t ntotal, void* s) {                                             \
     return rk4_stage_nl2<T>(bw, aw, new_step, m0, w2, w5, b, u, v, u0, v0, ku, un, kappa, w, nlocal, ntotal, s);                           \
+  }                                                                                                                                        \
+  int fus_sponge_terms_##SUF(T* y, const T* u, const T* v, const int32_t* idx, const T* cu, const T* cv, int64_t n, void* s) {            \
+    return sponge_terms<T>(y, u, v, idx, cu, cv, n, s);                                                                                    \
   }                                                                                                                                        \
   int fus_bioheat_stage_##SUF(T bw, T aw, int kind, T gate, T t_a, double dt, const T* minv, const T* pr, const T* src, T* b, T* T0,       \
                               T* Tn, T* acc, double* cem43, T* tmax, int init, int64_t nlocal, int64_t ntotal, void* s) {                  \

@@ -41,6 +41,9 @@ def main():
                     help="split the source face x = 0 into NY x NZ elements (sources.SourceArray) with delays that focus on --focus, and "
                          "report the peak pressure at the focus and along the x axis through it, recorded on the device every step")
     ap.add_argument("--focus", default=None, metavar="X,Y,Z", help="focal point of --array in m (default: the centre of the box)")
+    ap.add_argument("--sponge", type=int, default=0, metavar="CELLS",
+                    help="absorbing sponge layer of CELLS cells inside the four lateral faces (y and z), which the reference leaves rigid "
+                         "(sponge.SpongeLayer: one sparse damping launch per stage); default 0: off")
     a = ap.parse_args()
     if a.focus and not a.array:
         ap.error("--focus needs --array")
@@ -89,9 +92,19 @@ def main():
         axis = np.stack([np.linspace(0.0, L, 64), np.full(64, focus[1]), np.full(64, focus[2])], axis=1)
         pts = np.concatenate([focus[None, :], axis])
         probes = (pts, sens.PointSensors(mesh, pts, float_type, peak=True))
+    sponge = None
+    if a.sponge:
+        sp = fusgpu_loader.submodule("sponge")
+        if not 0 < a.sponge <= num_element // 2:
+            raise SystemExit(f"--sponge: 1 .. {num_element // 2} cells")
+        # the GLOBAL box, so every rank evaluates the same profile on its own dofs
+        sponge = sp.SpongeLayer(sp.box_profile((0.0, 0.0, 0.0), mesh.length, a.sponge * domain_length / num_element, sp.LATERAL, speed_of_sound))
     solver = ls.LinearSpectral3D(mesh, float_type, speed_of_sound, density, source_frequency, source_amplitude,
-                                 comm=comm, fused=not a.reference_sequence, source=source)
+                                 comm=comm, fused=not a.reference_sequence, source=source, sponge=sponge)
     solver.init()
+    if sponge is not None:
+        n_layer = solver._sponge[0].numel()
+        print(f"Sponge layer (rank {rank}): {a.sponge} cell(s) wide, {n_layer} owned dofs, sigma_max dt = {sponge.sigma_max * dt:.3f}", flush=True)
     if rank == 0:
         print("Solve!", flush=True)
     torch.cuda.synchronize()

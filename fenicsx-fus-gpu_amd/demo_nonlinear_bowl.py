@@ -65,6 +65,9 @@ def main():
                     help="implies --field-stats (without a FILE.npz nothing is written): after the acoustic run, heat soft tissue for SECONDS_ON "
                          "with the heat deposition q of the last period and cool it for SECONDS_OFF (bioheat.BioheatSpectral3D: Pennes' equation, "
                          "CEM43 thermal dose); prints the peak temperature, the focus of the dose and the volume above 240 CEM43")
+    ap.add_argument("--sponge", type=int, default=0, metavar="CELLS",
+                    help="absorbing sponge layer of CELLS cells inside the four lateral faces (y and z), which the reference leaves rigid "
+                         "(sponge.SpongeLayer: one sparse damping launch per stage); default 0: off")
     a = ap.parse_args()
     if a.thermal is not None and (len(a.thermal) > 2 or min(a.thermal) < 0.0):
         ap.error("--thermal SECONDS_ON [SECONDS_OFF], both >= 0")
@@ -139,10 +142,21 @@ def main():
                                  n_elements=ny * nz)
         if rank == 0:
             print(f"Array elements: {ny} x {nz}, focus: {tuple(float(v) for v in focus)}", flush=True)
+    sponge = None
+    if a.sponge:
+        sp = fusgpu_loader.submodule("sponge")
+        if not 0 < a.sponge <= num_element // 2:
+            raise SystemExit(f"--sponge: 1 .. {num_element // 2} cells")
+        # the GLOBAL box, so every rank evaluates the same profile on its own dofs
+        sponge = sp.SpongeLayer(sp.box_profile((0.0, 0.0, 0.0), mesh.length, a.sponge * L / num_element, sp.LATERAL, speed_of_sound))
     solver = nls.WesterveltSpectral3D(mesh, float_type, speed_of_sound, density, source_frequency, source_amplitude,
                                       nonlinear_coefficient, attenuation_coefficient_dB, comm=comm, fused=not a.reference_sequence, source=source,
+                                      sponge=sponge,
                                       in_kernel_geometry=True if (a.in_kernel_geometry or a.geometry == "kernel") else ("auto" if a.geometry == "auto" else False))
     solver.init()
+    if sponge is not None:
+        n_layer = solver._sponge[0].numel()
+        print(f"Sponge layer (rank {rank}): {a.sponge} cell(s) wide, {n_layer} owned dofs, sigma_max dt = {sponge.sigma_max * dt:.3f}", flush=True)
 
     # sampling set: the owned dofs on the mid-z plane of the global dof grid
     lex = mesh.global_lexicographic_ids()[: mesh.nlocal]

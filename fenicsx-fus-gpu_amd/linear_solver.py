@@ -54,7 +54,8 @@ class LinearSpectral3D(SpectralSolver3D):
     def __init__(self, mesh, float_type=np.float64, speed_of_sound=1500.0, density=1000.0,
                  source_frequency=0.5e6, source_amplitude=60000.0, comm=None, fused=True,
                  source_time="tn", overlap=True, halo_kernels=None, affine="auto", in_kernel_geometry="auto",
-                 halo_plan=None, defer_setup_exchange=False, reference_speed_of_sound=None, keep_G=False, source=None):
+                 halo_plan=None, defer_setup_exchange=False, reference_speed_of_sound=None, keep_G=False, source=None,
+                 sponge=None):
         """``speed_of_sound`` / ``density``: scalars, or one value per cell (heterogeneous medium: the DG0 material arrays of
         the reference's drivers, in the caller's cell order).  ``reference_speed_of_sound``: the c of the source term
         ``p0 w0 / c cos(w0 t)`` (cuda/demo_linear_box.py:515-530 uses the scalar of its homogeneous medium); default: the
@@ -65,9 +66,12 @@ class LinearSpectral3D(SpectralSolver3D):
         (numba-cpu/precompute.py:115-163), ``True`` forces the kernel form for any degree.  ``keep_G``: keep the G array on the
         device although the apply does not read it (``solver.G_array``).  ``source``: a ``sources.SourceArray`` (phased array:
         per-element amplitude, phase and delay, optionally a burst) in place of the one scalar waveform of ``source_value``;
-        bound to this rank's source facets here (``self.source``), ``None`` keeps every launch as it is."""
+        bound to this rank's source facets here (``self.source``), ``None`` keeps every launch as it is.  ``sponge``: a
+        ``sponge.SpongeLayer`` (absorbing layer: b -= 2 sigma m v_n + sigma^2 m u_n over its owned dofs, one sparse launch per stage
+        after the facet terms); ``None`` keeps every launch as it is."""
         c_cells, rho_cells = per_cell(speed_of_sound, mesh, "speed_of_sound"), per_cell(density, mesh, "density")
         bd1, bd2, D, G_d, detJ_d, (dF1_d, dF2_d) = self._init_common(mesh, float_type, comm, fused, source_time)
+        self._init_sponge(sponge)
         self.c0, self.rho0 = float(c_cells.mean()), float(rho_cells.mean())
         self.rho_cells, self.c_cells = rho_cells, c_cells  # per cell, the mesh's cell order (intensity.py)
         self.f0, self.p0 = float(source_frequency), float(source_amplitude)
@@ -132,6 +136,7 @@ class LinearSpectral3D(SpectralSolver3D):
         yield from self._reverse_setup([self.m])
         ops.fill(1.0, self.minv)
         ops.pointwise_divide(self.minv, self.m, self.minv)  # owned entries are what the fused kernel reads
+        self._bind_sponge(self.m)  # m is complete only now
 
     def source_value(self, t):
         """Window x p0 w0 / c0 x cos(w0 t) (cuda/demo_linear_box.py:515-530)."""
@@ -172,6 +177,7 @@ class LinearSpectral3D(SpectralSolver3D):
             else:  # the array's source facets alone (no set B): replaces filling g and its facet mass apply
                 ops.facet_source_terms(self.b, self.source, None, stage=self.source.stage_scalars(ts))
             self._mass_facet_stage(self.v_n, self.facet_coeff2, self.b, self.detJ_f2, self.fdm2)
+            self._sponge_terms(self.u_n, self.v_n)
 
         yield from self._cell_terms(self.u_n, self.v_n, facets)
         ops.pointwise_divide(self.b, self.m, self.kv)

@@ -32,7 +32,7 @@ class WesterveltSpectral3D(SpectralSolver3D):
                  source_frequency=1.1e6, source_amplitude=None, nonlinear_coefficient=3.5,
                  attenuation_coefficient_dB=0.2, comm=None, source_time="tn", overlap=True, fused=False,
                  in_kernel_geometry="auto", uniform_ratio="auto", halo_plan=None, defer_setup_exchange=False,
-                 reference_speed_of_sound=None, reference_density=None, keep_G=False, source=None):
+                 reference_speed_of_sound=None, reference_density=None, keep_G=False, source=None, sponge=None):
         """``speed_of_sound``, ``density``, ``nonlinear_coefficient``, ``attenuation_coefficient_dB``: scalars, or one value per
         cell in the caller's cell order (the DG0 material arrays of cuda/demo_nonlinear_bowl.py:166-178 -- water / skull / ...).
         ``reference_speed_of_sound`` / ``reference_density``: the scalars of the source term and of the default source amplitude
@@ -42,11 +42,14 @@ class WesterveltSpectral3D(SpectralSolver3D):
         ``in_kernel_geometry``: ``"auto"`` (default) -- the fused stage of degree >= 3 forms G in the cell kernel from the 8
         vertices of each (trilinear) cell and the G array is dropped unless ``keep_G``; ``False``: the reference's G stream;
         the reference launch sequence (``fused=False``) always reads G.  ``source``: a ``sources.SourceArray`` (phased array) in
-        place of the one waveform of ``source_values``, as ``LinearSpectral3D``; ``None`` keeps every launch as it is."""
+        place of the one waveform of ``source_values``, as ``LinearSpectral3D``; ``None`` keeps every launch as it is.  ``sponge``: a
+        ``sponge.SpongeLayer`` (absorbing layer), as ``LinearSpectral3D``, with the steady lumped mass m0 in its coefficients -- the
+        effective damping is then 2 sigma m0 / (m0 + w2 u_n), by definition; ``None`` keeps every launch as it is."""
         c_cells, rho_cells = per_cell(speed_of_sound, mesh, "speed_of_sound"), per_cell(density, mesh, "density")
         beta_cells = per_cell(nonlinear_coefficient, mesh, "nonlinear_coefficient")
         att_cells = per_cell(attenuation_coefficient_dB, mesh, "attenuation_coefficient_dB")
         bd1, bd2, D, G_d, detJ_d, (dF1_d, dF2_d) = self._init_common(mesh, float_type, comm, fused, source_time)
+        self._init_sponge(sponge)
         self.f0 = float(source_frequency)
         self.w0 = 2 * np.pi * self.f0
         pick = (lambda a: float(a[bd1[:, 0]].mean())) if bd1.shape[0] else (lambda a: float(a.mean()))
@@ -160,6 +163,7 @@ class WesterveltSpectral3D(SpectralSolver3D):
 
     def setup_schedule(self):
         yield from self._reverse_setup((self.m0, self.w2, self.w5))
+        self._bind_sponge(self.m0)  # m0 is complete only now
 
     def source_values(self, t):
         """g and dg/dt (cuda/demo_nonlinear_bowl.py:560-595)."""
@@ -246,6 +250,7 @@ class WesterveltSpectral3D(SpectralSolver3D):
         else:  # the array's g and dg terms in one launch (no set B)
             ops.facet_source_terms(self.b, self.source, None, stage=self.source.stage_scalars(ts))
         self.mass_facet(self.v_n, self.fc2_2, self.b, self.dF2, self.fdm2)
+        self._sponge_terms(self.u_n, self.v_n)
         if self.halo is not None:
             self.halo.rev(self.b)
         ops.pointwise_divide(self.b, self.m, self.kv)

@@ -626,6 +626,33 @@ def facet_source_terms(y, bound_array, field, stage=None, stage_dev=None):
     _lib.check(fn(*args, st.ctypes.data, _lib.stream_ptr()), "fus_facet_source_array")
 
 
+def sponge_terms(y, u, v, bound):
+    """The sponge layer's damping terms of one RK4 stage in one launch over the layer's dofs (csrc/sponge.hpp,
+    ``fus_sponge_terms_*``): with ``bound = (idx, cu, cv)`` of ``sponge.SpongeLayer.bind``,
+
+        y[idx] -= cv v[idx] + cu u[idx]
+
+    ``(u, v)`` the stage's inputs, ``y`` its right-hand side.  The adds are float atomics (next to a halo the launch runs while
+    the interior cells add into the same y).  An empty list is a no-op."""
+    idx, cu, cv = bound
+    dt = y.dtype if isinstance(y, torch.Tensor) else None
+    for name, t in (("y", y), ("u", u), ("v", v), ("cu", cu), ("cv", cv)):
+        _req(t, dt, name)
+    _req(idx, torch.int32, "idx")
+    n = idx.numel()
+    if cu.numel() != n or cv.numel() != n:
+        raise ValueError("sponge_terms: one cu and one cv per list entry")
+    if u.numel() != y.numel() or v.numel() != y.numel():
+        raise ValueError("sponge_terms: y, u and v must have the same number of entries")
+    if any(t.device != y.device for t in (u, v, idx, cu, cv)):
+        raise ValueError("sponge_terms: every operand must be on y's device")
+    if n == 0:
+        return
+    fn = getattr(_lib.load(), f"fus_sponge_terms_{_lib.suffix(dt)}")
+    _lib.check(fn(y.data_ptr(), u.data_ptr(), v.data_ptr(), idx.data_ptr(), cu.data_ptr(), cv.data_ptr(), int(n), _lib.stream_ptr()),
+               "fus_sponge_terms")
+
+
 # ----------------------------------------------------------------- cell operators
 def _to_device(a, dtype):
     """Host array or tensor -> contiguous tensor of ``dtype`` on the current device."""

@@ -10,6 +10,10 @@ physics through hooks:
   ``_source_scalars(t)``                ``(s1, s2)`` of the source facet term at time ``t``
   ``_source_set`` / ``_absorbing_set``  ``(c1, c2 or None, detJ, dofmap)`` / ``(c, detJ, dofmap)`` of the two facet sets
 
+With ``sponge=`` (an absorbing layer, sponge.py) a stage has one more launch, ``_sponge_terms(u_n, v_n)`` over the layer's owned
+dofs: appended to ``facets()`` in the fused stage, after the facet applies in ``_stage_reference``; a solver calls ``_init_sponge``
+in its constructor and ``_bind_sponge(mass)`` at the end of ``setup_schedule``, when its lumped mass is complete.
+
 ``rk4_schedule`` and ``rk4_graph`` record through one hook, ``_recording`` (the steps and their factors: ``recording.py``);
 ``run_schedule`` drives one rank's schedule generator to its value (``rk4``, ``bioheat.py``, ``field_monitor.py``), ``run_lockstep``
 those of several ranks of one process.  ``MeshSolver3D`` is the set-up these solvers share with ``bioheat.py``.
@@ -206,6 +210,25 @@ class SpectralSolver3D(MeshSolver3D):
         bd2 = mesh.boundary_facets([getattr(mesh, "absorbing_tag", 3)])
         return (bd1, bd2) + self._init_mesh(mesh, float_type, comm, (bd1, bd2))
 
+    # -- absorbing sponge layer (sponge.py): one sparse launch per stage, placed with the facet terms ----------------------
+    def _init_sponge(self, sponge):
+        """``sponge``: a ``sponge.SpongeLayer`` or None.  Its list of this rank's owned layer dofs is built here (host); its
+        coefficients need the COMPLETE lumped mass, so they are bound at the end of ``setup_schedule`` (``_bind_sponge``)."""
+        self.sponge, self._sponge = sponge, None
+        self._sponge_list = None if sponge is None else sponge.build(self.mesh)
+
+    def _bind_sponge(self, mass):
+        if self.sponge is not None:
+            self._sponge = self.sponge.bind(mass, self.tdt, self.dev, built=self._sponge_list)
+
+    def _sponge_terms(self, u_n, v_n):
+        """b[j] -= cv[j] v_n[j] + cu[j] u_n[j] over the layer's owned dofs; nothing without a layer."""
+        if self.sponge is None:
+            return
+        if self._sponge is None:
+            raise _lib.FusGpuError("sponge layer: the set-up exchange (setup_schedule) has not run, the layer is not bound yet")
+        ops.sponge_terms(self.b, u_n, v_n, self._sponge)
+
     def init(self):
         """u = v = 0 (cuda/demo_linear_box.py:434-435)."""
         for t in (self.u, self.v, self.ku, self.kv):
@@ -243,6 +266,13 @@ class SpectralSolver3D(MeshSolver3D):
 
             def facets():
                 ops.facet_terms(self.b, (c1, s1, c2, s2, detJ, dofmap), field, scalars=scalars)
+
+        if self.sponge is not None:  # the layer's launch follows the facet launch wherever a schedule (or a capture) places that
+            facet_launch = facets
+
+            def facets():
+                facet_launch()
+                self._sponge_terms(u_n, v_n)
 
         yield from self._cell_terms(u_n, v_n, facets)
 

@@ -153,6 +153,23 @@ int fus_facet_terms_dev_f32(float* y, const float* cA1, const float* cA2, const 
                             const int32_t* dmB, int64_t nentB, int ndof_per_entity, void* stream);
 
 /*
+ * The absorbing sponge layer's damping terms of one RK4 stage in one launch over the layer's dofs only (csrc/sponge.hpp):
+ * the layer is  u'' + 2 sigma u' + sigma^2 u = (undamped right-hand side),  sigma >= 0 and zero outside it; with the diagonal
+ * (GLL-collocated) mass m, per list entry k with j = idx[k]:
+ *   y[j] -= cv[k] v[j] + cu[k] u[j]          cv = 2 sigma_j m_j,   cu = sigma_j^2 m_j
+ *   idx      int32[n]   local indices of the owned dofs with sigma > 0, ascending (NOT checked here, as dofmaps are not:
+ *                       sponge.SpongeLayer builds them)
+ *   cu, cv   T[n]       the coefficients above        u, v   the stage's inputs        y   the stage's right-hand side b
+ * The adds are float atomics (the launch may run next to a stiffness apply into the same y).  n == 0 is a no-op; every
+ * argument is a fixed pointer or a constant, so the launch is captured with the step (hipGraph).  The reference has no
+ * counterpart: its domain ends in rigid walls everywhere but on the one tagged absorbing face.
+ */
+int fus_sponge_terms_f64(double* y, const double* u, const double* v, const int32_t* idx, const double* cu, const double* cv,
+                         int64_t n, void* stream);
+int fus_sponge_terms_f32(float* y, const float* u, const float* v, const int32_t* idx, const float* cu, const float* cv, int64_t n,
+                         void* stream);
+
+/*
  * Phased-array source facets (csrc/source_array.hpp): fus_facet_terms_* with a per-element source value instead of one
  * scalar for the whole source set.  Source facet f belongs to element e = element_of_facet[f] in [0, nelem), or -1
  * (inactive; the ids are NOT checked here, as dofmaps are not: sources.SourceArray validates them when it binds).  With

@@ -82,7 +82,7 @@ def cached_remarks():
 
 
 def main():
-    pats = [re.compile(p) for p in sys.argv[1:]] or [re.compile("stiffness_plan|westervelt_cell")]
+    pats = [re.compile(p) for p in sys.argv[1:]] or [re.compile("stiffness_plan|westervelt_cell|sponge_terms")]
     table = parse(cached_remarks())
     for name, d in table.items():
         if any(p.search(name) for p in pats):
