@@ -26,24 +26,21 @@ def main():
     ap.add_argument("--nreps", type=int, default=10)
     ap.add_argument("--threads", type=int, default=1)
     a = ap.parse_args()
-    from conftest import build_problem, pkg
-    from oracle import oracle_c
+    from conftest import build_problem
+    from oracle import oracle_c, rk4_oracle
 
     try:
         oracle_c.build(native=True)
         O = oracle_c.OracleLib(native=True)
     except Exception:
         O = oracle_c.OracleLib()
-    P, n = a.degree, a.degree + 1
+    P = a.degree
     pb = build_problem(P, a.cells, random_constants=False)
     mesh = pb["mesh"]
     print(f"Number of degrees-of-freedom: {mesh.ndofs_global}")
-    gll, pre = pkg("gll"), pkg("precompute")
     bd = mesh.boundary_facets()
     fdm = mesh.facet_dofmap(bd)
-    dF = np.zeros((bd.shape[0], n * n))
-    pre.compute_boundary_facets_scaled_jacobian_determinant(
-        dF, (mesh.x_dofs, mesh.x_g), bd, pre.tabulate_facet_gradients(pb["pts"]), gll.tensor_weights_2d(pb["wts"]))
+    dF = rk4_oracle.host_facet_detJ(mesh, bd)
     fc = np.ones(bd.shape[0])
     b = np.zeros(mesh.ndofs)
     u1 = np.ones(mesh.ndofs)

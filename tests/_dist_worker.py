@@ -19,8 +19,7 @@ sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 
 import fusgpu_loader  # noqa: E402
-from conftest import ref_field  # noqa: E402
-from halo_cpu import OracleHaloKernels, global_cell_constants  # noqa: E402
+from halo_cpu import OracleHaloKernels, rank_inputs  # noqa: E402
 
 
 class StagedComm:
@@ -75,18 +74,9 @@ def main():
     assert world == gx * gy * gz
     if mode in ("gpu-solver", "gpu-solver-nl"):
         return run_solver(outdir, P, (nx, ny, nz), (gx, gy, gz), overlap, nonlinear=mode.endswith("nl"))
-    boxmesh, gll, pre = (fusgpu_loader.submodule(m) for m in ("boxmesh", "gll", "precompute"))
-    scat = fusgpu_loader.submodule("scatterer")
+    boxmesh, gll, scat = (fusgpu_loader.submodule(m) for m in ("boxmesh", "gll", "scatterer"))
     mesh = boxmesh.BoxMesh(P, (nx, ny, nz), grid=(gx, gy, gz), rank=rank, perturb=0.16, seed=3)
-    pts, wts, D = gll.tabulate_1d(P)
-    n = P + 1
-    w3 = gll.tensor_weights_3d(wts)
-    dg = pre.tabulate_hex_p1_gradients(gll.tensor_points_3d(pts))
-    G = np.zeros((mesh.ncells, n**3, 6))
-    pre.compute_scaled_geometrical_factor(G, (mesh.x_dofs, mesh.x_g), mesh.ncells, dg, w3)
-    cc = global_cell_constants(mesh)
-    x = ref_field(mesh.dof_coordinates())
-    x[mesh.nlocal:] = -777.0  # ghosts are stale until the forward scatter
+    D = gll.tabulate_1d(P)[2]
     comm = scat.TorchComm()
     if mode == "cpu":
         from oracle.oracle_c import OracleLib
@@ -105,9 +95,9 @@ def main():
         ops = fusgpu_loader.submodule("operators")
         op = ops.stiffness_operator(P, D.flatten(), np.float64)
         halo = scat.HaloApply(mesh, op, StagedComm(comm), np.float64, overlap=bool(overlap))
-    x_d = torch.from_numpy(x).to(dev)
-    y_d = torch.zeros(mesh.ndofs, dtype=torch.float64, device=dev)
-    halo.apply(x_d, torch.from_numpy(cc).to(dev), y_d, torch.from_numpy(G).to(dev), torch.from_numpy(mesh.dofmap).to(dev))
+    rk = rank_inputs(mesh, dev)  # ghosts are stale until the forward scatter
+    x_d, y_d = rk["x"], rk["y"]
+    halo.apply(x_d, rk["cc"], y_d, rk["G"], rk["dm"])
     if dev.type == "cuda":
         torch.cuda.synchronize()
     lex = mesh.global_lexicographic_ids()

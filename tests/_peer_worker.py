@@ -45,8 +45,8 @@ def main():
     import torch.distributed as dist
 
     import fusgpu_loader
-    from conftest import build_problem, pkg, ref_field, rel_l2
-    from halo_cpu import global_cell_constants
+    from conftest import build_problem, pkg, rel_l2
+    from halo_cpu import global_cell_constants, rank_inputs
 
     torch.cuda.set_device(0)
     dev = torch.device("cuda", 0)
@@ -98,19 +98,11 @@ def main():
         assert int(np.prod(grid)) == world
         from oracle.oracle_c import OracleLib
 
-        ops, gll, pre = pkg("operators"), pkg("gll"), pkg("precompute")
-        pts, wts, D = gll.tabulate_1d(P)
-        n = P + 1
+        ops, gll = pkg("operators"), pkg("gll")
         mesh = boxmesh.BoxMesh(P, cells, grid=grid, rank=rank, perturb=0.16, seed=3, ghost_order=ghost_order)
-        G = np.zeros((mesh.ncells, n**3, 6))
-        pre.compute_scaled_geometrical_factor(G, (mesh.x_dofs, mesh.x_g), mesh.ncells,
-                                              pre.tabulate_hex_p1_gradients(gll.tensor_points_3d(pts)), gll.tensor_weights_3d(wts))
-        x = ref_field(mesh.dof_coordinates())
-        x[mesh.nlocal:] = -777.0  # ghosts are stale until the forward scatter
-        x_d, y_d = torch.from_numpy(x).to(dev), torch.zeros(mesh.ndofs, dtype=torch.float64, device=dev)
-        cc_d, G_d = torch.from_numpy(global_cell_constants(mesh)).to(dev), torch.from_numpy(G).to(dev)
-        dm_d = torch.from_numpy(mesh.dofmap).to(dev)
-        op = ops.stiffness_operator(P, D.flatten(), np.float64)
+        rk = rank_inputs(mesh, dev)  # ghosts are stale until the forward scatter
+        x_d, y_d, cc_d, G_d, dm_d = (rk[k] for k in ("x", "y", "cc", "G", "dm"))
+        op = ops.stiffness_operator(P, gll.tabulate_1d(P)[2].flatten(), np.float64)
         halo = scat.HaloApply(mesh, op, comm, np.float64, schedule=schedule)  # plan: index exchange over gloo
         assert halo.schedule_kind == schedule
         for _ in range(2):
@@ -260,11 +252,11 @@ def hybrid(args, proc, nproc, dev):
     import torch
     import torch.distributed as dist
 
-    from conftest import build_problem, pkg, ref_field, rel_l2
-    from halo_cpu import global_cell_constants
+    from conftest import build_problem, pkg, rel_l2
+    from halo_cpu import global_cell_constants, rank_inputs
     from oracle.oracle_c import OracleLib
 
-    scat, boxmesh, utils, ops, gll, pre, ls = (pkg(m) for m in ("scatterer", "boxmesh", "utils", "operators", "gll", "precompute", "linear_solver"))
+    scat, boxmesh, utils, ops, gll, ls = (pkg(m) for m in ("scatterer", "boxmesh", "utils", "operators", "gll", "linear_solver"))
     P = int(args[0])
     cells, grid = tuple(int(v) for v in args[1:4]), tuple(int(v) for v in args[4:7])
     ghost_order = args[7] if args[7] in ("owner", "lex") else int(args[7])
@@ -282,20 +274,10 @@ def hybrid(args, proc, nproc, dev):
 
     lockstep = pkg("solver_base").run_lockstep
     if what == "apply":
-        pts, wts, D = gll.tabulate_1d(P)
-        n = P + 1
-        w3, dg = gll.tensor_weights_3d(wts), pre.tabulate_hex_p1_gradients(gll.tensor_points_3d(pts))
-        op = ops.stiffness_operator(P, D.flatten(), np.float64)
+        op = ops.stiffness_operator(P, gll.tabulate_1d(P)[2].flatten(), np.float64)
         comms, halos, ranks = [], [], []
         for r in mine:
-            mesh = meshes[r]
-            G = np.zeros((mesh.ncells, n**3, 6))
-            pre.compute_scaled_geometrical_factor(G, (mesh.x_dofs, mesh.x_g), mesh.ncells, dg, w3)
-            x = ref_field(mesh.dof_coordinates())
-            x[mesh.nlocal:] = -777.0
-            ranks.append(dict(mesh=mesh, x=torch.from_numpy(x).to(dev), y=torch.zeros(mesh.ndofs, dtype=torch.float64, device=dev),
-                              cc=torch.from_numpy(global_cell_constants(mesh)).to(dev), G=torch.from_numpy(G).to(dev),
-                              dm=torch.from_numpy(mesh.dofmap).to(dev)))
+            ranks.append(rank_inputs(meshes[r], dev))
             comms.append(scat.NativeComm(local=(4242, R, r), transport="peer", hosted=mine))
         for r, rk, comm in zip(mine, ranks, comms):  # closures in the same order in every process: rank-local index 0, 1, ...
             halos.append(scat.HaloApply(rk["mesh"], op, comm, np.float64, plan=(od[r], gd[r]), schedule="concurrent"))

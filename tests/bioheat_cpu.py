@@ -5,7 +5,7 @@ sequence and the same dose rule in numpy, fp64, on ``oracle.oracle_np.stiffness_
 import numpy as np
 
 from conftest import pkg
-from oracle import oracle_np
+from oracle import oracle_np, rk4_oracle
 
 A = (0.0, 0.5, 0.5, 1.0)
 B = (1.0 / 6.0, 1.0 / 3.0, 1.0 / 3.0, 1.0 / 6.0)
@@ -63,16 +63,9 @@ class CpuBioheat:
     product w_b rho_b C_b.  ``fixed``: local dof indices held at their initial value."""
 
     def __init__(self, mesh, k, rho_c, w=0.0, Ta=37.0, fixed=()):
-        gll, pre = pkg("gll"), pkg("precompute")
         self.mesh, self.P, self.Ta = mesh, mesh.P, float(Ta)
-        P, n, nc = mesh.P, mesh.P + 1, mesh.ncells
-        pts, wts, D = gll.tabulate_1d(P, np.float64)
-        w3 = gll.tensor_weights_3d(wts).astype(np.float64)
-        dphi = pre.tabulate_hex_p1_gradients(gll.tensor_points_3d(pts), np.float64)
-        gm = (mesh.x_dofs, mesh.x_g.astype(np.float64))
-        self.G, self.detJ, self.D = np.zeros((nc, n**3, 6)), np.zeros((nc, n**3)), D
-        pre.compute_scaled_geometrical_factor(self.G, gm, nc, dphi, w3)
-        pre.compute_scaled_jacobian_determinant(self.detJ, gm, nc, dphi, w3)
+        nc = mesh.ncells
+        self.G, self.detJ, self.D = rk4_oracle.host_G(mesh), rk4_oracle.host_detJ(mesh), pkg("gll").tabulate_1d(mesh.P, np.float64)[2]
         cell = lambda v: np.full(nc, float(v)) if np.ndim(v) == 0 else np.asarray(v, dtype=np.float64)  # noqa: E731
         self.k = cell(k)
         self.mc, self.mw, self.vol = self.lumped(cell(rho_c)), self.lumped(cell(w)), self.lumped(np.ones(nc))

@@ -5,7 +5,8 @@ CPU tensors.  Backed by the ORACLE; never imported by the product."""
 import numpy as np
 import torch
 
-from oracle import oracle_np
+from conftest import ref_field
+from oracle import oracle_np, rk4_oracle
 
 
 class OracleHaloKernels:
@@ -35,3 +36,21 @@ def global_cell_constants(mesh, dtype=np.float64):
     """Rank-independent per-cell constants (function of the global cell index)."""
     ijk = mesh._cell_ijk + np.array([mesh.cell_range[a][0] for a in range(3)])[None, :]
     return (1.0 + 0.1 * ((ijk[:, 0] * 7 + ijk[:, 1] * 3 + ijk[:, 2]) % 5)).astype(dtype)
+
+
+def stale_ghost_input(mesh):
+    """The reference's test field on one rank's dofs, its ghost entries stale (-777) until a forward scatter refreshes them."""
+    x = ref_field(mesh.dof_coordinates())
+    x[mesh.nlocal:] = -777.0
+    return x
+
+
+def rank_inputs(mesh, dev, factor="G"):
+    """One rank's operands of a partitioned fp64 apply as tensors on ``dev``: the stale-ghost input ``x``, a zero ``y``, the
+    rank-independent cell constants ``cc``, the dofmap ``dm`` and the cells' geometry factor under its name, ``G`` (stiffness) or
+    ``detJ`` (mass), from the oracle's host recipe (rk4_oracle.host_G / host_detJ; conftest.build_problem, which makes the serial
+    side of these comparisons, keeps its own copy)."""
+    geom = {"G": rk4_oracle.host_G, "detJ": rk4_oracle.host_detJ}[factor](mesh)
+    to = lambda a: torch.from_numpy(a).to(dev)  # noqa: E731
+    return {"mesh": mesh, "x": to(stale_ghost_input(mesh)), "y": torch.zeros(mesh.ndofs, dtype=torch.float64, device=dev),
+            "cc": to(global_cell_constants(mesh)), factor: to(geom), "dm": to(mesh.dofmap)}

@@ -9,25 +9,24 @@ import itertools
 import numpy as np
 import pytest
 
-from conftest import build_problem, pkg, rel_l2, ref_field
-from halo_cpu import global_cell_constants
+from conftest import build_problem, pkg, rel_l2
+from halo_cpu import global_cell_constants, stale_ghost_input
+from oracle import rk4_oracle
 
 _world_ids = itertools.count(5000)
 
 
 def mock_dolfinx_rank(P, cells, grid, rank, seed):
     """One rank's data as a dolfinx driver would see it, scrambled from BoxMesh."""
-    boxmesh, gll, pre = pkg("boxmesh"), pkg("gll"), pkg("precompute")
+    boxmesh, gll = pkg("boxmesh"), pkg("gll")
     mesh = boxmesh.BoxMesh(P, cells, grid=grid, rank=rank, perturb=0.16, seed=3, ghost_order=seed)
     rng = np.random.default_rng(100 * seed + rank)
     n = P + 1
     cperm = rng.permutation(mesh.ncells)                     # cells in arbitrary order
     sigma = np.random.default_rng(seed).permutation(n**3)    # the element's dof_ordering (same on all ranks)
     dofmap_std = mesh.dofmap[cperm][:, sigma]                # V.dofmap.list on the standard element
-    pts, wts, D = gll.tabulate_1d(P)
-    G = np.zeros((mesh.ncells, n**3, 6))
-    pre.compute_scaled_geometrical_factor(G, (mesh.x_dofs, mesh.x_g), mesh.ncells, pre.tabulate_hex_p1_gradients(gll.tensor_points_3d(pts)),
-                                          gll.tensor_weights_3d(wts))
+    D = gll.tabulate_1d(P)[2]
+    G = rk4_oracle.host_G(mesh)
     return dict(mesh=mesh, dofmap_std=dofmap_std, dof_ordering=sigma, G=G[cperm], cc=global_cell_constants(mesh)[cperm],
                 x_dofs=mesh.x_dofs[cperm], D=D)
 
@@ -63,9 +62,8 @@ def test_partitioned_apply_through_adaptor_cpu(oracle_c, P, cells, grid):
     nl = [rm.nlocal for rm, _, _ in rms]
     xs = []
     for rk, (rm, _, _) in zip(ranks, rms):
-        x = ref_field(rk["mesh"].dof_coordinates())
-        x[rm.nlocal:] = -777.0
-        xs.append(x)
+        assert rm.nlocal == rk["mesh"].nlocal
+        xs.append(stale_ghost_input(rk["mesh"]))
     oracle_np.scatter_forward_all(xs, od, gd, nl)
     ys = []
     for rk, (rm, G, cc), x in zip(ranks, rms, xs):
@@ -105,8 +103,8 @@ def test_partitioned_apply_through_adaptor_gpu(oracle_c, P, cells, grid):
     op = ops.stiffness_operator(P, ranks[0]["D"].flatten(), np.float64)
     state = []
     for r, (rk, (rm, (G, cc))) in enumerate(zip(ranks, parts)):
-        x = ref_field(rk["mesh"].dof_coordinates())
-        x[rm.nlocal:] = -777.0
+        assert rm.nlocal == rk["mesh"].nlocal
+        x = stale_ghost_input(rk["mesh"])
         halo = scat.HaloApply(rm, op, scat.NativeComm(local=(wid, R, r)), np.float64, plan=(od[r], gd[r]))
         state.append(dict(halo=halo, x=torch.from_numpy(x).to(dev), y=torch.zeros(rm.ndofs, dtype=torch.float64, device=dev),
                           cc=torch.from_numpy(cc).to(dev), G=torch.from_numpy(G).to(dev), dm=torch.from_numpy(rm.dofmap).to(dev)))
@@ -175,7 +173,7 @@ def test_duck_typed_index_map_end_to_end_on_reference_plans(oracle_c, fixture):
     from conftest import GOLDEN
     from oracle import oracle_np
 
-    ad, utils, boxmesh, gll, pre = (pkg(m) for m in ("dolfinx_adaptor", "utils", "boxmesh", "gll", "precompute"))
+    ad, utils, boxmesh, gll = (pkg(m) for m in ("dolfinx_adaptor", "utils", "boxmesh", "gll"))
     d = np.load(os.path.join(GOLDEN, fixture + ".npz"))
     P, shape, grid = int(d["P"]), tuple(int(v) for v in d["shape"]), tuple(int(v) for v in d["grid"])
     go = str(d["ghost_order"])
@@ -189,20 +187,15 @@ def test_duck_typed_index_map_end_to_end_on_reference_plans(oracle_c, fixture):
         assert np.array_equal(od[r][0], d[f"owners_idx_{r}"]) and np.array_equal(od[r][3], d[f"unique_owners_{r}"])
         assert np.array_equal(gd[r][0], d[f"ghosts_idx_{r}"]) and np.array_equal(gd[r][3], d[f"unique_ghosts_{r}"])
     # end to end: scrambled cells -> partition_for_overlap(duck-typed map) -> exchange + operator == serial
-    n = P + 1
-    pts, wts, D = gll.tabulate_1d(P)
+    D = gll.tabulate_1d(P)[2]
     od, gd = utils.compute_scatterer_data_all(ims)
     xs, rms = [], []
     for r, m in enumerate(meshes):
-        G = np.zeros((m.ncells, n**3, 6))
-        pre.compute_scaled_geometrical_factor(G, (m.x_dofs, m.x_g), m.ncells, pre.tabulate_hex_p1_gradients(gll.tensor_points_3d(pts)),
-                                              gll.tensor_weights_3d(wts))
+        G = rk4_oracle.host_G(m)
         cperm = np.random.default_rng(r).permutation(m.ncells)
         rm, (Gp, ccp) = ad.partition_for_overlap(m.dofmap[cperm], ims[r], (G[cperm], global_cell_constants(m)[cperm]))
         assert rm.index_map is ims[r] and rm.nlocal == m.nlocal and rm.nghost == m.nghost
-        x = ref_field(m.dof_coordinates())
-        x[m.nlocal:] = -777.0
-        xs.append(x)
+        xs.append(stale_ghost_input(m))
         rms.append((rm, Gp, ccp))
     nl = [m.nlocal for m in meshes]
     oracle_np.scatter_forward_all(xs, od, gd, nl)

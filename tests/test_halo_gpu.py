@@ -21,7 +21,8 @@ import numpy as np
 import pytest
 
 from conftest import build_problem, golden_files, pkg, rel_l2, ref_field
-from halo_cpu import global_cell_constants
+from halo_cpu import global_cell_constants, rank_inputs
+from oracle import rk4_oracle
 
 pytestmark = pytest.mark.gpu
 
@@ -212,25 +213,13 @@ def test_partitioned_apply_async_transport_one_gpu(gpu, oracle_c, P, cells, grid
     torch = gpu
     schedule = overlap if overlap else "split"
     overlap = bool(overlap)
-    boxmesh, scat, ops, gll, pre = (pkg(m) for m in ("boxmesh", "scatterer", "operators", "gll", "precompute"))
+    boxmesh, scat, ops, gll = (pkg(m) for m in ("boxmesh", "scatterer", "operators", "gll"))
     R = int(np.prod(grid))
     wid = next(_world_ids)
     dev = torch.device("cuda", 0)
-    pts, wts, D = gll.tabulate_1d(P)
-    n = P + 1
-    w3 = gll.tensor_weights_3d(wts)
-    dg = pre.tabulate_hex_p1_gradients(gll.tensor_points_3d(pts))
-    op = ops.stiffness_operator(P, D.flatten(), np.float64)
-    ranks = []
-    for r in range(R):
-        mesh = boxmesh.BoxMesh(P, cells, grid=grid, rank=r, perturb=0.16, seed=3, ghost_order=ghost_order)
-        G = np.zeros((mesh.ncells, n**3, 6))
-        pre.compute_scaled_geometrical_factor(G, (mesh.x_dofs, mesh.x_g), mesh.ncells, dg, w3)
-        x = ref_field(mesh.dof_coordinates())
-        x[mesh.nlocal:] = -777.0  # ghosts are stale until the forward scatter
-        ranks.append(dict(mesh=mesh, x=torch.from_numpy(x).to(dev), y=torch.zeros(mesh.ndofs, dtype=torch.float64, device=dev),
-                          cc=torch.from_numpy(global_cell_constants(mesh)).to(dev), G=torch.from_numpy(G).to(dev),
-                          dm=torch.from_numpy(mesh.dofmap).to(dev)))
+    op = ops.stiffness_operator(P, gll.tabulate_1d(P)[2].flatten(), np.float64)
+    # ghosts are stale until the forward scatter
+    ranks = [rank_inputs(boxmesh.BoxMesh(P, cells, grid=grid, rank=r, perturb=0.16, seed=3, ghost_order=ghost_order), dev) for r in range(R)]
 
     utils = pkg("utils")  # an in-process world: every rank's halo plan at once
     od, gd = utils.compute_scatterer_data_all([rk["mesh"].index_map for rk in ranks])
@@ -291,26 +280,17 @@ def test_partitioned_mass_apply_row_split_one_gpu(gpu, oracle_c, P, cells, grid,
     torch = gpu
     schedule = overlap if overlap else "split"
     overlap = bool(overlap)
-    boxmesh, scat, ops, gll, pre, utils = (pkg(m) for m in ("boxmesh", "scatterer", "operators", "gll", "precompute", "utils"))
+    boxmesh, scat, ops, utils = (pkg(m) for m in ("boxmesh", "scatterer", "operators", "utils"))
     R = int(np.prod(grid))
     wid = next(_world_ids)
     dev = torch.device("cuda", 0)
-    pts, wts, D = gll.tabulate_1d(P)
     n = P + 1
-    w3 = gll.tensor_weights_3d(wts)
-    dg = pre.tabulate_hex_p1_gradients(gll.tensor_points_3d(pts))
     op = ops.mass_operator(n**3, np.float64)
     ranks = []
     for r in range(R):
         mesh = boxmesh.BoxMesh(P, cells, grid=grid, rank=r, perturb=0.16, seed=3, ghost_order=ghost_order)
         assert mesh.ncells * n**3 >= ops._MASS_PLAN_MIN_ENTRIES
-        detJ = np.zeros((mesh.ncells, n**3))
-        pre.compute_scaled_jacobian_determinant(detJ, (mesh.x_dofs, mesh.x_g), mesh.ncells, dg, w3)
-        x = ref_field(mesh.dof_coordinates())
-        x[mesh.nlocal:] = -777.0  # ghosts are stale until the forward scatter
-        ranks.append(dict(mesh=mesh, x=torch.from_numpy(x).to(dev), y=torch.zeros(mesh.ndofs, dtype=torch.float64, device=dev),
-                          cc=torch.from_numpy(global_cell_constants(mesh)).to(dev), detJ=torch.from_numpy(detJ).to(dev),
-                          dm=torch.from_numpy(mesh.dofmap).to(dev)))
+        ranks.append(rank_inputs(mesh, dev, "detJ"))  # ghosts are stale until the forward scatter
     od, gd = utils.compute_scatterer_data_all([rk["mesh"].index_map for rk in ranks])
     halos = [scat.HaloApply(rk["mesh"], op, _local_comm(scat, wid, R, r, transport), np.float64, overlap=overlap, plan=(od[r], gd[r]),
                             schedule=schedule) for r, rk in enumerate(ranks)]
@@ -334,8 +314,7 @@ def test_partitioned_mass_apply_row_split_one_gpu(gpu, oracle_c, P, cells, grid,
             live = nxt
     torch.cuda.synchronize()
     ms = boxmesh.BoxMesh(P, cells, perturb=0.16, seed=3)
-    detJ_s = np.zeros((ms.ncells, n**3))
-    pre.compute_scaled_jacobian_determinant(detJ_s, (ms.x_dofs, ms.x_g), ms.ncells, dg, w3)
+    detJ_s = rk4_oracle.host_detJ(ms)
     x_s = ref_field(ms.dof_coordinates())
     y_ser = np.zeros(ms.ndofs)
     oracle_c.mass_apply(x_s, global_cell_constants(ms), y_ser, detJ_s, ms.dofmap)
@@ -872,14 +851,11 @@ def test_concurrent_schedule_issue_order_two_in_process_ranks(gpu, oracle_c):
     forward exchange is posted.  A rank without boundary or without interior cells has no such launch.  Result against the serial
     apply, and no failed device-side wait."""
     torch = gpu
-    boxmesh, scat, ops, gll, pre, utils = (pkg(m) for m in ("boxmesh", "scatterer", "operators", "gll", "precompute", "utils"))
+    boxmesh, scat, ops, gll, utils = (pkg(m) for m in ("boxmesh", "scatterer", "operators", "gll", "utils"))
     P, cells, grid, R = 2, (4, 2, 2), (2, 1, 1), 2
     wid = next(_world_ids)
     dev = torch.device("cuda", 0)
-    pts, wts, D = gll.tabulate_1d(P)
-    w3 = gll.tensor_weights_3d(wts)
-    dg = pre.tabulate_hex_p1_gradients(gll.tensor_points_3d(pts))
-    op = ops.stiffness_operator(P, D.flatten(), np.float64)
+    op = ops.stiffness_operator(P, gll.tabulate_1d(P)[2].flatten(), np.float64)
     caller = torch.cuda.current_stream().cuda_stream
     log = []  # the entries of the apply in progress, per rank
 
@@ -899,16 +875,7 @@ def test_concurrent_schedule_issue_order_two_in_process_ranks(gpu, oracle_c):
             return fn(*a, **k)
         return call
 
-    ranks = []
-    for r in range(R):
-        mesh = boxmesh.BoxMesh(P, cells, grid=grid, rank=r, perturb=0.16, seed=3)
-        G = np.zeros((mesh.ncells, (P + 1)**3, 6))
-        pre.compute_scaled_geometrical_factor(G, (mesh.x_dofs, mesh.x_g), mesh.ncells, dg, w3)
-        x = ref_field(mesh.dof_coordinates())
-        x[mesh.nlocal:] = -777.0
-        ranks.append(dict(mesh=mesh, x=torch.from_numpy(x).to(dev), y=torch.zeros(mesh.ndofs, dtype=torch.float64, device=dev),
-                          cc=torch.from_numpy(global_cell_constants(mesh)).to(dev), G=torch.from_numpy(G).to(dev),
-                          dm=torch.from_numpy(mesh.dofmap).to(dev)))
+    ranks = [rank_inputs(boxmesh.BoxMesh(P, cells, grid=grid, rank=r, perturb=0.16, seed=3), dev) for r in range(R)]
     od, gd = utils.compute_scatterer_data_all([rk["mesh"].index_map for rk in ranks])
     halos = []
     for r, rk in enumerate(ranks):

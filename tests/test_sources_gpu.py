@@ -1,11 +1,11 @@
 """Phased-array sources on the device (csrc/source_array.hpp through operators.facet_source_terms and the solvers'
-``source=``): the kernel against a numpy restatement, a uniform array against the scalar source on every stage path, an
-independent host RK4 loop, linearity, delays as time shifts, mirror symmetry of steering, and partitioned runs."""
+``source=``): the kernel against a numpy restatement, a uniform array against the scalar source on every stage path, the
+oracle's host RK4 loop with the source applied element by element, linearity, delays as time shifts, mirror symmetry of steering, and partitioned runs."""
 import numpy as np
 import pytest
 
 from conftest import pkg, rel_l2
-from oracle import oracle_np
+from oracle import oracle_np, rk4_oracle
 
 pytestmark = pytest.mark.gpu
 
@@ -103,52 +103,19 @@ def test_uniform_array_equals_scalar_source(solver, path):
 
 
 def _host_linear(mesh, arr, nsteps, dt):
-    """An independent host RK4 loop of the linear solver (oracle operators; rk4_oracle.solve's stage) with the source applied
-    per element: mass_apply of the constant vector g_e over that element's facet rows."""
-    gll, pre = pkg("gll"), pkg("precompute")
-    P, n = mesh.P, mesh.P + 1
-    pts, wts, D = gll.tabulate_1d(P)
-    w3 = gll.tensor_weights_3d(wts)
-    dgr = pre.tabulate_hex_p1_gradients(gll.tensor_points_3d(pts))
-    nc, nd = mesh.ncells, mesh.ndofs
-    bd1, bd2 = mesh.boundary_facets([2]), mesh.boundary_facets([3])
-    G, detJ = np.zeros((nc, n**3, 6)), np.zeros((nc, n**3))
-    pre.compute_scaled_geometrical_factor(G, (mesh.x_dofs, mesh.x_g), nc, dgr, w3)
-    pre.compute_scaled_jacobian_determinant(detJ, (mesh.x_dofs, mesh.x_g), nc, dgr, w3)
-    w2, dpf = gll.tensor_weights_2d(wts), pre.tabulate_facet_gradients(pts)
-    dF1, dF2 = np.zeros((bd1.shape[0], n * n)), np.zeros((bd2.shape[0], n * n))
-    pre.compute_boundary_facets_scaled_jacobian_determinant(dF1, (mesh.x_dofs, mesh.x_g), bd1, dpf, w2)
-    pre.compute_boundary_facets_scaled_jacobian_determinant(dF2, (mesh.x_dofs, mesh.x_g), bd2, dpf, w2)
-    fd1, fd2 = mesh.facet_dofmap(bd1), mesh.facet_dofmap(bd2)
-    cc1, cc2 = np.full(nc, 1 / RHO / C0 / C0), np.full(nc, -1 / RHO)
-    fc1, fc2 = np.full(bd1.shape[0], 1 / RHO), np.full(bd2.shape[0], -1 / RHO / C0)
-    ids = arr.assign(mesh, bd1)
-    rows = [np.nonzero(ids == e)[0] for e in range(arr.n_elements)]
+    """The oracle's linear model (rk4_oracle.solve: its geometry, coefficients, stage and loop) with the source applied per element,
+    independently of the product: mass_apply of the constant vector g_e over that element's facet rows."""
+    rows = [np.nonzero(arr.assign(mesh, mesh.boundary_facets([2])) == e)[0] for e in range(arr.n_elements)]
     A = P0 * 2 * np.pi * F0 / C0
-    m = np.zeros(nd)
-    oracle_np.mass_apply(np.ones(nd), cc1, m, detJ, mesh.dofmap)
-    Ar, Br, Cr = (0.0, 0.5, 0.5, 1.0), (1 / 6, 1 / 3, 1 / 3, 1 / 6), (0.0, 0.5, 0.5, 1.0)
 
-    def f1(t, un, vn):
-        b = np.zeros(nd)
-        oracle_np.stiffness_apply(P, D.flatten(), un, cc2, b, G, mesh.dofmap)
+    def source_term(t, b, coefficients, detJ, dofmap):
+        (fc1,) = coefficients
         g, _ = arr.values(t, F0, A)
         for e, r in enumerate(rows):
             if r.size:
-                oracle_np.mass_apply(np.full(nd, g[e]), fc1[r], b, dF1[r], fd1[r])
-        oracle_np.mass_apply(np.ascontiguousarray(vn), fc2, b, dF2, fd2)
-        return b / m
+                oracle_np.mass_apply(np.full(mesh.ndofs, g[e]), fc1[r], b, detJ[r], dofmap[r])
 
-    u, v, ku, kv, t = np.zeros(nd), np.zeros(nd), np.zeros(nd), np.zeros(nd), 0.0
-    for _ in range(nsteps):
-        u0, v0 = u.copy(), v.copy()
-        for i in range(4):
-            un, vn = u0 + Ar[i] * dt * ku, v0 + Ar[i] * dt * kv
-            ku = vn.copy()
-            kv = f1(t + Cr[i] * dt, un, vn)
-            u, v = u + Br[i] * dt * ku, v + Br[i] * dt * kv
-        t += dt
-    return u
+    return rk4_oracle.solve(mesh, nsteps, dt, c0=C0, rho0=RHO, f0=F0, p0=P0, source_term=source_term)[0]
 
 
 def _array4(L, **kw):

@@ -1,5 +1,5 @@
-"""Absorbing sponge layers (sponge.py, csrc/sponge.hpp), the part that needs no GPU: the CPU model of the layer (tests/sponge_cpu.py)
-and the identity that pins its form, the profile, the layer's dof lists on one and several ranks, the kernel's resource usage and the
+"""Absorbing sponge layers (sponge.py, csrc/sponge.hpp), the part that needs no GPU: the CPU model of the layer (the stage term of
+tests/sponge_cpu.py in the loops of oracle/rk4_oracle.py) and the identity that pins its form, the profile, the layer's dof lists on one and several ranks, the kernel's resource usage and the
 argument checks of its entry points."""
 
 import ctypes as C
@@ -20,20 +20,19 @@ def _bits(a):
 
 # ---- the model ---------------------------------------------------------------------------------------------------------------------
 def test_model_without_layer_is_the_oracle_loop_bitwise():
-    """sigma == 0 (absent, and as an explicit array of zeros): the restated loops return the oracle's fields bit for bit."""
+    """sigma == 0 with the term ACTIVE (sigma absent, which the layer's factory turns into zeros, and an explicit array of zeros): both
+    loops return the fields of the loop without a term, bit for bit.  This test once guarded a separate restatement of the two loops
+    that lived in tests/sponge_cpu.py; that fork is gone (the layer is a ``stage_term`` of the oracle's own loops), and its results
+    were compared bit for bit with this model's when it was removed (profiles/oracle_model_refactor.log)."""
     boxmesh = pkg("boxmesh")
     mesh = boxmesh.BoxMesh(2, (3, 2, 2), length=(0.006, 0.004, 0.004), perturb=0.1, seed=1)
     dt = 1.0e-7
-    u_ref, v_ref = rk4_oracle.solve(mesh, 3, dt)
-    assert np.max(np.abs(u_ref)) > 0
-    for sigma in (None, np.zeros(mesh.ndofs)):
-        u, v = sponge_cpu.solve(mesh, 3, dt, sigma=sigma)
-        assert np.array_equal(_bits(u), _bits(u_ref)) and np.array_equal(_bits(v), _bits(v_ref))
-    u_ref, v_ref = rk4_oracle.solve_westervelt(mesh, 3, dt)
-    assert np.max(np.abs(u_ref)) > 0
-    for sigma in (None, np.zeros(mesh.ndofs)):
-        u, v = sponge_cpu.solve_westervelt(mesh, 3, dt, sigma=sigma)
-        assert np.array_equal(_bits(u), _bits(u_ref)) and np.array_equal(_bits(v), _bits(v_ref))
+    for solve in (rk4_oracle.solve, rk4_oracle.solve_westervelt):
+        u_ref, v_ref = solve(mesh, 3, dt)
+        assert np.max(np.abs(u_ref)) > 0
+        for sigma in (None, np.zeros(mesh.ndofs)):
+            u, v = solve(mesh, 3, dt, stage_term=sponge_cpu.layer_term(mesh, sigma))
+            assert np.array_equal(_bits(u), _bits(u_ref)) and np.array_equal(_bits(v), _bits(v_ref))
 
 
 @pytest.fixture(scope="module")
@@ -51,8 +50,8 @@ def constant_sigma_runs(oracle_c):
 
     def distance(steps, h, **more):
         T = steps * h
-        ud, _ = sponge_cpu.solve(mesh, steps, h, sigma=sigma, u=u_init, v=-sigma * u_init, **kw, **more)
-        uw, _ = sponge_cpu.solve(mesh, steps, h, sigma=None, u=u_init, v=0 * u_init, **kw)
+        ud, _ = rk4_oracle.solve(mesh, steps, h, stage_term=sponge_cpu.layer_term(mesh, sigma, **more), u=u_init, v=-sigma * u_init, **kw)
+        uw, _ = rk4_oracle.solve(mesh, steps, h, u=u_init, v=0 * u_init, **kw)
         return rel_l2(ud, np.exp(-sigma * T) * uw)
 
     return dict(dt=distance(16, dt), half=distance(32, dt / 2), factor_one=distance(16, dt, cv_factor=1.0))

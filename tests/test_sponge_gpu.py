@@ -1,11 +1,13 @@
 """Absorbing sponge layers on the GPU: the sparse kernel (csrc/sponge.hpp) against numpy, both wave solvers with a layer -- every stage
-implementation -- against the CPU model (tests/sponge_cpu.py), the empty layer, hipGraph replay, partitioned runs and fp32."""
+implementation -- against the CPU model (oracle/rk4_oracle.py with the stage term of tests/sponge_cpu.py), the empty
+layer, hipGraph replay, partitioned runs and fp32."""
 
 import numpy as np
 import pytest
 
 import sponge_cpu
 from conftest import TOL, pkg, rel_l2, rel_max
+from oracle import rk4_oracle
 
 pytestmark = pytest.mark.gpu
 
@@ -98,8 +100,8 @@ def _linear_case(name, oracle_c):
         h = ls.time_step_parameters(mesh, k["P"], 1500.0, 0.5e6, mesh.length[0])
         dt, tf, _ = ls.snap_time_step(h, k["P"], 1500.0, 0.5e6, mesh.length[0])
         sigma = _lateral(mesh, 1500.0)
-        with_layer = sponge_cpu.solve(mesh, k["steps"], dt, sigma=sigma, oracle_c=oracle_c)
-        without = sponge_cpu.solve(mesh, k["steps"], dt, oracle_c=oracle_c)
+        with_layer = rk4_oracle.solve(mesh, k["steps"], dt, stage_term=sponge_cpu.layer_term(mesh, sigma), oracle_c=oracle_c)
+        without = rk4_oracle.solve(mesh, k["steps"], dt, oracle_c=oracle_c)
         for a in with_layer + without:
             a.setflags(write=False)
         _model_cache[name] = (mesh, dt, tf, sigma, with_layer, without)
@@ -153,8 +155,8 @@ def _westervelt_case(oracle_c):
         h = ls.time_step_parameters(mesh, P, 1480.0, 1.1e6, L)
         dt, tf, _ = ls.snap_time_step(h, P, 1480.0, 1.1e6, L)
         sigma = _lateral(mesh, 1480.0)
-        with_layer = sponge_cpu.solve_westervelt(mesh, steps, dt, sigma=sigma, oracle_c=oracle_c)
-        without = sponge_cpu.solve_westervelt(mesh, steps, dt, oracle_c=oracle_c)
+        with_layer = rk4_oracle.solve_westervelt(mesh, steps, dt, stage_term=sponge_cpu.layer_term(mesh, sigma), oracle_c=oracle_c)
+        without = rk4_oracle.solve_westervelt(mesh, steps, dt, oracle_c=oracle_c)
         for a in with_layer + without:
             a.setflags(write=False)
         _model_cache["westervelt"] = (mesh, dt, tf, steps, sigma, with_layer, without)
