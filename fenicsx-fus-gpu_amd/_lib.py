@@ -9,6 +9,7 @@ from __future__ import annotations
 
 import ctypes as C
 import os
+import re
 
 import numpy as np
 import torch
@@ -16,128 +17,89 @@ import torch
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # FUS_LIB_PATH: load another build of the same ABI (A/B runs of two builds on one device)
 LIB_PATH = os.environ.get("FUS_LIB_PATH") or os.path.join(_HERE, "csrc", "libfusgpu.so")
-
-_i64, _int, _vp = C.c_int64, C.c_int, C.c_void_p
-
-# every symbol include/fus_gpu.h declares -> (argtypes); restype is int unless noted
-_SUFFIXES = (("f64", C.c_double), ("f32", C.c_float))
-
-
-def _signatures():
-    sig = {
-        "fus_abi_version": [],
-        "fus_device_info": [_int, C.c_char_p, C.POINTER(_int), C.POINTER(_i64), C.POINTER(_int)],
-        "fus_set_tuning": [_int, _int],
-        "fus_get_tuning": [_int],
-        "fus_stiffness_plan_bytes": [_int, _i64],
-        "fus_plan_entities_per_batch": [_int],
-        "fus_plan_bytes": [_int, _int, _i64],
-        "fus_plan_build": [_vp, _int, _int, _i64, _vp, _i64, _vp],
-        "fus_plan_build_ordered": [_vp, _vp, _int, _int, _i64, _vp, _i64, _vp],
-        "fus_plan_release": [_vp],
-        "fus_plan_encoding": [_vp, C.POINTER(_i64), C.POINTER(_i64), C.POINTER(_int), C.POINTER(_int)],
-        "fus_plan_mark_exclusive": [_vp, _int, _int, _i64, _vp, _i64, _vp],
-        "fus_mass_gather_plan_bytes": [_int, _i64, _i64],
-        "fus_mass_gather_plan_build": [_vp, _int, _i64, _i64, _vp, _i64, _vp],
-        "fus_mass_gather_plan_build_rows": [_vp, _int, _i64, _i64, _vp, _int, _vp, _i64, _vp],
-        "fus_mass_gather_static_bytes": [_int, _i64, _int],
-        "fus_mass_gather_static_build_f64": [_vp, _vp, _vp, _i64, _vp],
-        "fus_mass_gather_static_build_f32": [_vp, _vp, _vp, _i64, _vp],
-        "fus_mass_apply_gather_static_f64": [_vp, _vp, _vp, _vp, _vp, _int, _i64, _vp],
-        "fus_mass_apply_gather_static_f32": [_vp, _vp, _vp, _vp, _vp, _int, _i64, _vp],
-        "fus_mass_gather_plan_info": [_vp, _vp],
-        "fus_stiffness_plan_build": [_vp, _int, _i64, _vp, _i64, _vp],
-        # communicator + halo exchange (csrc/halo_comm.hpp)
-        "fus_comm_unique_id": [_vp],
-        "fus_comm_create": [_vp, _int, _int, C.POINTER(_vp)],
-        "fus_comm_create_local": [_int, _int, _int, C.POINTER(_vp)],
-        "fus_comm_create_peer": [_int, _int, C.POINTER(_vp)],
-        "fus_halo_ipc_blob_bytes": [_vp],
-        "fus_halo_ipc_export": [_vp, _vp],
-        "fus_halo_ipc_connect": [_vp, _int, _vp],
-        "fus_halo_ipc_status": [_vp, _vp],
-        "fus_comm_rank": [_vp],
-        "fus_comm_size": [_vp],
-        "fus_comm_stream": [_vp],
-        "fus_comm_last_error": [_vp],
-        "fus_comm_fork": [_vp, _vp],
-        "fus_comm_fork_lazy": [_vp, _vp],
-        "fus_comm_fork_ex": [_vp, _vp, _int],
-        "fus_comm_fork_flush": [_vp],
-        "fus_comm_join": [_vp, _vp],
-        "fus_comm_arm_join": [_vp],
-        "fus_comm_health": [_vp, _vp],
-        "fus_comm_health_detail": [_vp, _vp],
-        "fus_comm_sync_timeouts": [_vp, _vp],
-        "fus_comm_destroy": [_vp],
-        "fus_halo_create": [_vp, _int, _i64, _i64, _int, _vp, _vp, _vp, _int, _vp, _vp, _vp, C.POINTER(_vp)],
-        "fus_halo_is_direct": [_vp],
-        "fus_halo_destroy": [_vp],
-        "fus_halo_forward_begin": [_vp, _vp, _vp],
-        "fus_halo_forward_end": [_vp, _vp, _vp],
-        "fus_halo_reverse_begin": [_vp, _vp, _vp],
-        "fus_halo_reverse_end": [_vp, _vp, _vp],
-        "fus_halo_forward_begin_group": [_vp, _vp, _int, _vp],
-        "fus_halo_reverse_begin_group": [_vp, _vp, _int, _vp],
-        "fus_halo_forward": [_vp, _vp, _vp],
-        "fus_halo_reverse": [_vp, _vp, _vp],
-    }
-    for suf, ct in _SUFFIXES:
-        sig[f"fus_stiffness_apply_{suf}"] = [_vp, _vp, _vp, _vp, _vp, _vp, _int, _i64, _vp]
-        sig[f"fus_stiffness_apply_planned_{suf}"] = [_vp, _vp, _vp, _vp, _vp, _vp, _int, _i64, _vp]
-        sig[f"fus_stiffness_apply_planned_affine_{suf}"] = [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _int, _i64, _vp]
-        sig[f"fus_stiffness_apply_planned_geom_{suf}"] = [_vp] * 9 + [_int, _i64, _vp]
-        sig[f"fus_gradient_apply_planned_geom_{suf}"] = [_vp] * 3 + [_i64] + [_vp] * 6 + [_int, _i64, _vp]
-        sig[f"fus_mass_apply_planned_{suf}"] = [_vp, _vp, _vp, _vp, _vp, _int, _int, _i64, _vp]
-        sig[f"fus_mass_apply_{suf}"] = [_vp, _vp, _vp, _vp, _vp, _int, _i64, _vp]
-        sig[f"fus_mass_apply_gather_{suf}"] = [_vp, _vp, _vp, _vp, _vp, _int, _i64, _vp]
-        sig[f"fus_facet_terms_{suf}"] = [_vp, _vp, ct, _vp, ct, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _i64, _int, _vp]
-        sig[f"fus_facet_terms_dev_{suf}"] = [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _i64, _int, _vp]
-        sig[f"fus_sponge_terms_{suf}"] = [_vp] * 6 + [_i64, _vp]
-        sig[f"fus_axpy_{suf}"] = [ct, _vp, _vp, _i64, _vp]
-        sig[f"fus_scale_{suf}"] = [ct, _vp, _vp, _i64, _vp]
-        sig[f"fus_copy_{suf}"] = [_vp, _vp, _i64, _vp]
-        sig[f"fus_fill_{suf}"] = [ct, _vp, _i64, _vp]
-        sig[f"fus_pointwise_divide_{suf}"] = [_vp, _vp, _vp, _i64, _vp]
-        sig[f"fus_square_{suf}"] = [_vp, _vp, _i64, _vp]
-        sig[f"fus_muladd_{suf}"] = [_vp, _vp, _vp, _i64, _vp]
-        sig[f"fus_geometry_factors_{suf}"] = [_vp, _vp, _vp, _vp, _int, _i64, _vp, _vp, _vp]
-        sig[f"fus_facet_jacobian_{suf}"] = [_vp, _vp, _vp, _vp, _vp, _int, _i64, _vp, _vp]
-        sig[f"fus_westervelt_cell_apply_planned_{suf}"] = [_vp] * 12 + [_int, _i64, _vp]
-        sig[f"fus_westervelt_cell_apply_planned_geom_{suf}"] = [_vp] * 14 + [_int, _i64, _vp]
-        sig[f"fus_rk4_stage_nl_{suf}"] = [ct, ct, _int] + [_vp] * 9 + [_i64, _i64, _vp]
-        sig[f"fus_rk4_stage_nl2_{suf}"] = [ct, ct, _int] + [_vp] * 10 + [ct, _vp, _i64, _i64, _vp]
-        sig[f"fus_rk4_stage_{suf}"] = [ct, ct, _int] + [_vp] * 8 + [_i64, _i64, _vp]
-        sig[f"fus_facet_source_array_{suf}"] = [_vp] * 6 + [_i64] + [_vp] * 3 + [_i64] + [_vp] * 4 + [_i64, _int, _vp, _vp]
-        sig[f"fus_facet_source_array_dev_{suf}"] = [_vp] * 6 + [_i64] + [_vp] * 3 + [_i64] + [_vp] * 4 + [_i64, _int, _vp, _vp]
-        sig[f"fus_probe_eval_{suf}"] = [_vp, _vp, _i64, _vp, _i64, _vp, _int, _vp, _i64, _int] + [_vp] * 5 + [_int, _vp]
-        sig[f"fus_field_accumulate_{suf}"] = [_vp, _vp, _i64] + [_vp] * 6 + [_i64, _vp, _int, _int, _vp]
-        sig[f"fus_bioheat_stage_{suf}"] = [ct, ct, _int, ct, ct, C.c_double] + [_vp] * 9 + [_int, _i64, _i64, _vp]
-        sig[f"fus_pack_fwd_{suf}"] = [_vp, _vp, _vp, _i64, _vp]
-        sig[f"fus_unpack_fwd_{suf}"] = [_vp, _vp, _vp, _i64, _i64, _vp]
-        sig[f"fus_pack_rev_{suf}"] = [_vp, _vp, _vp, _i64, _i64, _vp]
-        sig[f"fus_unpack_rev_{suf}"] = [_vp, _vp, _vp, _i64, _vp]
-    return sig
-
-
-SIGNATURES = _signatures()
-
-TUNE_STIFFNESS_VARIANT = 1
-TUNE_XCD_REMAP = 2
-TUNE_MASS_VARIANT = 3
-TUNE_PLAN_VARIANT = 4
-TUNE_PLAN_RUNS = 5
-TUNE_VECTOR_STREAM = 6
-TUNE_PLAN_ROWS = 7  # fp64 general-G apply: 1 (default) one slot per local row + compact run tables where the plan allows, 0 never
-TUNE_PLAN_XCD_GROUP = 8  # general-G planned apply: g consecutive batches per XCD label; -1 auto (default), 0 off, 2 .. 256 (a power of two) = g
-
-ABI_VERSION = 3  # include/fus_gpu.h FUS_ABI_VERSION
-
-_lib = None
+HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "fus_gpu.h")
 
 
 class FusGpuError(RuntimeError):
     pass
+
+
+_BY_VALUE = {"int": C.c_int, "int64_t": C.c_int64, "double": C.c_double, "float": C.c_float}
+_RETURNS = {"int": C.c_int, "int64_t": C.c_int64, "void*": C.c_void_p, "const char*": C.c_char_p}
+
+
+def parse_header(text):
+    """The C ABI as include/fus_gpu.h declares it -> ({function: (restype, [argtypes])}, {macro: integer value}).
+    Every pointer, and a handle (``typedef struct X* name;``) by value, is ``c_void_p``; a scalar by value is its ctypes class.
+    Anything else is refused, never guessed: a wrong class here would hand a kernel launch garbage instead of failing to load."""
+    text = re.sub(r"/\*.*?\*/|//[^\n]*", lambda m: " " + "\n" * m[0].count("\n"), text, flags=re.S)  # comments, keeping the line structure
+    defines = {m[1]: int(m[2]) for m in re.finditer(r"^[ \t]*#[ \t]*define[ \t]+(FUS_\w+)[ \t]+\(?(-?\d+)\)?[ \t]*$", text, re.M)}
+    text = re.sub(r"^[ \t]*#.*$", "", text, flags=re.M)  # the other preprocessor lines: include guard, #include, #ifdef __cplusplus
+    text = re.sub(r'extern\s+"C"\s*\{|^\s*\}\s*$', "", text, flags=re.M)
+    functions, handles = {}, set()
+    for stmt in (" ".join(s.split()) for s in text.split(";")):
+        handle = re.fullmatch(r"typedef struct \w+ ?\* ?(\w+)", stmt)
+        if handle:
+            handles.add(handle[1])
+            continue
+        if not stmt:
+            continue
+        m = re.fullmatch(r"([\w\s*]+?) ?\b(fus_\w+) ?\(([^()]*)\)", stmt)
+        ret = m and m[1].replace(" *", "*")
+        if not m or ret not in _RETURNS:
+            raise FusGpuError(f"include/fus_gpu.h: cannot bind '{stmt[:120]}': not a prototype 'int | int64_t | void* | const char* fus_name(parameters)'")
+        params = [] if m[3].strip() in ("", "void") else m[3].split(",")
+        argtypes = []
+        for p in params:
+            words = [w for w in p.split() if w != "const"]  # type, then the name if there is one
+            if "*" in p or (1 <= len(words) <= 2 and words[0] in handles and words[-1].isidentifier()):
+                argtypes.append(C.c_void_p)
+            elif 1 <= len(words) <= 2 and words[0] in _BY_VALUE and words[-1].isidentifier():
+                argtypes.append(_BY_VALUE[words[0]])
+            else:
+                raise FusGpuError(f"include/fus_gpu.h: {m[2]}: parameter '{p.strip()}' is neither a pointer, a handle nor one of {', '.join(_BY_VALUE)} by value")
+        functions[m[2]] = (_RETURNS[ret], argtypes)
+    return functions, defines
+
+
+def _read_header():
+    try:
+        with open(HEADER_PATH) as f:
+            return parse_header(f.read())
+    except OSError as e:
+        raise FusGpuError(f"{HEADER_PATH}: the C ABI's header, which this binding is derived from, cannot be read ({e})") from None
+
+
+# every function include/fus_gpu.h declares, and its integer macros: the header is the one declaration, nothing is restated here
+DECLARATIONS, _DEFINES = _read_header()
+# {name: argtypes} of the entry points (what a stand-in library has to answer); the two that only return a string are bound like the rest
+SIGNATURES = {name: argtypes for name, (_, argtypes) in DECLARATIONS.items() if name not in ("fus_error_string", "fus_source_hash")}
+
+ABI_VERSION = _DEFINES["FUS_ABI_VERSION"]
+ERR_COMM = _DEFINES["FUS_ERR_COMM"]
+ERR_UNSUPPORTED_ENTITY = _DEFINES["FUS_ERR_UNSUPPORTED_ENTITY"]
+MIN_DEGREE, MAX_DEGREE = _DEFINES["FUS_MIN_DEGREE"], _DEFINES["FUS_MAX_DEGREE"]
+UNIQUE_ID_BYTES = _DEFINES["FUS_UNIQUE_ID_BYTES"]
+FORK_LAZY, FORK_ATTACH = _DEFINES["FUS_FORK_LAZY"], _DEFINES["FUS_FORK_ATTACH"]
+# tuning keys: the header documents each next to its #define
+TUNE_STIFFNESS_VARIANT = _DEFINES["FUS_TUNE_STIFFNESS_VARIANT"]
+TUNE_XCD_REMAP = _DEFINES["FUS_TUNE_XCD_REMAP"]
+TUNE_MASS_VARIANT = _DEFINES["FUS_TUNE_MASS_VARIANT"]
+TUNE_PLAN_VARIANT = _DEFINES["FUS_TUNE_PLAN_VARIANT"]
+TUNE_PLAN_RUNS = _DEFINES["FUS_TUNE_PLAN_RUNS"]
+TUNE_VECTOR_STREAM = _DEFINES["FUS_TUNE_VECTOR_STREAM"]
+TUNE_PLAN_ROWS = _DEFINES["FUS_TUNE_PLAN_ROWS"]
+TUNE_PLAN_XCD_GROUP = _DEFINES["FUS_TUNE_PLAN_XCD_GROUP"]
+
+_lib = None
+
+
+def bind(cdll):
+    """Set ``argtypes`` and ``restype`` of every declared function on a loaded library; AttributeError if it lacks one."""
+    for name, (restype, argtypes) in DECLARATIONS.items():
+        fn = getattr(cdll, name)
+        fn.argtypes, fn.restype = argtypes, restype
+    return cdll
 
 
 def load():
@@ -151,17 +113,7 @@ def load():
             "(run `python -c 'import __graft_entry__ as g; g.build()'` or `make -C fenicsx-fus-gpu_amd/csrc`). "
             "There is no CPU fallback."
         )
-    lib = C.CDLL(LIB_PATH)
-    for name, argtypes in SIGNATURES.items():
-        fn = getattr(lib, name)  # AttributeError if the library lacks a declared symbol
-        fn.argtypes = argtypes
-        fn.restype = {"fus_stiffness_plan_bytes": _i64, "fus_plan_bytes": _i64, "fus_comm_stream": _vp,
-                      "fus_mass_gather_plan_bytes": _i64, "fus_mass_gather_static_bytes": _i64,
-                      "fus_halo_ipc_blob_bytes": _i64, "fus_comm_last_error": C.c_char_p}.get(name, _int)
-    lib.fus_error_string.argtypes = [_int]
-    lib.fus_error_string.restype = C.c_char_p
-    lib.fus_source_hash.argtypes = []
-    lib.fus_source_hash.restype = C.c_char_p
+    lib = bind(C.CDLL(LIB_PATH))
     if lib.fus_abi_version() != ABI_VERSION:
         raise FusGpuError(f"{LIB_PATH}: ABI version {lib.fus_abi_version()}, this package needs {ABI_VERSION} "
                           "(include/fus_gpu.h FUS_ABI_VERSION): rebuild the library")
@@ -169,14 +121,9 @@ def load():
     return lib
 
 
-ERR_COMM = -5
-ERR_UNSUPPORTED_ENTITY = -3
-
-
 def tree_source_hash():
     """The hash csrc/Makefile embeds (fus_source_hash()), recomputed from the sources in this tree."""
     import hashlib
-    import re
 
     csrc = os.path.join(_HERE, "csrc")
     mk = open(os.path.join(csrc, "Makefile")).read()
@@ -252,7 +199,7 @@ def stream_ptr():
 def device_info(device: int = 0):
     lib = load()
     name = C.create_string_buffer(256)
-    cu, hbm, lds = _int(0), _i64(0), _int(0)
+    cu, hbm, lds = C.c_int(0), C.c_int64(0), C.c_int(0)
     check(lib.fus_device_info(device, name, C.byref(cu), C.byref(hbm), C.byref(lds)), "fus_device_info")
     return {"name": name.value.decode(), "compute_units": cu.value, "hbm_bytes": hbm.value, "lds_bytes_per_cu": lds.value}
 

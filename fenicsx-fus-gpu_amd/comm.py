@@ -168,7 +168,7 @@ class NativeComm:
         # Bootstrap that fails on ALL ranks or on none: (1) every rank probes librccl (dlopen + ncclGetUniqueId; only
         # rank 0's id is used) and the ranks agree on the outcome BEFORE anything is broadcast; (2) rank 0's id is
         # broadcast; (3) ncclCommInitRank, then the ranks agree again before any of them proceeds.
-        buf = C.create_string_buffer(128)
+        buf = C.create_string_buffer(_lib.UNIQUE_ID_BYTES)
         rc = lib.fus_comm_unique_id(buf)
         err = None if rc == 0 else f"fus_comm_unique_id: {lib.fus_error_string(rc).decode()}: {(lib.fus_comm_last_error(None) or b'?').decode()}"
         if self.size > 1:
@@ -229,7 +229,8 @@ class NativeComm:
         ``lazy`` (PEER transport): no wait kernel -- the first send kernel of the exchange the caller posts NEXT on the
         communicator's stream waits for the fork flag itself.  ``attach``: no signal kernel -- the next PLANNED operator
         launch on the caller's stream publishes the flag when it starts (``fork_flush()`` if none follows)."""
-        _lib.check(self._lib.fus_comm_fork_ex(self.handle, _lib.stream_ptr(), (1 if lazy else 0) | (2 if attach else 0)), "fus_comm_fork", self.handle)
+        flags = (_lib.FORK_LAZY if lazy else 0) | (_lib.FORK_ATTACH if attach else 0)
+        _lib.check(self._lib.fus_comm_fork_ex(self.handle, _lib.stream_ptr(), flags), "fus_comm_fork", self.handle)
 
     def fork_flush(self):
         """Publish an attached fork signal that no planned launch has carried (``fus_comm_fork_flush``)."""

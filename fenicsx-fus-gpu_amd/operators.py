@@ -666,8 +666,8 @@ class _CellOperator:
 
     def __init__(self, P, float_type, dphi=None):
         self.P = int(P)
-        if not (1 <= self.P <= 10):
-            raise ValueError(f"polynomial degree {P} outside the supported range 1..10")
+        if not (_lib.MIN_DEGREE <= self.P <= _lib.MAX_DEGREE):
+            raise ValueError(f"polynomial degree {P} outside the supported range {_lib.MIN_DEGREE}..{_lib.MAX_DEGREE}")
         self.n = self.P + 1
         self.dtype = _lib.torch_dtype(float_type)
         self._dphi = None if dphi is None else self._table(dphi)

@@ -25,6 +25,7 @@
 #include <stdexcept>
 #include <string>
 #include <type_traits>
+#include <utility>
 
 #include "fus_gpu.h"
 
@@ -51,99 +52,13 @@ struct Geometry {  // what compute_scaled_geometrical_factor / _jacobian_determi
 };
 
 namespace detail {
-template <typename T>
-struct Abi;
-template <>
-struct Abi<double> {
-  static int geometry(const double* xg, const int32_t* xd, const double* dphi, const double* w, int nq, int64_t nc, double* G,
-                      double* dJ, void* s) {
-    return fus_geometry_factors_f64(xg, xd, dphi, w, nq, nc, G, dJ, s);
-  }
-  static int stiffness(const double* x, const double* c, double* y, const double* G, const void* ws, const double* dphi, int P,
-                       int64_t nc, void* s) {
-    return fus_stiffness_apply_planned_f64(x, c, y, G, ws, dphi, P, nc, s);
-  }
-  static int gradient(const double* x, const double* c, double* y, int64_t ys, const double* xg, const int32_t* xd, const double* pts, const double* wts,
-                      const void* ws, const double* dphi, int P, int64_t nc, void* s) {
-    return fus_gradient_apply_planned_geom_f64(x, c, y, ys, xg, xd, pts, wts, ws, dphi, P, nc, s);
-  }
-  static int mass(const double* x, const double* c, double* y, const double* dJ, const void* ws, int N, int epb, int64_t ne,
-                  void* s) {
-    return fus_mass_apply_planned_f64(x, c, y, dJ, ws, N, epb, ne, s);
-  }
-  static int mass_gather(const double* x, const double* c, double* y, const double* dJ, const void* ws, int N, int64_t ne, void* s) {
-    return fus_mass_apply_gather_f64(x, c, y, dJ, ws, N, ne, s);
-  }
-  static int static_build(const void* ws, const double* dJ, void* sws, int64_t bytes, void* s) {
-    return fus_mass_gather_static_build_f64(ws, dJ, sws, bytes, s);
-  }
-  static int mass_gather_static(const double* x, const double* c, double* y, const void* ws, const void* sws, int N, int64_t ne, void* s) {
-    return fus_mass_apply_gather_static_f64(x, c, y, ws, sws, N, ne, s);
-  }
-  static int probe(const double* u, const int32_t* cells, int64_t m, const int32_t* dm, int64_t nc, const double* w, int P, double* rec,
-                   int64_t cap, int slot, double* pmax, double* pmin, double* hre, double* him, const double* coef, int H, void* s) {
-    return fus_probe_eval_f64(u, cells, m, dm, nc, w, P, rec, cap, slot, pmax, pmin, hre, him, coef, H, s);
-  }
-  static int field(const double* u, const double* v, int64_t n, double* pmax, double* pmin, double* usq, double* vsq, double* hre, double* him,
-                   int64_t hstride, const double* coef, int H, int init, void* s) {
-    return fus_field_accumulate_f64(u, v, n, pmax, pmin, usq, vsq, hre, him, hstride, coef, H, init, s);
-  }
-  static int bioheat(double bw, double aw, int kind, double gate, double ta, double dt, const double* minv, const double* pr, const double* s, double* b, double* T0, double* Tn, double* acc,
-                     double* cem43, double* tmax, int init, int64_t nlocal, int64_t ntotal, void* st) {
-    return fus_bioheat_stage_f64(bw, aw, kind, gate, ta, dt, minv, pr, s, b, T0, Tn, acc, cem43, tmax, init, nlocal, ntotal, st);
-  }
-  static int source_array(double* y, const double* c1, const double* c2, const double* dA, const int32_t* dmA, const int32_t* eid, int64_t nA,
-                          const double* a, const double* ph, const double* tau, int64_t E, const double* xB, const double* cB, const double* dB,
-                          const int32_t* dmB, int64_t nB, int N, const double* stage, bool dev, void* s) {
-    return dev ? fus_facet_source_array_dev_f64(y, c1, c2, dA, dmA, eid, nA, a, ph, tau, E, xB, cB, dB, dmB, nB, N, stage, s)
-               : fus_facet_source_array_f64(y, c1, c2, dA, dmA, eid, nA, a, ph, tau, E, xB, cB, dB, dmB, nB, N, stage, s);
-  }
-};
-template <>
-struct Abi<float> {
-  static int geometry(const float* xg, const int32_t* xd, const float* dphi, const float* w, int nq, int64_t nc, float* G, float* dJ,
-                      void* s) {
-    return fus_geometry_factors_f32(xg, xd, dphi, w, nq, nc, G, dJ, s);
-  }
-  static int stiffness(const float* x, const float* c, float* y, const float* G, const void* ws, const float* dphi, int P, int64_t nc,
-                       void* s) {
-    return fus_stiffness_apply_planned_f32(x, c, y, G, ws, dphi, P, nc, s);
-  }
-  static int gradient(const float* x, const float* c, float* y, int64_t ys, const float* xg, const int32_t* xd, const float* pts, const float* wts,
-                      const void* ws, const float* dphi, int P, int64_t nc, void* s) {
-    return fus_gradient_apply_planned_geom_f32(x, c, y, ys, xg, xd, pts, wts, ws, dphi, P, nc, s);
-  }
-  static int mass(const float* x, const float* c, float* y, const float* dJ, const void* ws, int N, int epb, int64_t ne, void* s) {
-    return fus_mass_apply_planned_f32(x, c, y, dJ, ws, N, epb, ne, s);
-  }
-  static int mass_gather(const float* x, const float* c, float* y, const float* dJ, const void* ws, int N, int64_t ne, void* s) {
-    return fus_mass_apply_gather_f32(x, c, y, dJ, ws, N, ne, s);
-  }
-  static int static_build(const void* ws, const float* dJ, void* sws, int64_t bytes, void* s) {
-    return fus_mass_gather_static_build_f32(ws, dJ, sws, bytes, s);
-  }
-  static int mass_gather_static(const float* x, const float* c, float* y, const void* ws, const void* sws, int N, int64_t ne, void* s) {
-    return fus_mass_apply_gather_static_f32(x, c, y, ws, sws, N, ne, s);
-  }
-  static int probe(const float* u, const int32_t* cells, int64_t m, const int32_t* dm, int64_t nc, const float* w, int P, float* rec,
-                   int64_t cap, int slot, double* pmax, double* pmin, double* hre, double* him, const double* coef, int H, void* s) {
-    return fus_probe_eval_f32(u, cells, m, dm, nc, w, P, rec, cap, slot, pmax, pmin, hre, him, coef, H, s);
-  }
-  static int field(const float* u, const float* v, int64_t n, float* pmax, float* pmin, double* usq, double* vsq, double* hre, double* him,
-                   int64_t hstride, const double* coef, int H, int init, void* s) {
-    return fus_field_accumulate_f32(u, v, n, pmax, pmin, usq, vsq, hre, him, hstride, coef, H, init, s);
-  }
-  static int bioheat(float bw, float aw, int kind, float gate, float ta, double dt, const float* minv, const float* pr, const float* s, float* b, float* T0, float* Tn, float* acc,
-                     double* cem43, float* tmax, int init, int64_t nlocal, int64_t ntotal, void* st) {
-    return fus_bioheat_stage_f32(bw, aw, kind, gate, ta, dt, minv, pr, s, b, T0, Tn, acc, cem43, tmax, init, nlocal, ntotal, st);
-  }
-  static int source_array(float* y, const float* c1, const float* c2, const float* dA, const int32_t* dmA, const int32_t* eid, int64_t nA,
-                          const double* a, const double* ph, const double* tau, int64_t E, const float* xB, const float* cB, const float* dB,
-                          const int32_t* dmB, int64_t nB, int N, const double* stage, bool dev, void* s) {
-    return dev ? fus_facet_source_array_dev_f32(y, c1, c2, dA, dmA, eid, nA, a, ph, tau, E, xB, cB, dB, dmB, nB, N, stage, s)
-               : fus_facet_source_array_f32(y, c1, c2, dA, dmA, eid, nA, a, ph, tau, E, xB, cB, dB, dmB, nB, N, stage, s);
-  }
-};
+// the entry point of a typed pair for T: f64 for double, f32 for float.  The call that follows is checked by the compiler against the
+// prototype of fus_gpu.h, so a functor cannot pass what the C ABI does not declare.
+template <typename T, typename F64, typename F32>
+constexpr typename std::conditional<std::is_same<T, double>::value, F64, F32>::type typed(F64 f64, F32 f32) {
+  static_assert(std::is_same<T, double>::value || std::is_same<T, float>::value, "T: float or double");
+  return std::get<std::is_same<T, float>::value ? 1 : 0>(std::pair<F64, F32>(f64, f32));
+}
 
 // a device allocation owned by a functor: released when the functor's constructor throws after it, too (a member that is
 // fully constructed is destroyed then; a raw pointer freed by the class's own destructor is not).  The stream the geometry
@@ -242,7 +157,7 @@ struct GatherStaticPlan {
     const int64_t bytes = fus_mass_gather_static_bytes(ndof_per_entity, n_entities, (int)sizeof(T));
     if (bytes < 0) return;
     check_hip(hipMalloc(&ws, (size_t)bytes), "hipMalloc(static companion of the gather plan)");
-    const int rc = Abi<T>::static_build(gather_ws, detJ, ws, bytes, stream);
+    const int rc = typed<T>(fus_mass_gather_static_build_f64, fus_mass_gather_static_build_f32)(gather_ws, detJ, ws, bytes, stream);
     if (rc == FUS_ERR_UNSUPPORTED_ENTITY) return;
     check(rc, "fus_mass_gather_static_build");
     ok = true;
@@ -263,7 +178,8 @@ public:
   MassSpectral3D(const int32_t* dofmap, int64_t ncells, const Geometry<T>& geo, hipStream_t stream = nullptr) : Nc(ncells) {
     check_abi();  // before anything is allocated
     detJ_own_.allocate((size_t)Nc * Nd, stream, "hipMalloc(detJ)");
-    check(detail::Abi<T>::geometry(geo.x_g, geo.x_dofs, geo.dphi_p1, geo.weights, Nd, Nc, nullptr, detJ_own_.p, stream),
+    check(detail::typed<T>(fus_geometry_factors_f64, fus_geometry_factors_f32)(geo.x_g, geo.x_dofs, geo.dphi_p1, geo.weights, Nd, Nc, nullptr,
+                                                                               detJ_own_.p, stream),
           "fus_geometry_factors (detJ)");
     detJ_ = detJ_own_.p;
     plan_.build(dofmap, Nd, Nc, stream);
@@ -297,14 +213,17 @@ public:
   /// y += M x   (x, y: device vectors of nlocal + nghost entries; coeffs: device T[ncells])
   void operator()(const T* x, const T* coeffs, T* y, hipStream_t stream = nullptr) const {
     if (static_.ok)
-      check(detail::Abi<T>::mass_gather_static(x, coeffs, y, gather_.ws, static_.ws, Nd, Nc, stream), "fus_mass_apply_gather_static");
+      check(detail::typed<T>(fus_mass_apply_gather_static_f64, fus_mass_apply_gather_static_f32)(x, coeffs, y, gather_.ws, static_.ws, Nd, Nc, stream),
+            "fus_mass_apply_gather_static");
     else if (gather_.ok)
-      check(detail::Abi<T>::mass_gather(x, coeffs, y, detJ_, gather_.ws, Nd, Nc, stream), "fus_mass_apply_gather");
+      check(detail::typed<T>(fus_mass_apply_gather_f64, fus_mass_apply_gather_f32)(x, coeffs, y, detJ_, gather_.ws, Nd, Nc, stream),
+            "fus_mass_apply_gather");
     else
       apply_atomic(x, coeffs, y, stream);
   }
   void apply_atomic(const T* x, const T* coeffs, T* y, hipStream_t stream = nullptr) const {
-    check(detail::Abi<T>::mass(x, coeffs, y, detJ_, plan_.ws, Nd, plan_.epb, Nc, stream), "fus_mass_apply_planned");
+    check(detail::typed<T>(fus_mass_apply_planned_f64, fus_mass_apply_planned_f32)(x, coeffs, y, detJ_, plan_.ws, Nd, plan_.epb, Nc, stream),
+          "fus_mass_apply_planned");
   }
   const T* detJ() const { return detJ_; }
 
@@ -330,7 +249,8 @@ public:
       : Nc(ncells), dphi_(dphi) {
     check_abi();  // before anything is allocated
     G_own_.allocate((size_t)Nc * Nd * 6, stream, "hipMalloc(G)");
-    check(detail::Abi<T>::geometry(geo.x_g, geo.x_dofs, geo.dphi_p1, geo.weights, Nd, Nc, G_own_.p, nullptr, stream),
+    check(detail::typed<T>(fus_geometry_factors_f64, fus_geometry_factors_f32)(geo.x_g, geo.x_dofs, geo.dphi_p1, geo.weights, Nd, Nc, G_own_.p,
+                                                                               nullptr, stream),
           "fus_geometry_factors (G)");
     G_ = G_own_.p;
     plan_.build(dofmap, Nd, Nc, stream);
@@ -345,7 +265,8 @@ public:
   StiffnessSpectral3D& operator=(const StiffnessSpectral3D&) = delete;
   /// y += K x
   void operator()(const T* x, const T* coeffs, T* y, hipStream_t stream = nullptr) const {
-    check(detail::Abi<T>::stiffness(x, coeffs, y, G_, plan_.ws, dphi_, P, Nc, stream), "fus_stiffness_apply_planned");
+    check(detail::typed<T>(fus_stiffness_apply_planned_f64, fus_stiffness_apply_planned_f32)(x, coeffs, y, G_, plan_.ws, dphi_, P, Nc, stream),
+          "fus_stiffness_apply_planned");
   }
   const T* G() const { return G_; }
 
@@ -377,7 +298,8 @@ public:
   GradientSpectral3D& operator=(const GradientSpectral3D&) = delete;
   /// y: T[3][ystride], ystride >= number of dofs; contributions are added
   void operator()(const T* x, const T* coeffs, T* y, int64_t ystride, hipStream_t stream = nullptr) const {
-    check(detail::Abi<T>::gradient(x, coeffs, y, ystride, x_g_, x_dofs_, pts_, wts_, plan_.ws, dphi_, P, Nc, stream),
+    check(detail::typed<T>(fus_gradient_apply_planned_geom_f64, fus_gradient_apply_planned_geom_f32)(x, coeffs, y, ystride, x_g_, x_dofs_, pts_, wts_,
+                                                                                                     plan_.ws, dphi_, P, Nc, stream),
           "fus_gradient_apply_planned_geom");
   }
 
@@ -405,8 +327,8 @@ class PointProbe {
   // the general launch: row ``slot`` of rec[capacity][npts], running max / min, H harmonic accumulators (null = off)
   void operator()(const T* u, T* rec, int64_t capacity, int slot, double* pmax, double* pmin, double* hre, double* him,
                   const double* coef, int H, void* stream = nullptr) const {
-    check(detail::Abi<T>::probe(u, cells_, npts_, dofmap_, ncells_, weights_, P, rec, capacity, slot, pmax, pmin, hre, him, coef, H,
-                                stream),
+    check(detail::typed<T>(fus_probe_eval_f64, fus_probe_eval_f32)(u, cells_, npts_, dofmap_, ncells_, weights_, P, rec, capacity, slot, pmax, pmin,
+                                                                   hre, him, coef, H, stream),
           "fus_probe_eval");
   }
   int64_t npts() const { return npts_; }
@@ -432,7 +354,8 @@ class FieldAccumulator {
   }
   // one record of (u, v); ``coef``: the 2H factors of this step in device memory; ``init``: the first record of a window
   void operator()(const T* u, const T* v, const double* coef, bool init, void* stream = nullptr) const {
-    check(detail::Abi<T>::field(u, v, n_, pmax_, pmin_, usq_, vsq_, hre_, him_, hstride_, coef, H_, init ? 1 : 0, stream),
+    check(detail::typed<T>(fus_field_accumulate_f64, fus_field_accumulate_f32)(u, v, n_, pmax_, pmin_, usq_, vsq_, hre_, him_, hstride_, coef, H_,
+                                                                               init ? 1 : 0, stream),
           "fus_field_accumulate");
   }
 
@@ -461,8 +384,9 @@ class BioheatStage {
   void operator()(int i, double dt, T gate, bool init = false, void* stream = nullptr) const {
     static const double a[4] = {0.0, 0.5, 0.5, 1.0}, bq[4] = {1.0 / 6.0, 1.0 / 3.0, 1.0 / 3.0, 1.0 / 6.0};
     const int kind = i == 3 ? LAST : (i == 0 ? FIRST : MIDDLE);
-    check(detail::Abi<T>::bioheat((T)(bq[i] * dt), (T)(i == 3 ? 0.0 : a[i + 1] * dt), kind, gate, ta_, dt, minv_, pr_, s_, b_, T0_, Tn_, acc_,
-                                  cem43_, tmax_, init ? 1 : 0, nlocal_, ntotal_, stream),
+    check(detail::typed<T>(fus_bioheat_stage_f64, fus_bioheat_stage_f32)((T)(bq[i] * dt), (T)(i == 3 ? 0.0 : a[i + 1] * dt), kind, gate, ta_, dt, minv_,
+                                                                         pr_, s_, b_, T0_, Tn_, acc_, cem43_, tmax_, init ? 1 : 0, nlocal_, ntotal_,
+                                                                         stream),
           "fus_bioheat_stage");
   }
 
@@ -498,8 +422,9 @@ class FacetSourceArray {
 
  private:
   void launch(T* y, const double* stage, bool dev, const T* xB, void* stream) const {
-    check(detail::Abi<T>::source_array(y, c1_, c2_, detJ_, dm_, eid_, nA_, a_, ph_, tau_, E_, xB, cB_, detJB_, dmB_, xB ? nB_ : 0, N_, stage,
-                                       dev, stream),
+    const auto entry = dev ? detail::typed<T>(fus_facet_source_array_dev_f64, fus_facet_source_array_dev_f32)
+                           : detail::typed<T>(fus_facet_source_array_f64, fus_facet_source_array_f32);
+    check(entry(y, c1_, c2_, detJ_, dm_, eid_, nA_, a_, ph_, tau_, E_, xB, cB_, detJB_, dmB_, xB ? nB_ : 0, N_, stage, stream),
           "fus_facet_source_array");
   }
   const T *c1_, *c2_, *detJ_;

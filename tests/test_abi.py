@@ -30,6 +30,124 @@ def test_library_exports_every_declared_symbol():
     assert bound == set(names), sorted(bound ^ set(names))
 
 
+def test_header_parser_on_small_texts():
+    """``_lib.parse_header`` on texts that hold each form the header uses (and some it does not yet): the exact type lists, and a
+    refusal, never a guess, for what it cannot bind."""
+    lib_mod = pkg("_lib")
+    i, i64, d, f, vp = C.c_int, C.c_int64, C.c_double, C.c_float, C.c_void_p
+    text = """
+        #ifndef FUS_GPU_H
+        #define FUS_GPU_H
+        #include <stdint.h>
+        #ifdef __cplusplus
+        extern "C" {
+        #endif
+        #define FUS_OK 0
+        #define FUS_ERR_COMM (-5) /* a comment after the value */
+        #define FUS_MAX_DEGREE 10 // and one of the other kind
+        /* a comment that names fus_not_a_function(int x); over
+           two lines */
+        int fus_multi_line(const double* x, double alpha,
+                           int64_t n,
+                           void* stream);
+        int fus_comment_inside(void* id /* FUS_UNIQUE_ID_BYTES, (128) */, int n);
+        int64_t fus_const_both(const int a, int const b, const float* const c, float const d, const void* const* e);
+        int fus_unnamed(int, double, const float*, int64_t);
+        typedef struct fus_thing* fus_thing_t;
+        int fus_handle(fus_thing_t thing, const fus_thing_t other, fus_thing_t* out, const fus_thing_t* many);
+        int fus_nothing(void);
+        int fus_nothing_at_all();
+        void* fus_returns_pointer(fus_thing_t thing);
+        const char *fus_returns_text(int code);
+        #ifdef __cplusplus
+        }
+        #endif
+        #endif
+    """
+    functions, defines = lib_mod.parse_header(text)
+    assert functions == {
+        "fus_multi_line": (i, [vp, d, i64, vp]),
+        "fus_comment_inside": (i, [vp, i]),
+        "fus_const_both": (i64, [i, i, vp, f, vp]),
+        "fus_unnamed": (i, [i, d, vp, i64]),
+        "fus_handle": (i, [vp, vp, vp, vp]),
+        "fus_nothing": (i, []),
+        "fus_nothing_at_all": (i, []),
+        "fus_returns_pointer": (vp, [vp]),
+        "fus_returns_text": (C.c_char_p, [i]),
+    }
+    assert list(functions) == ["fus_multi_line", "fus_comment_inside", "fus_const_both", "fus_unnamed", "fus_handle", "fus_nothing",
+                               "fus_nothing_at_all", "fus_returns_pointer", "fus_returns_text"]  # the header's order
+    assert defines == {"FUS_OK": 0, "FUS_ERR_COMM": -5, "FUS_MAX_DEGREE": 10}
+    refused = {
+        "an unknown type by value": "int fus_bad(size_t n);",
+        "a two-word type by value": "int fus_bad(unsigned int n);",
+        "a struct by value": "int fus_bad(struct fus_thing t);",
+        "a handle before its typedef": "int fus_bad(fus_thing_t t); typedef struct fus_thing* fus_thing_t;",
+        "an array parameter": "int fus_bad(int n[4]);",
+        "parentheses in the list (a callback)": "int fus_bad(int (*callback)(int), void* stream);",
+        "an unknown return type": "double fus_bad(int n);",
+        "void as return type": "void fus_bad(int n);",
+        "two prototypes without a semicolon between them": "int fus_bad(int n) int fus_worse(int n);",
+        "a function that is not fus_*": "int other_function(int n);",
+        "another typedef": "typedef int fus_index_t; int fus_bad(fus_index_t n);",
+        "an empty parameter": "int fus_bad(int n, , int m);",
+    }
+    for what, bad in refused.items():
+        try:
+            lib_mod.parse_header("int fus_good(int n);\n" + bad)
+        except lib_mod.FusGpuError as e:
+            assert re.search("fus_bad|other_function|fus_index_t", str(e)), (what, e)  # the message names the declaration
+        else:
+            pytest.fail(f"the parser bound {what}: {bad}")
+
+
+def test_a_missing_header_is_an_error_with_its_path(monkeypatch, tmp_path):
+    lib_mod = pkg("_lib")
+    missing = str(tmp_path / "include" / "fus_gpu.h")
+    monkeypatch.setattr(lib_mod, "HEADER_PATH", missing)
+    with pytest.raises(lib_mod.FusGpuError, match=re.escape(missing)):
+        lib_mod._read_header()
+
+
+def test_binding_of_the_real_header_pinned():
+    """Three entry points of different shape, the return types that are not ``int`` and the constants, as literals: what the parser
+    must find in include/fus_gpu.h as it stands."""
+    lib_mod = pkg("_lib")
+    i, i64, d, f, vp = C.c_int, C.c_int64, C.c_double, C.c_float, C.c_void_p
+    sig = lib_mod.SIGNATURES
+    assert len(sig) == 123 and len(lib_mod.DECLARATIONS) == 125
+    assert sig["fus_bioheat_stage_f32"] == [f, f, i, f, f, d, vp, vp, vp, vp, vp, vp, vp, vp, vp, i, i64, i64, vp]
+    assert sig["fus_bioheat_stage_f64"] == [d, d, i, d, d, d, vp, vp, vp, vp, vp, vp, vp, vp, vp, i, i64, i64, vp]
+    assert sig["fus_halo_create"] == [vp, i, i64, i64, i, vp, vp, vp, i, vp, vp, vp, vp]
+    assert sig["fus_device_info"] == [i, vp, vp, vp, vp]
+    assert sig["fus_rk4_stage_nl2_f32"] == [f, f, i] + [vp] * 10 + [f, vp, i64, i64, vp]
+    assert lib_mod.DECLARATIONS["fus_error_string"] == (C.c_char_p, [i]) and lib_mod.DECLARATIONS["fus_source_hash"] == (C.c_char_p, [])
+    not_int = {name: restype for name, (restype, _) in lib_mod.DECLARATIONS.items() if restype is not i}
+    assert not_int == {"fus_source_hash": C.c_char_p, "fus_error_string": C.c_char_p, "fus_comm_last_error": C.c_char_p,
+                       "fus_comm_stream": vp, "fus_stiffness_plan_bytes": i64, "fus_plan_bytes": i64,
+                       "fus_mass_gather_plan_bytes": i64, "fus_mass_gather_static_bytes": i64, "fus_halo_ipc_blob_bytes": i64}
+    for types in sig.values():  # a pointer is c_void_p itself: tests/test_operator_routes.py tells pointers from numbers by identity
+        assert all(t in (i, i64, d, f, vp) for t in types)
+    got = {n: getattr(lib_mod, n) for n in ("ABI_VERSION", "ERR_COMM", "ERR_UNSUPPORTED_ENTITY", "TUNE_STIFFNESS_VARIANT", "TUNE_XCD_REMAP",
+                                            "TUNE_MASS_VARIANT", "TUNE_PLAN_VARIANT", "TUNE_PLAN_RUNS", "TUNE_VECTOR_STREAM", "TUNE_PLAN_ROWS",
+                                            "TUNE_PLAN_XCD_GROUP", "UNIQUE_ID_BYTES", "FORK_LAZY", "FORK_ATTACH", "MIN_DEGREE", "MAX_DEGREE")}
+    assert got == {"ABI_VERSION": 3, "ERR_COMM": -5, "ERR_UNSUPPORTED_ENTITY": -3, "TUNE_STIFFNESS_VARIANT": 1, "TUNE_XCD_REMAP": 2,
+                   "TUNE_MASS_VARIANT": 3, "TUNE_PLAN_VARIANT": 4, "TUNE_PLAN_RUNS": 5, "TUNE_VECTOR_STREAM": 6, "TUNE_PLAN_ROWS": 7,
+                   "TUNE_PLAN_XCD_GROUP": 8, "UNIQUE_ID_BYTES": 128, "FORK_LAZY": 1, "FORK_ATTACH": 2, "MIN_DEGREE": 1, "MAX_DEGREE": 10}
+
+
+def test_bind_declares_every_function_on_a_library():
+    """``_lib.bind`` on a fresh ``CDLL`` (what ``load()`` and tools/ab_stream_launch.py do): every declared function carries the
+    header's types afterwards."""
+    lib_mod = pkg("_lib")
+    raw = lib_mod.bind(C.CDLL(lib_mod.LIB_PATH))
+    for name, (restype, argtypes) in lib_mod.DECLARATIONS.items():
+        fn = getattr(raw, name)
+        assert fn.restype is restype and list(fn.argtypes) == argtypes, name
+    assert raw.fus_source_hash() == lib_mod.load().fus_source_hash()
+
+
 def test_host_only_entry_points():
     lib_mod = pkg("_lib")
     lib = lib_mod.load()

@@ -32,17 +32,8 @@ def main(argv=None):
 
     lib_mod = fusgpu_loader.submodule("_lib")
 
-    def load(path):  # the declarations of _lib.load() on a library of our choosing
-        lib = C.CDLL(os.path.abspath(path))
-        for name, argtypes in lib_mod.SIGNATURES.items():
-            fn = getattr(lib, name)
-            fn.argtypes = argtypes
-            fn.restype = C.c_int64 if name.endswith("_bytes") else C.c_int
-        lib.fus_source_hash.restype = C.c_char_p
-        return lib
-
     torch.cuda.set_device(0)
-    libs = {"parent": load(a.parent_lib), "head": load(a.head_lib)}
+    libs = {arm: lib_mod.bind(C.CDLL(os.path.abspath(path))) for arm, path in (("parent", a.parent_lib), ("head", a.head_lib))}
     sp = lib_mod.stream_ptr
     with measure.Log("ab_stream_launch", a.log) as log:
         log(f"# tools/ab_stream_launch.py on {torch.cuda.get_device_name(0)}: parent library {libs['parent'].fus_source_hash().decode()}, "
