@@ -19,6 +19,8 @@ precompute  detJ / G / facet detJ (host)
 boxmesh     synthetic structured hex meshes + block partitioning
 gll         GLL nodes, weights, derivative tables
 device      numba.cuda-like shim over torch tensors (to_device, ...)
+sources     SourceArray (phased-array facet sources), PointSources (monopoles inside the volume)
+receivers   ElementReceivers (what each array element receives), time_reversal
 _lib        ctypes binding of csrc/libfusgpu.so (fails loudly if missing)
 """
 

@@ -18,6 +18,9 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 # FUS_LIB_PATH: load another build of the same ABI (A/B runs of two builds on one device)
 LIB_PATH = os.environ.get("FUS_LIB_PATH") or os.path.join(_HERE, "csrc", "libfusgpu.so")
 HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "fus_gpu.h")
+# headers that extend the ABI with further entry points of the same library (each includes fus_gpu.h): additions since the set of
+# functions of fus_gpu.h was pinned are declared there, and bound from there in the same way
+EXTENSION_HEADER_PATHS = (os.path.join(os.path.dirname(_HERE), "include", "fus_gpu_array.h"),)
 
 
 class FusGpuError(RuntimeError):
@@ -62,18 +65,24 @@ def parse_header(text):
     return functions, defines
 
 
-def _read_header():
+def _read_header(path=None):
+    path = HEADER_PATH if path is None else path
     try:
-        with open(HEADER_PATH) as f:
+        with open(path) as f:
             return parse_header(f.read())
     except OSError as e:
-        raise FusGpuError(f"{HEADER_PATH}: the C ABI's header, which this binding is derived from, cannot be read ({e})") from None
+        raise FusGpuError(f"{path}: the C ABI's header, which this binding is derived from, cannot be read ({e})") from None
 
 
 # every function include/fus_gpu.h declares, and its integer macros: the header is the one declaration, nothing is restated here
 DECLARATIONS, _DEFINES = _read_header()
 # {name: argtypes} of the entry points (what a stand-in library has to answer); the two that only return a string are bound like the rest
 SIGNATURES = {name: argtypes for name, (_, argtypes) in DECLARATIONS.items() if name not in ("fus_error_string", "fus_source_hash")}
+
+# ... and every function the extension headers declare, {name: (restype, [argtypes])}: bound with the rest, kept apart from them
+EXTENSIONS = {name: decl for path in EXTENSION_HEADER_PATHS for name, decl in _read_header(path)[0].items()}
+if set(EXTENSIONS) & set(DECLARATIONS):
+    raise FusGpuError(f"declared both in include/fus_gpu.h and in an extension header: {sorted(set(EXTENSIONS) & set(DECLARATIONS))}")
 
 ABI_VERSION = _DEFINES["FUS_ABI_VERSION"]
 ERR_COMM = _DEFINES["FUS_ERR_COMM"]
@@ -95,8 +104,9 @@ _lib = None
 
 
 def bind(cdll):
-    """Set ``argtypes`` and ``restype`` of every declared function on a loaded library; AttributeError if it lacks one."""
-    for name, (restype, argtypes) in DECLARATIONS.items():
+    """Set ``argtypes`` and ``restype`` of every declared function (include/fus_gpu.h and its extension headers) on a loaded library;
+    AttributeError if it lacks one."""
+    for name, (restype, argtypes) in {**DECLARATIONS, **EXTENSIONS}.items():
         fn = getattr(cdll, name)
         fn.argtypes, fn.restype = argtypes, restype
     return cdll

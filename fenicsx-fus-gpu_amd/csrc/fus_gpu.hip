@@ -3,6 +3,7 @@
 // its _f64 / _f32 twins are one-line forwards stamped by FUS_TYPED at the end of this file.
 // Build: see Makefile (hipcc --offload-arch=gfx950).
 #include "../../include/fus_gpu.h"
+#include "../../include/fus_gpu_array.h"
 
 #include <hip/hip_runtime.h>
 
@@ -10,6 +11,7 @@
 #include <cstdio>
 
 #include "bioheat.hpp"
+#include "element_receive.hpp"
 #include "field_monitor.hpp"
 #include "fus_dispatch.hpp"
 #include "geometry.hpp"
@@ -17,6 +19,7 @@
 #include "mass.hpp"
 #include "mass_gather.hpp"
 #include "plan_build.hpp"
+#include "point_source.hpp"
 #include "probe.hpp"
 #include "rk4.hpp"
 #include "source_array.hpp"
@@ -185,6 +188,47 @@ int probe_eval(const T* u, const int32_t* cells, int64_t npts, const int32_t* do
     e = fus::launch_probe_eval<T, decltype(p)::value>(u, cells, dofmap, weights, npts, ncells, row, pmax, pmin, hre, him, coef, H, s);
   });
   return hip_rc(e);
+}
+
+// point sources (csrc/point_source.hpp), the transpose of probe_eval: every check before any device work; npts == 0 is a no-op.
+// ``stage``: the fp64 block {t, w0, A, f0, alpha, D} in host memory, copied into the launch.
+template <typename T>
+int point_source(T* y, const int32_t* cells, int64_t npts, const int32_t* dofmap, int64_t ncells, const T* weights, int P,
+                 const double* amp, const double* phase, const double* delay, const double* stage, void* stream) {
+  if (npts < 0 || ncells < 0) return FUS_ERR_INVALID_ARGUMENT;
+  if (P < FUS_MIN_DEGREE || P > FUS_MAX_DEGREE) return FUS_ERR_UNSUPPORTED_DEGREE;
+  if (npts == 0) return FUS_OK;
+  if (!y || !cells || !dofmap || !weights || !amp || !phase || !delay || !stage) return FUS_ERR_INVALID_ARGUMENT;
+  if (misaligned(y, sizeof(T)) || misaligned(weights, sizeof(T)) || misaligned(cells, sizeof(int32_t)) ||
+      misaligned(dofmap, sizeof(int32_t)) || misaligned(stage, sizeof(double)) || misaligned(amp, sizeof(double)) ||
+      misaligned(phase, sizeof(double)) || misaligned(delay, sizeof(double)))
+    return FUS_ERR_INVALID_ARGUMENT;
+  const fus::SourceStage st{stage[0], stage[1], stage[2], stage[3], stage[4], stage[5]};
+  // a NaN fails every comparison: f0 and alpha must be positive, D zero (continuous wave) or positive
+  if (!(st.f0 > 0.0) || !(st.alpha > 0.0) || !(st.D >= 0.0)) return FUS_ERR_INVALID_ARGUMENT;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  hipError_t e = hipErrorInvalidValue;
+  degree_dispatch(P, [&](auto p) {
+    e = fus::launch_point_source<T, decltype(p)::value>(y, cells, dofmap, weights, npts, ncells, amp, phase, delay, st, s);
+  });
+  return hip_rc(e);
+}
+
+// element receivers (csrc/element_receive.hpp): every check before any device work; nelem == 0 is a no-op
+template <typename T>
+int element_receive(const T* u, const int32_t* dof, const T* wgt, const int64_t* offsets, int64_t nelem, T* rec, int64_t capacity,
+                    int slot, double* hre, double* him, const double* coef, int H, void* stream) {
+  if (nelem < 0 || capacity < 0 || H < 0 || nelem > 0x7fffffffLL) return FUS_ERR_INVALID_ARGUMENT;
+  if (nelem == 0) return FUS_OK;
+  if (!u || !dof || !wgt || !offsets) return FUS_ERR_INVALID_ARGUMENT;
+  if (rec && (slot < 0 || slot >= capacity)) return FUS_ERR_INVALID_ARGUMENT;
+  if ((hre || him || H > 0) && (!hre || !him || !coef || H < 1)) return FUS_ERR_INVALID_ARGUMENT;
+  if (misaligned(u, sizeof(T)) || misaligned(wgt, sizeof(T)) || misaligned(rec, sizeof(T)) || misaligned(dof, sizeof(int32_t)) ||
+      misaligned(offsets, sizeof(int64_t)) || misaligned(hre, sizeof(double)) || misaligned(him, sizeof(double)) ||
+      misaligned(coef, sizeof(double)))
+    return FUS_ERR_INVALID_ARGUMENT;
+  T* row = rec ? rec + (int64_t)slot * nelem : nullptr;
+  return hip_rc(fus::launch_element_receive<T>(u, dof, wgt, offsets, nelem, row, hre, him, coef, H, static_cast<hipStream_t>(stream)));
 }
 
 // full-field monitors (csrc/field_monitor.hpp): every check before any device work; n == 0 or no output requested is a no-op
@@ -664,6 +708,14 @@ int fus_plan_mark_exclusive(void* workspace, int N, int entities_per_batch, int6
                            T* rec, int64_t capacity, int slot, double* pmax, double* pmin, double* hre, double* him, const double* coef,   \
                            int H, void* s) {                                                                                               \
     return probe_eval<T>(u, cells, npts, dofmap, ncells, weights, P, rec, capacity, slot, pmax, pmin, hre, him, coef, H, s);               \
+  }                                                                                                                                        \
+  int fus_point_source_##SUF(T* y, const int32_t* cells, int64_t npts, const int32_t* dofmap, int64_t ncells, const T* weights, int P,     \
+                             const double* amplitude, const double* phase, const double* delay, const double* stage, void* s) {            \
+    return point_source<T>(y, cells, npts, dofmap, ncells, weights, P, amplitude, phase, delay, stage, s);                                 \
+  }                                                                                                                                        \
+  int fus_element_receive_##SUF(const T* u, const int32_t* dof, const T* wgt, const int64_t* offsets, int64_t nelem, T* rec,               \
+                                int64_t capacity, int slot, double* hre, double* him, const double* coef, int H, void* s) {                \
+    return element_receive<T>(u, dof, wgt, offsets, nelem, rec, capacity, slot, hre, him, coef, H, s);                                     \
   }                                                                                                                                        \
   int fus_field_accumulate_##SUF(const T* u, const T* v, int64_t n, T* pmax, T* pmin, double* usq, double* vsq, double* hre, double* him,  \
                                  int64_t hstride, const double* coef, int H, int init, void* s) {                                          \

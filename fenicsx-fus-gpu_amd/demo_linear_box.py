@@ -7,6 +7,8 @@ replaces dolfinx's ``create_box``.
 
     python fenicsx-fus-gpu_amd/demo_linear_box.py [--cells N] [--degree P] [--reference-sequence] [--out file.npz]
     python fenicsx-fus-gpu_amd/demo_linear_box.py --array 8,8 --focus 0.06,0.05,0.06     # phased array focused on a point
+    python fenicsx-fus-gpu_amd/demo_linear_box.py --length 0.012 --cells 8 --time-reversal 0.011 0.0063 0.0058 --elements 3 3
+                                                   # listen to a virtual source at the focus through an aberrating slab, fire back
     python -m torch.distributed.run --nproc-per-node 8 fenicsx-fus-gpu_amd/demo_linear_box.py   # one rank per GPU
 
 Prints the reference's progress / timing lines (cuda/demo_linear_box.py:125,183,569-581) and
@@ -44,9 +46,19 @@ def main():
     ap.add_argument("--sponge", type=int, default=0, metavar="CELLS",
                     help="absorbing sponge layer of CELLS cells inside the four lateral faces (y and z), which the reference leaves rigid "
                          "(sponge.SpongeLayer: one sparse damping launch per stage); default 0: off")
+    ap.add_argument("--length", type=float, default=0.12, help="edge of the box in m (default: the reference's 0.12)")
+    ap.add_argument("--time-reversal", type=float, nargs=3, default=None, metavar=("FX", "FY", "FZ"),
+                    help="time-reversal focusing on the point (FX, FY, FZ) through an aberrating slab (twice the speed of sound, one "
+                         "wavelength thick, in front of the y > L/2 half of the aperture): a receive run with a virtual point source at the "
+                         "focus (sources.PointSources, receivers.ElementReceivers), then transmit runs with the conjugate phases "
+                         "(receivers.time_reversal) and with the geometric ones (sources.focus_phases); prints the first-harmonic "
+                         "amplitude at the focus of both.  One rank; composes with --sponge")
+    ap.add_argument("--elements", type=int, nargs=2, default=(4, 4), metavar=("NY", "NZ"), help="elements of the --time-reversal array (default 4 4)")
     a = ap.parse_args()
     if a.focus and not a.array:
         ap.error("--focus needs --array")
+    if a.time_reversal and (a.array or int(os.environ.get("WORLD_SIZE", "1")) > 1):
+        ap.error("--time-reversal runs on one rank and builds its own array (--elements)")
 
     import torch
     import torch.distributed as dist
@@ -65,7 +77,7 @@ def main():
     float_type = np.float64
     source_frequency, source_amplitude = 0.5e6, 60000.0
     speed_of_sound, density = 1500.0, 1000.0
-    domain_length = 0.12
+    domain_length = a.length
     wave_length = speed_of_sound / source_frequency
     num_element = a.cells if a.cells is not None else int(2 * domain_length / wave_length)
     grid = boxmesh.default_grid(world)
@@ -99,6 +111,8 @@ def main():
             raise SystemExit(f"--sponge: 1 .. {num_element // 2} cells")
         # the GLOBAL box, so every rank evaluates the same profile on its own dofs
         sponge = sp.SpongeLayer(sp.box_profile((0.0, 0.0, 0.0), mesh.length, a.sponge * domain_length / num_element, sp.LATERAL, speed_of_sound))
+    if a.time_reversal:
+        return time_reversal_run(a, mesh, sponge, float_type, speed_of_sound, density, source_frequency, source_amplitude)
     solver = ls.LinearSpectral3D(mesh, float_type, speed_of_sound, density, source_frequency, source_amplitude,
                                  comm=comm, fused=not a.reference_sequence, source=source, sponge=sponge)
     solver.init()
@@ -162,6 +176,47 @@ def main():
                     np.savetxt(f, data, fmt="%.8f", delimiter=",")
     if world > 1:
         dist.destroy_process_group()
+
+
+def time_reversal_run(a, mesh, sponge, float_type, c0, density, f0, p0):
+    """--time-reversal: listen to a virtual point source at the focus through the slab, then fire the array with the conjugate and
+    with the geometric phases and compare the first harmonic at the focus (recorded on the device over the last two periods)."""
+    import fusgpu_loader
+
+    ls, src, rxm, sens = (fusgpu_loader.submodule(m) for m in ("linear_solver", "sources", "receivers", "sensors"))
+    L, lam, period = mesh.length, c0 / f0, 1.0 / f0
+    focus = np.asarray(a.time_reversal, dtype=np.float64)[None, :]
+    ny, nz = a.elements
+    cen = mesh.x_g.astype(np.float64)[mesh.x_dofs].mean(axis=1)
+    slab = (cen[:, 0] > lam) & (cen[:, 0] < 2.0 * lam) & (cen[:, 1] > 0.5 * L[1])
+    if not slab.any() or np.any(np.abs(cen[slab] - focus).max(axis=1) < 0.5 * mesh.h[0]):
+        raise SystemExit("--time-reversal: the slab (x in (lambda, 2 lambda), y > L/2) holds no cell of this mesh, or the focus lies in it")
+    c = np.where(slab, 2.0 * c0, c0)
+    dt, _, _ = ls.snap_time_step(ls.time_step_parameters(mesh, a.degree, 2.0 * c0, f0, L[0]), a.degree, 2.0 * c0, f0, L[0])
+    tf = L[0] / c0 + 8.0 * period  # the ramp (4 periods), the transit, and the two periods that are recorded
+    kw = dict(speed_of_sound=c, density=density, source_frequency=f0, reference_speed_of_sound=c0, fused=not a.reference_sequence, sponge=sponge)
+    grid = src.grid_elements(ny, nz, (0.0, L[1]), (0.0, L[2]))
+    print(f"Time reversal: focus {tuple(float(v) for v in focus[0])}, {ny} x {nz} elements, slab of {int(slab.sum())} cells at c = {2.0 * c0}, "
+          f"{int(round(tf / dt))} steps per run", flush=True)
+    listen = ls.LinearSpectral3D(mesh, float_type, source_amplitude=0.0, point_source=src.PointSources(focus), **kw)
+    rx = rxm.ElementReceivers(mesh, grid, float_type, harmonics=(1,), frequency=f0, n_elements=ny * nz, detJ=listen.detJ_f1)
+    listen.init()
+    listen.rk4(0.0, tf, dt, max_steps=a.max_steps, receivers=rx, record_from=tf - 2.0 * period)
+    R = rx.harmonic(1)
+
+    def transmit(array):
+        s = ls.LinearSpectral3D(mesh, float_type, source_amplitude=p0, source=array, **kw)
+        probe = sens.PointSensors(mesh, focus, float_type, harmonics=(1,), frequency=f0)
+        s.init()
+        s.rk4(0.0, tf, dt, max_steps=a.max_steps, sensors=probe, record_from=tf - 2.0 * period)
+        return float(probe.harmonic_amplitude(1)[0]), s
+
+    a_tr, s = transmit(rxm.time_reversal(rx))
+    centres = src.grid_centres(ny, nz, 0.0, (0.0, L[1]), (0.0, L[2]))
+    a_geo, _ = transmit(src.SourceArray(grid, phase=src.focus_phases(centres, focus[0], c0, f0), n_elements=ny * nz))
+    bound = s.p0 * s.w0 / s.c0 / density * float(np.sum(rx.areas() * np.abs(R)))  # reciprocity: sum_e |G_e|
+    print(f"First-harmonic amplitude at the focus: time reversal {a_tr:.6g}, geometric (focus_phases) {a_geo:.6g}")
+    print(f"Time-reversal gain over the geometric phases: {a_tr / a_geo:.3f} ({a_tr / bound:.3f} of the reciprocity bound {bound:.6g})")
 
 
 if __name__ == "__main__":

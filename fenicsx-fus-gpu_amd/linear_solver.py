@@ -55,7 +55,7 @@ class LinearSpectral3D(SpectralSolver3D):
                  source_frequency=0.5e6, source_amplitude=60000.0, comm=None, fused=True,
                  source_time="tn", overlap=True, halo_kernels=None, affine="auto", in_kernel_geometry="auto",
                  halo_plan=None, defer_setup_exchange=False, reference_speed_of_sound=None, keep_G=False, source=None,
-                 sponge=None):
+                 sponge=None, point_source=None, point_claim=None):
         """``speed_of_sound`` / ``density``: scalars, or one value per cell (heterogeneous medium: the DG0 material arrays of
         the reference's drivers, in the caller's cell order).  ``reference_speed_of_sound``: the c of the source term
         ``p0 w0 / c cos(w0 t)`` (cuda/demo_linear_box.py:515-530 uses the scalar of its homogeneous medium); default: the
@@ -68,7 +68,12 @@ class LinearSpectral3D(SpectralSolver3D):
         per-element amplitude, phase and delay, optionally a burst) in place of the one scalar waveform of ``source_value``;
         bound to this rank's source facets here (``self.source``), ``None`` keeps every launch as it is.  ``sponge``: a
         ``sponge.SpongeLayer`` (absorbing layer: b -= 2 sigma m v_n + sigma^2 m u_n over its owned dofs, one sparse launch per stage
-        after the facet terms); ``None`` keeps every launch as it is."""
+        after the facet terms); ``None`` keeps every launch as it is.  ``point_source``: a ``sources.PointSources`` (monopoles inside
+        the volume: b[dofmap[c][ijk]] += g_p(t) Lx[i] Ly[j] Lz[k], one launch per stage after the facet terms, at the stage's source
+        time); it coexists with ``source``, the scalar source and ``sponge``; ``source_amplitude=0.0`` silences the facet source for a
+        receive run (the virtual source of a time-reversal run, receivers.py).  ``None`` keeps every launch as it is.
+        ``point_claim``: this rank's row of ``sources.claim_points`` when several ranks are driven from one process (handed in like
+        ``halo_plan``); ranks in different processes agree through one gather."""
         c_cells, rho_cells = per_cell(speed_of_sound, mesh, "speed_of_sound"), per_cell(density, mesh, "density")
         bd1, bd2, D, G_d, detJ_d, (dF1_d, dF2_d) = self._init_common(mesh, float_type, comm, fused, source_time)
         self._init_sponge(sponge)
@@ -76,6 +81,7 @@ class LinearSpectral3D(SpectralSolver3D):
         self.rho_cells, self.c_cells = rho_cells, c_cells  # per cell, the mesh's cell order (intensity.py)
         self.f0, self.p0 = float(source_frequency), float(source_amplitude)
         self.w0 = 2.0 * np.pi * self.f0
+        self._init_point_source(point_source, point_claim)
         P, n, dev, ft = self.P, self.P + 1, self.dev, self.tdt_np
         self.D = D
         rho, c = rho_cells.astype(ft), c_cells.astype(ft)
@@ -178,6 +184,7 @@ class LinearSpectral3D(SpectralSolver3D):
                 ops.facet_source_terms(self.b, self.source, None, stage=self.source.stage_scalars(ts))
             self._mass_facet_stage(self.v_n, self.facet_coeff2, self.b, self.detJ_f2, self.fdm2)
             self._sponge_terms(self.u_n, self.v_n)
+            self._point_terms(ts)
 
         yield from self._cell_terms(self.u_n, self.v_n, facets)
         ops.pointwise_divide(self.b, self.m, self.kv)

@@ -32,7 +32,8 @@ class WesterveltSpectral3D(SpectralSolver3D):
                  source_frequency=1.1e6, source_amplitude=None, nonlinear_coefficient=3.5,
                  attenuation_coefficient_dB=0.2, comm=None, source_time="tn", overlap=True, fused=False,
                  in_kernel_geometry="auto", uniform_ratio="auto", halo_plan=None, defer_setup_exchange=False,
-                 reference_speed_of_sound=None, reference_density=None, keep_G=False, source=None, sponge=None):
+                 reference_speed_of_sound=None, reference_density=None, keep_G=False, source=None, sponge=None,
+                 point_source=None, point_claim=None):
         """``speed_of_sound``, ``density``, ``nonlinear_coefficient``, ``attenuation_coefficient_dB``: scalars, or one value per
         cell in the caller's cell order (the DG0 material arrays of cuda/demo_nonlinear_bowl.py:166-178 -- water / skull / ...).
         ``reference_speed_of_sound`` / ``reference_density``: the scalars of the source term and of the default source amplitude
@@ -44,7 +45,10 @@ class WesterveltSpectral3D(SpectralSolver3D):
         the reference launch sequence (``fused=False``) always reads G.  ``source``: a ``sources.SourceArray`` (phased array) in
         place of the one waveform of ``source_values``, as ``LinearSpectral3D``; ``None`` keeps every launch as it is.  ``sponge``: a
         ``sponge.SpongeLayer`` (absorbing layer), as ``LinearSpectral3D``, with the steady lumped mass m0 in its coefficients -- the
-        effective damping is then 2 sigma m0 / (m0 + w2 u_n), by definition; ``None`` keeps every launch as it is."""
+        effective damping is then 2 sigma m0 / (m0 + w2 u_n), by definition; ``None`` keeps every launch as it is.  ``point_source`` /
+        ``point_claim``: a ``sources.PointSources`` (monopoles inside the volume), as ``LinearSpectral3D``; it coexists with ``source``,
+        the scalar source and ``sponge``, and ``source_amplitude=0.0`` silences the facet source for a receive run; ``None`` keeps
+        every launch as it is."""
         c_cells, rho_cells = per_cell(speed_of_sound, mesh, "speed_of_sound"), per_cell(density, mesh, "density")
         beta_cells = per_cell(nonlinear_coefficient, mesh, "nonlinear_coefficient")
         att_cells = per_cell(attenuation_coefficient_dB, mesh, "attenuation_coefficient_dB")
@@ -52,6 +56,7 @@ class WesterveltSpectral3D(SpectralSolver3D):
         self._init_sponge(sponge)
         self.f0 = float(source_frequency)
         self.w0 = 2 * np.pi * self.f0
+        self._init_point_source(point_source, point_claim)
         pick = (lambda a: float(a[bd1[:, 0]].mean())) if bd1.shape[0] else (lambda a: float(a.mean()))
         self.c0 = float(reference_speed_of_sound) if reference_speed_of_sound is not None else (
             float(speed_of_sound) if np.ndim(speed_of_sound) == 0 else pick(c_cells))
@@ -251,6 +256,7 @@ class WesterveltSpectral3D(SpectralSolver3D):
             ops.facet_source_terms(self.b, self.source, None, stage=self.source.stage_scalars(ts))
         self.mass_facet(self.v_n, self.fc2_2, self.b, self.dF2, self.fdm2)
         self._sponge_terms(self.u_n, self.v_n)
+        self._point_terms(ts)
         if self.halo is not None:
             self.halo.rev(self.b)
         ops.pointwise_divide(self.b, self.m, self.kv)

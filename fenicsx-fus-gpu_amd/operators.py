@@ -653,6 +653,81 @@ def sponge_terms(y, u, v, bound):
                "fus_sponge_terms")
 
 
+def point_source_terms(y, bound, stage):
+    """The point sources' terms of one RK4 stage in one launch (csrc/point_source.hpp, ``fus_point_source_*``): with ``bound`` a
+    ``sources.BoundPointSources`` (the probe's tables ``cells`` / ``rows`` / ``weights`` and per-point ``amplitude`` / ``phase`` /
+    ``delay``) and ``stage`` the host fp64 block ``{t, w0, A, f0, alpha, D}`` (``bound.stage_scalars(t)``),
+
+        y[rows[cells[p]][ijk]] += g_p(t) Lx[i] Ly[j] Lz[k]
+
+    ``y`` is the stage's right-hand side.  The adds are float atomics (points may share dofs; next to a halo the launch runs while
+    the interior cells add into the same y).  No points is a no-op."""
+    bp = bound
+    dt = y.dtype if isinstance(y, torch.Tensor) else None
+    _req(y, dt, "y")
+    if bp.dtype != dt:
+        raise TypeError(f"the point sources were bound for {bp.dtype}, y is {dt}")
+    _req(bp.weights, dt, "weights")
+    _req(bp.cells, torch.int32, "cells")
+    _req(bp.rows, torch.int32, "rows")
+    for name, t in (("amplitude", bp.amplitude), ("phase", bp.phase), ("delay", bp.delay)):
+        _req(t, torch.float64, name)
+    m, n = bp.cells.numel(), bp.P + 1
+    if bp.weights.numel() != m * 3 * n or any(t.numel() != m for t in (bp.amplitude, bp.phase, bp.delay)):
+        raise ValueError("point_source_terms: weights [m, 3, P + 1] and one amplitude, phase and delay per point")
+    if bp.rows.dim() != 2 or bp.rows.shape[1] != n**3:
+        raise ValueError(f"point_source_terms: rows must be [k, {n**3}] dofmap rows")
+    if y.numel() < bp.ndofs:
+        raise ValueError(f"point_source_terms: y has {y.numel()} entries, the dofmap rows were checked against {bp.ndofs}")
+    if any(t.device != y.device for t in (bp.weights, bp.cells, bp.rows, bp.amplitude, bp.phase, bp.delay)):
+        raise ValueError("point_source_terms: every operand must be on y's device")
+    if m == 0:
+        return
+    st = np.ascontiguousarray(np.asarray(stage, dtype=np.float64).reshape(-1))
+    if st.size < 6:
+        raise ValueError("stage must hold {t, w0, A, f0, alpha, D}")
+    fn = getattr(_lib.load(), f"fus_point_source_{_lib.suffix(dt)}")
+    _lib.check(fn(y.data_ptr(), bp.cells.data_ptr(), int(m), bp.rows.data_ptr(), int(bp.rows.shape[0]), bp.weights.data_ptr(), int(bp.P),
+                  bp.amplitude.data_ptr(), bp.phase.data_ptr(), bp.delay.data_ptr(), st.ctypes.data, _lib.stream_ptr()),
+               "fus_point_source")
+
+
+def element_receive(u, dof, wgt, offsets, rec=None, slot=0, hre=None, him=None, coef=None):
+    """The surface integrals of ``u`` over the elements of a receiving array in one launch (csrc/element_receive.hpp,
+    ``fus_element_receive_*``): ``S_e = sum wgt[k] u[dof[k]]`` over ``k in [offsets[e], offsets[e + 1])``, written to row ``slot`` of
+    ``rec`` [capacity, E] and accumulated into ``hre`` / ``him`` [H, E] with this step's factors ``coef`` [2H] (each optional).
+    ``receivers.ElementReceivers`` builds the lists.  Summed in double in a fixed order, no atomics; no elements is a no-op."""
+    dt = u.dtype if isinstance(u, torch.Tensor) else None
+    _req(u, dt, "u")
+    _req(wgt, dt, "wgt")
+    _req(dof, torch.int32, "dof")
+    _req(offsets, torch.int64, "offsets")
+    E = offsets.numel() - 1
+    if E < 0 or dof.numel() != wgt.numel():
+        raise ValueError("element_receive: offsets [E + 1], one weight per dof entry")
+    capacity = 0
+    if rec is not None:
+        _req(rec, dt, "rec")
+        if rec.dim() != 2 or rec.shape[1] != E or not 0 <= int(slot) < rec.shape[0]:
+            raise ValueError(f"element_receive: rec must be [capacity, {E}] with slot in [0, capacity)")
+        capacity = rec.shape[0]
+    H = 0
+    if hre is not None or him is not None or coef is not None:
+        for name, t in (("hre", hre), ("him", him), ("coef", coef)):
+            _req(t, torch.float64, name)
+        H = coef.numel() // 2
+        if H < 1 or hre.shape != (H, E) or him.shape != (H, E):
+            raise ValueError("element_receive: hre and him [H, E], coef [2H], H >= 1")
+    if any(t is not None and t.device != u.device for t in (dof, wgt, offsets, rec, hre, him, coef)):
+        raise ValueError("element_receive: every operand must be on u's device")
+    if E == 0:
+        return
+    ptr = lambda t: None if t is None else t.data_ptr()  # noqa: E731
+    fn = getattr(_lib.load(), f"fus_element_receive_{_lib.suffix(dt)}")
+    _lib.check(fn(u.data_ptr(), ptr(dof), ptr(wgt), offsets.data_ptr(), int(E), ptr(rec), int(capacity), int(slot), ptr(hre), ptr(him),
+                  ptr(coef), int(H), _lib.stream_ptr()), "fus_element_receive")
+
+
 # ----------------------------------------------------------------- cell operators
 def _to_device(a, dtype):
     """Host array or tensor -> contiguous tensor of ``dtype`` on the current device."""

@@ -12,7 +12,9 @@ physics through hooks:
 
 With ``sponge=`` (an absorbing layer, sponge.py) a stage has one more launch, ``_sponge_terms(u_n, v_n)`` over the layer's owned
 dofs: appended to ``facets()`` in the fused stage, after the facet applies in ``_stage_reference``; a solver calls ``_init_sponge``
-in its constructor and ``_bind_sponge(mass)`` at the end of ``setup_schedule``, when its lumped mass is complete.
+in its constructor and ``_bind_sponge(mass)`` at the end of ``setup_schedule``, when its lumped mass is complete.  With
+``point_source=`` (monopoles inside the volume, sources.PointSources) one more again, ``_point_terms(t)`` at the stage's source time, in
+the same two places; a solver calls ``_init_point_source`` in its constructor.
 
 ``rk4_schedule`` and ``rk4_graph`` record through one hook, ``_recording`` (the steps and their factors: ``recording.py``);
 ``run_schedule`` drives one rank's schedule generator to its value (``rk4``, ``bioheat.py``, ``field_monitor.py``), ``run_lockstep``
@@ -229,6 +231,19 @@ class SpectralSolver3D(MeshSolver3D):
             raise _lib.FusGpuError("sponge layer: the set-up exchange (setup_schedule) has not run, the layer is not bound yet")
         ops.sponge_terms(self.b, u_n, v_n, self._sponge)
 
+    # -- point sources (sources.PointSources): one more launch per stage, placed where the sponge layer's is -----------------------
+    def _init_point_source(self, point_source, point_claim=None):
+        """``point_source``: a ``sources.PointSources`` or None, bound here to the points this rank injects (needs ``self.f0``).
+        ``point_claim``: this rank's row of ``sources.claim_points`` for ranks driven from one process (they have no gather)."""
+        self.point_source = point_source
+        self._points = None if point_source is None else point_source.bind(
+            self.mesh, self.tdt_np, self.dev, self.f0, comm=self.comm, claim=point_claim)
+
+    def _point_terms(self, t):
+        """b[dofmap[c][ijk]] += g_p(t) Lx[i] Ly[j] Lz[k] over this rank's points; nothing without point sources."""
+        if self._points is not None:
+            ops.point_source_terms(self.b, self._points, self._points.stage_scalars(t))
+
     def init(self):
         """u = v = 0 (cuda/demo_linear_box.py:434-435)."""
         for t in (self.u, self.v, self.ku, self.kv):
@@ -274,6 +289,15 @@ class SpectralSolver3D(MeshSolver3D):
                 facet_launch()
                 self._sponge_terms(u_n, v_n)
 
+        if self._points is not None:  # ... and the point sources' launch: before the reverse scatter of b (a point's cell may hold ghost dofs)
+            if t is None:
+                raise _lib.FusGpuError("point sources take their stage time from the host: a step with a point source cannot be captured")
+            before_points = facets
+
+            def facets():
+                before_points()
+                self._point_terms(t)
+
         yield from self._cell_terms(u_n, v_n, facets)
 
     def _fused_step(self, t, dt):
@@ -301,25 +325,27 @@ class SpectralSolver3D(MeshSolver3D):
         ops.copy(self.v0, self.v)
 
     # -- the time loop -----------------------------------------------------------------------------------------------------
-    def rk4(self, start_time, final_time, dt, max_steps=None, sensors=None, record_from=None, monitor=None):
+    def rk4(self, start_time, final_time, dt, max_steps=None, sensors=None, record_from=None, monitor=None, receivers=None):
         """Advance from ``start_time`` to ``final_time`` (cuda/demo_linear_box.py:487-566).
         Returns ``(t, steps)``.  ``sensors``: a ``sensors.PointSensors`` recorded after every step that ends after
         ``record_from`` (default: every step) while its series has room -- the supported way to observe the field mid-run.
         ``monitor``: a ``field_monitor.FieldMonitor`` that accumulates (u, v) over the owned dofs after the same steps (one
-        launch, no exchange); it may be given together with ``sensors``."""
-        result = run_schedule(self.rk4_schedule(start_time, final_time, dt, max_steps, sensors, record_from, monitor))
+        launch, no exchange); it may be given together with ``sensors``.  ``receivers``: a ``receivers.ElementReceivers`` (the surface
+        integral of the field over each element of an array, one launch) recorded after the same steps as the sensors."""
+        result = run_schedule(self.rk4_schedule(start_time, final_time, dt, max_steps, sensors, record_from, monitor, receivers))
         # N > 1: every device-side wait of the exchange is bounded, so a late or dead neighbour cannot hang this
         # rank -- it must not hand back a field computed from stale ghosts either (the reference would block in
         # MPI Waitall, cuda/scatterer.py:175): raise.  One synchronisation per rk4() call.
         self.check_halo_health(f"{type(self).__name__}.rk4")
         return result
 
-    def _recording(self, sensors, monitor, start_time, final_time, dt, max_steps, record_from):
-        """Plan both recorders for this ``rk4`` call (``expect_steps``) and return ``record(t)``: the generator that records what is
+    def _recording(self, sensors, monitor, start_time, final_time, dt, max_steps, record_from, receivers=None):
+        """Plan the recorders for this ``rk4`` call (``expect_steps``) and return ``record(t)``: the generator that records what is
         due after a step ending at ``t``.  On a partitioned mesh the ghost entries of the field are not current after a step: the
-        sensors' forward exchange is posted first, with a ``yield`` after posting (the solvers' schedules post their stage
-        exchanges the same way, so in-process lockstep drivers keep working); the monitor reads owned dofs only."""
-        for recorder in (sensors, monitor):
+        forward exchange the sensors and the receivers read after is posted first -- once, if either is due -- with a ``yield`` after
+        posting (the solvers' schedules post their stage exchanges the same way, so in-process lockstep drivers keep working); the
+        monitor reads owned dofs only."""
+        for recorder in (sensors, monitor, receivers):
             if recorder is not None:
                 recorder.expect_steps(start_time, final_time, dt, max_steps, record_from)
         rf = -np.inf if record_from is None else float(record_from)
@@ -328,18 +354,20 @@ class SpectralSolver3D(MeshSolver3D):
             if not t > rf:
                 return
             u, v = (self.u0, self.v0) if self.fused else (self.u, self.v)
-            if sensors is not None and not sensors.full:
+            due = [r for r in (sensors, receivers) if r is not None and not r.full]
+            if due:
                 if self.halo is not None:
                     wk = self.halo.fwd.begin(u)
                     yield "forward"
                     self.halo.fwd.end(u, wk)
-                sensors.record(u, t)
+                for r in due:
+                    r.record(u, t)
             if monitor is not None:
                 monitor.record(u, v, t)
 
         return record
 
-    def rk4_schedule(self, start_time, final_time, dt, max_steps=None, sensors=None, record_from=None, monitor=None):
+    def rk4_schedule(self, start_time, final_time, dt, max_steps=None, sensors=None, record_from=None, monitor=None, receivers=None):
         """``rk4`` as a generator that yields whenever this rank has posted halo exchanges (see
         ``HaloApply.schedule``); its return value is ``(t, steps)``.  A driver that advances several ranks' generators
         itself calls ``check_halo_health()`` when they are exhausted (``rk4`` does).  ``u`` / ``v`` are valid only once
@@ -347,7 +375,7 @@ class SpectralSolver3D(MeshSolver3D):
         mid-run through ``sensors`` (see ``rk4``; on a partitioned mesh a recording step posts a forward exchange of the
         field first, with a yield) or, over every owned dof, through ``monitor`` (no exchange, no yield)."""
         t, step = float(start_time), 0
-        record = self._recording(sensors, monitor, t, final_time, dt, max_steps, record_from)
+        record = self._recording(sensors, monitor, t, final_time, dt, max_steps, record_from, receivers)
         if self.fused:
             self._fused_enter()
         for t0, h in rk4_steps(t, final_time, dt, max_steps):
@@ -398,16 +426,20 @@ class SpectralSolver3D(MeshSolver3D):
             self._graph_plans[dt] = held
         return g
 
-    def rk4_graph(self, start_time, final_time, dt, max_steps=None, sensors=None, record_from=None, monitor=None):
+    def rk4_graph(self, start_time, final_time, dt, max_steps=None, sensors=None, record_from=None, monitor=None, receivers=None):
         """``rk4`` with the full-size steps replayed from ONE captured hipGraph.  Same kernels in the same
         order on the same data as ``rk4``.  One rank, fused path; a last shorter step runs through ``rk4``.
-        ``sensors`` / ``monitor`` / ``record_from`` as in ``rk4``: their launches follow a replay on the same stream, outside
-        the captured graph.  Returns ``(t, steps)``."""
+        ``sensors`` / ``monitor`` / ``receivers`` / ``record_from`` as in ``rk4``: their launches follow a replay on the same stream,
+        outside the captured graph.  A solver with point sources cannot be replayed (their stage time is a launch argument; a device
+        stage block for them does not exist yet): ``FusGpuError``.  Returns ``(t, steps)``."""
         if not self.fused or self.halo is not None:
             raise _lib.FusGpuError("rk4_graph: single-rank fused path only")
+        if self._points is not None:
+            raise _lib.FusGpuError("rk4_graph: a solver with point_source= cannot be replayed from a captured graph (the point sources' "
+                                   "stage time is a host argument of their launch): use rk4")
         t, tf = float(start_time), float(final_time)
         rows, ends = [], []
-        record = self._recording(sensors, monitor, t, tf, dt, max_steps, record_from)
+        record = self._recording(sensors, monitor, t, tf, dt, max_steps, record_from, receivers)
         src = self.source
         for t0, h in rk4_steps(t, tf, dt, max_steps):
             if h != dt:
@@ -436,7 +468,7 @@ class SpectralSolver3D(MeshSolver3D):
             self._fused_exit()
         steps = len(rows)
         if t < tf and (max_steps is None or steps < max_steps):
-            t, more = self.rk4(t, tf, dt, None if max_steps is None else max_steps - steps, sensors, record_from, monitor)
+            t, more = self.rk4(t, tf, dt, None if max_steps is None else max_steps - steps, sensors, record_from, monitor, receivers)
             steps += more
         return t, steps
 

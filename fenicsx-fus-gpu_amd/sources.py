@@ -43,6 +43,21 @@ def _window(s, f0, alpha=ALPHA):
     return w, dw
 
 
+def _waveform(t, frequency, scale, amplitude, phase, delay, duration, alpha=ALPHA):
+    """Host ``(g(t), dg/dt)`` of the waveform both source kinds share, one value per element / point:
+    ``g = a A Env(s) cos(w0 s + phi)``, ``s = t - tau`` (the module docstring)."""
+    f0 = float(frequency)
+    w0 = 2.0 * np.pi * f0
+    s = float(t) - delay
+    env, denv = _window(s, f0, alpha)
+    if duration is not None:
+        w2, dw2 = _window(duration - s, f0, alpha)
+        env, denv = env * w2, denv * w2 - env * dw2
+    a = amplitude * float(scale)
+    cs, sn = np.cos(w0 * s + phase), np.sin(w0 * s + phase)
+    return env * a * cs, denv * a * cs - env * a * w0 * sn
+
+
 def facet_centroids(mesh, facets):
     """``[m, 3]`` centroids of the boundary facets ``facets`` (``(cell, local facet)`` rows): the mean of the facet's four
     vertices, from ``x_dofs`` / ``x_g`` (any mesh the solvers take: ``BoxMesh``, ``dolfinx_adaptor.ArrayMesh``)."""
@@ -114,16 +129,7 @@ class SourceArray:
 
     def values(self, t, frequency, scale, alpha=ALPHA):
         """Host ``(g_e(t), dg_e/dt)``, ``[E]`` each, for carrier ``frequency`` and source constant ``scale`` (``A``)."""
-        f0 = float(frequency)
-        w0 = 2.0 * np.pi * f0
-        s = float(t) - self.delay
-        env, denv = _window(s, f0, alpha)
-        if self.duration is not None:
-            w2, dw2 = _window(self.duration - s, f0, alpha)
-            env, denv = env * w2, denv * w2 - env * dw2
-        a = self.amplitude * float(scale)
-        cs, sn = np.cos(w0 * s + self.phase), np.sin(w0 * s + self.phase)
-        return env * a * cs, denv * a * cs - env * a * w0 * sn
+        return _waveform(t, frequency, scale, self.amplitude, self.phase, self.delay, self.duration, alpha)
 
     def stage_scalars(self, t, frequency, scale, alpha=ALPHA):
         """The fp64 stage block ``{t, w0, A, f0, alpha, D}`` of the kernel (``D = 0``: continuous wave)."""
@@ -195,6 +201,131 @@ class BoundSourceArray:
 
     def stage_scalars(self, t):
         return self.array.stage_scalars(t, self.frequency, self.scale)
+
+
+# -- point sources -----------------------------------------------------------------------------
+class PointSources:
+    """Monopole sources inside the volume, ``q_p(t) delta(x - x_p)`` (csrc/point_source.hpp, ``fus_point_source_*``): the term a
+    stage's right-hand side gets is ``b[dofmap[c][ijk]] += g_p(t) Lx[i] Ly[j] Lz[k]``, the transpose of a point sensor, with the
+    array's waveform per point, ``g_p(t) = a_p Env(s) cos(w0 s + phi_p)``, ``s = t - tau_p``.  The amplitude IS the monopole strength
+    (the stage block's ``A`` is 1).  A virtual source at the target of a time-reversal run (receivers.py):
+
+        solver = LinearSpectral3D(mesh, source_amplitude=0.0, point_source=PointSources(focus))
+
+    ``points``: ``[m, 3]`` (or one point); ``amplitude`` / ``phase`` (radians) / ``delay`` (seconds): scalars or one value per point;
+    ``duration``: burst length in seconds or ``None`` (continuous wave), as ``SourceArray``."""
+
+    def __init__(self, points, amplitude=1.0, phase=0.0, delay=0.0, duration=None):
+        pts = np.asarray(points, dtype=np.float64)
+        if pts.ndim == 1 and pts.size == 3:
+            pts = pts[None, :]
+        if pts.ndim != 2 or pts.shape[1] != 3:
+            raise ValueError(f"points: [m, 3] points, got shape {pts.shape}")
+        if not np.all(np.isfinite(pts)):
+            raise ValueError("points: coordinates must be finite")
+        self.points = np.ascontiguousarray(pts)
+        m = self.npoints = int(pts.shape[0])
+        self.amplitude = _per_element(amplitude, m, "amplitude")
+        self.phase = _per_element(phase, m, "phase")
+        self.delay = _per_element(delay, m, "delay")
+        if duration is not None:
+            duration = float(duration)
+            if not (np.isfinite(duration) and duration > 0.0):
+                raise ValueError(f"duration must be a positive number of seconds or None, got {duration}")
+        self.duration = duration
+
+    check_duration = SourceArray.check_duration
+    stage_scalars = SourceArray.stage_scalars
+
+    def values(self, t, frequency, scale=1.0, alpha=ALPHA):
+        """Host ``(g_p(t), dg_p/dt)``, ``[m]`` each, as ``SourceArray.values`` (a one-point source equals a one-element array)."""
+        return _waveform(t, frequency, scale, self.amplitude, self.phase, self.delay, self.duration, alpha)
+
+    def setup(self, mesh, locator=None):
+        """This rank's ``sensors.SensorSetup`` of the points: those that lie in one of its cells, sorted by cell."""
+        from .sensors import sensor_setup
+
+        return sensor_setup(mesh, self.points, locator)
+
+    def bind(self, mesh, dtype, device, frequency, comm=None, claim=None, setup=None, locator=None):
+        """Locate the points in this rank's cells (``sensors.sensor_setup``) and upload the tables of those it injects.  Every point
+        is injected by exactly ONE rank, the lowest that holds it (the rule of ``sensors.merge``): ranks in different processes agree
+        through one gather over ``comm`` here; ranks driven from one process are handed ``claim``, this rank's row of
+        ``claim_points`` (all ranks' set-ups).  On one rank a point outside the mesh is a ``ValueError``."""
+        import torch
+
+        from . import _lib
+
+        self.check_duration(frequency)
+        su = setup if setup is not None else self.setup(mesh, locator)
+        size = int(getattr(comm, "size", 1)) if comm is not None else 1
+        if claim is None:
+            if size == 1:
+                if su.point_ids.size != self.npoints:
+                    lost = np.setdiff1d(np.arange(self.npoints), su.point_ids)
+                    raise ValueError(f"point source(s) {lost.tolist()} lie outside the mesh")
+                claim = np.ones(self.npoints, dtype=bool)
+            else:
+                from .scatterer import gather_arrays
+
+                every = gather_arrays(comm, {"ids": su.point_ids}, "PointSources.bind", "claim=claim_points(setups, npoints)[rank]")
+                claim = claim_points([z["ids"] for z in every], self.npoints)[int(comm.rank)]
+        claim = np.asarray(claim, dtype=bool)
+        if claim.shape != (self.npoints,):
+            raise ValueError(f"claim: one flag per point ({self.npoints}), got shape {claim.shape}")
+        keep = claim[su.point_ids]  # device order stays sorted by cell
+        ids = su.point_ids[keep]
+        n = int(mesh.P) + 1
+        if su.rows.size and int(su.rows.max()) >= int(mesh.ndofs):
+            raise ValueError("dofmap row outside the local vector")
+        ft = np.dtype(dtype)
+        td = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(device)  # noqa: E731
+        return BoundPointSources(self, _lib.torch_dtype(dtype), int(mesh.P), int(mesh.ndofs), ids, td(su.cell_index[keep].astype(np.int32)),
+                                 td(su.rows.astype(np.int32).reshape(-1, n**3)), td(su.weights[keep].astype(ft).reshape(-1, 3, n)),
+                                 td(self.amplitude[ids]), td(self.phase[ids]), td(self.delay[ids]), float(frequency))
+
+
+def claim_points(per_rank, npoints):
+    """Which rank injects which point: ``per_rank`` holds, in rank order, each rank's ``SensorSetup`` (or its ``point_ids``); returns one
+    bool row ``[npoints]`` per rank, the LOWEST rank that holds a point claiming it (``sensors.merge``'s rule).  A point that no rank
+    holds is a ``ValueError``: it would be dropped silently otherwise."""
+    owner = np.full(int(npoints), -1, dtype=np.int64)
+    for r in reversed(range(len(per_rank))):  # the lowest rank writes last
+        ids = np.asarray(getattr(per_rank[r], "point_ids", per_rank[r]), dtype=np.int64).reshape(-1)
+        owner[ids] = r
+    if np.any(owner < 0):
+        raise ValueError(f"point source(s) {np.nonzero(owner < 0)[0].tolist()} lie outside the mesh")
+    return [owner == r for r in range(len(per_rank))]
+
+
+@dataclass
+class BoundPointSources:
+    """``PointSources`` on the device for one rank: what ``operators.point_source_terms`` launches with."""
+
+    sources: PointSources
+    dtype: object  # torch dtype of the field
+    P: int
+    ndofs: int  # length of the local vector the rows index
+    point_ids: np.ndarray  # int64 [m]  the points this rank injects (indices into the caller's list, device order)
+    cells: object  # int32 [m]  row of ``rows`` per point
+    rows: object  # int32 [k, n^3]  dofmap rows of the cells that hold a located point
+    weights: object  # T [m, 3, n]
+    amplitude: object  # float64 [m]
+    phase: object
+    delay: object
+    frequency: float
+
+    @property
+    def npoints(self):
+        return int(self.point_ids.size)
+
+    def values(self, t):
+        g, dg = self.sources.values(t, self.frequency)
+        return g[self.point_ids], dg[self.point_ids]
+
+    def stage_scalars(self, t):
+        """The fp64 stage block ``{t, w0, A = 1, f0, alpha, D}`` of the kernel."""
+        return self.sources.stage_scalars(t, self.frequency, 1.0)
 
 
 # -- geometry helpers --------------------------------------------------------------------------

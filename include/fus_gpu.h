@@ -55,7 +55,7 @@ extern "C" {
  *      Added since without a bump (new symbols only): fus_mass_gather_plan_bytes / _build / _info, fus_mass_apply_gather_*,
  *      fus_mass_gather_plan_build_rows, fus_mass_gather_static_bytes / _build_* , fus_mass_apply_gather_static_*,
  *      fus_probe_eval_*, fus_facet_source_array_* / fus_facet_source_array_dev_*, fus_field_accumulate_*,
- *      fus_bioheat_stage_*.  Tightened without a bump: a build at a workspace address replaces what any family had registered
+ *      fus_bioheat_stage_*, fus_sponge_terms_*; in fus_gpu_array.h: fus_point_source_*, fus_element_receive_*.  Tightened without a bump: a build at a workspace address replaces what any family had registered
  *      there; fus_rk4_stage_nl_* rejects new_step outside 0..3.
  * There are deliberately NO fus_cpu_* twins of the entry points (SURVEY.md 8b proposed them): a CPU path inside the
  * product would be a silent fallback; the CPU restatement of the reference is test infrastructure and lives outside the product tree.

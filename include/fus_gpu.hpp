@@ -28,6 +28,7 @@
 #include <utility>
 
 #include "fus_gpu.h"
+#include "fus_gpu_array.h"
 
 namespace fus_gpu {
 
@@ -436,6 +437,57 @@ class FacetSourceArray {
   const T *cB_, *detJB_;
   const int32_t* dmB_;
   int64_t nB_;
+};
+
+// Point sources (fus_point_source_*): monopoles inside the volume, the transpose of PointProbe over the same tables (``cells`` [npts],
+// the dofmap rows they index, ``weights`` [npts][3][P + 1]) with a per-point ``amplitude`` / ``phase`` / ``delay`` (fp64).  All device
+// arrays, caller-owned.
+template <typename T, int P>
+class PointSource {
+ public:
+  PointSource(const int32_t* cells, int64_t npts, const int32_t* dofmap, int64_t ncells, const T* weights, const double* amplitude,
+              const double* phase, const double* delay)
+      : cells_(cells), npts_(npts), dofmap_(dofmap), ncells_(ncells), weights_(weights), a_(amplitude), ph_(phase), tau_(delay) {
+    check_abi();
+  }
+  // y += the points' terms at the stage block {t, w0, A, f0, alpha, D} (host memory): after the facet terms, before the reverse scatter of y
+  void operator()(T* y, const double* stage, void* stream = nullptr) const {
+    check(detail::typed<T>(fus_point_source_f64, fus_point_source_f32)(y, cells_, npts_, dofmap_, ncells_, weights_, P, a_, ph_, tau_, stage,
+                                                                       stream),
+          "fus_point_source");
+  }
+
+ private:
+  const int32_t* cells_;
+  int64_t npts_;
+  const int32_t* dofmap_;
+  int64_t ncells_;
+  const T* weights_;
+  const double *a_, *ph_, *tau_;
+};
+
+// Element receivers (fus_element_receive_*): S_e = sum wgt[k] u[dof[k]] over the entries [offsets[e], offsets[e + 1]) of each of
+// ``nelem`` elements (the facet-dof entries sorted by element, ``wgt`` their scaled facet detJ).  Not normalised: the area is sum wgt.
+template <typename T>
+class ElementReceive {
+ public:
+  ElementReceive(const int32_t* dof, const T* wgt, const int64_t* offsets, int64_t nelem) : dof_(dof), wgt_(wgt), offsets_(offsets), nelem_(nelem) {
+    check_abi();
+  }
+  // row ``slot`` of rec[capacity][nelem] and H harmonic accumulators hre / him [H][nelem] with this step's factors coef [2H] (null = off)
+  void operator()(const T* u, T* rec, int64_t capacity, int slot, double* hre = nullptr, double* him = nullptr, const double* coef = nullptr,
+                  int H = 0, void* stream = nullptr) const {
+    check(detail::typed<T>(fus_element_receive_f64, fus_element_receive_f32)(u, dof_, wgt_, offsets_, nelem_, rec, capacity, slot, hre, him, coef,
+                                                                             H, stream),
+          "fus_element_receive");
+  }
+  int64_t nelem() const { return nelem_; }
+
+ private:
+  const int32_t* dof_;
+  const T* wgt_;
+  const int64_t* offsets_;
+  int64_t nelem_;
 };
 
 }  // namespace fus_gpu

@@ -70,7 +70,7 @@ def cached_remarks():
     """Remarks of the current sources, cached under csrc/_asm keyed on source mtimes."""
     cache = os.path.join(CSRC, "_asm", "resource_usage_device.txt")
     srcs = [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith((".hip", ".hpp"))]
-    srcs.append(os.path.join(ROOT, "include", "fus_gpu.h"))
+    srcs += [os.path.join(ROOT, "include", h) for h in ("fus_gpu.h", "fus_gpu_array.h")]
     newest = max(os.path.getmtime(p) for p in srcs)
     if os.path.exists(cache) and os.path.getmtime(cache) >= newest:
         return open(cache).read()
@@ -82,7 +82,7 @@ def cached_remarks():
 
 
 def main():
-    pats = [re.compile(p) for p in sys.argv[1:]] or [re.compile("stiffness_plan|westervelt_cell|sponge_terms")]
+    pats = [re.compile(p) for p in sys.argv[1:]] or [re.compile("stiffness_plan|westervelt_cell|sponge_terms|point_source|element_receive")]
     table = parse(cached_remarks())
     for name, d in table.items():
         if any(p.search(name) for p in pats):
