@@ -21,6 +21,9 @@ HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "fus_gpu.h")
 # headers that extend the ABI with further entry points of the same library (each includes fus_gpu.h): additions since the set of
 # functions of fus_gpu.h was pinned are declared there, and bound from there in the same way
 EXTENSION_HEADER_PATHS = (os.path.join(os.path.dirname(_HERE), "include", "fus_gpu_array.h"),)
+# ... and the headers added since THAT set was pinned in its turn (tests/test_point_sources.py pins EXTENSIONS to fus_gpu_array.h's four
+# functions): every later extension header goes here, its functions into ADDITIONS
+ADDITION_HEADER_PATHS = (os.path.join(os.path.dirname(_HERE), "include", "fus_gpu_relaxation.h"),)
 
 
 class FusGpuError(RuntimeError):
@@ -83,6 +86,9 @@ SIGNATURES = {name: argtypes for name, (_, argtypes) in DECLARATIONS.items() if 
 EXTENSIONS = {name: decl for path in EXTENSION_HEADER_PATHS for name, decl in _read_header(path)[0].items()}
 if set(EXTENSIONS) & set(DECLARATIONS):
     raise FusGpuError(f"declared both in include/fus_gpu.h and in an extension header: {sorted(set(EXTENSIONS) & set(DECLARATIONS))}")
+ADDITIONS = {name: decl for path in ADDITION_HEADER_PATHS for name, decl in _read_header(path)[0].items()}
+if set(ADDITIONS) & (set(EXTENSIONS) | set(DECLARATIONS)):
+    raise FusGpuError(f"declared in two headers of the C ABI: {sorted(set(ADDITIONS) & (set(EXTENSIONS) | set(DECLARATIONS)))}")
 
 ABI_VERSION = _DEFINES["FUS_ABI_VERSION"]
 ERR_COMM = _DEFINES["FUS_ERR_COMM"]
@@ -106,7 +112,7 @@ _lib = None
 def bind(cdll):
     """Set ``argtypes`` and ``restype`` of every declared function (include/fus_gpu.h and its extension headers) on a loaded library;
     AttributeError if it lacks one."""
-    for name, (restype, argtypes) in {**DECLARATIONS, **EXTENSIONS}.items():
+    for name, (restype, argtypes) in {**DECLARATIONS, **EXTENSIONS, **ADDITIONS}.items():
         fn = getattr(cdll, name)
         fn.argtypes, fn.restype = argtypes, restype
     return cdll

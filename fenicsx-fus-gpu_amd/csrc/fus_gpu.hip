@@ -4,6 +4,7 @@
 // Build: see Makefile (hipcc --offload-arch=gfx950).
 #include "../../include/fus_gpu.h"
 #include "../../include/fus_gpu_array.h"
+#include "../../include/fus_gpu_relaxation.h"
 
 #include <hip/hip_runtime.h>
 
@@ -21,6 +22,7 @@
 #include "plan_build.hpp"
 #include "point_source.hpp"
 #include "probe.hpp"
+#include "relaxation.hpp"
 #include "rk4.hpp"
 #include "source_array.hpp"
 #include "sponge.hpp"
@@ -360,6 +362,30 @@ int bioheat_stage(T bw, T aw, int kind, T gate, T t_a, double dt, const T* minv,
     return FUS_ERR_INVALID_ARGUMENT;
   return hip_rc(fus::launch_bioheat_stage<T>(bw, aw, kind, gate, t_a, dt, minv, pr, s, b, T0, Tn, acc, cem43, tmax, init != 0, nlocal, ntotal,
                                              static_cast<hipStream_t>(stream)));
+}
+
+// relaxation stage (csrc/relaxation.hpp): every check before any device work; nlocal == 0 is a no-op
+template <typename T>
+int relax_stage(T bw, T aw, T aw_u, int kind, int nr, const double* tau, const double* kappa_scalar, const T* kappa, T* xi0, T* xin, T* acc,
+                int64_t stride, const T* u_base, const T* vn, T* ur, int64_t nlocal, void* stream) {
+  if (nlocal < 0 || stride < nlocal) return FUS_ERR_INVALID_ARGUMENT;
+  if (kind < 0 || kind > 2 || nr < 1 || nr > FUS_RELAX_MAX_MECHANISMS) return FUS_ERR_INVALID_ARGUMENT;
+  if (nlocal == 0) return FUS_OK;
+  if (!tau || (!kappa && !kappa_scalar) || !xi0 || !xin || !acc || !u_base || !vn || !ur) return FUS_ERR_INVALID_ARGUMENT;
+  for (int nu = 0; nu < nr; ++nu)
+    if (!(tau[nu] > 0.0)) return FUS_ERR_INVALID_ARGUMENT;
+  if (misaligned(kappa, sizeof(T)) || misaligned(xi0, sizeof(T)) || misaligned(xin, sizeof(T)) || misaligned(acc, sizeof(T)) ||
+      misaligned(u_base, sizeof(T)) || misaligned(vn, sizeof(T)) || misaligned(ur, sizeof(T)))
+    return FUS_ERR_INVALID_ARGUMENT;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  hipError_t e = hipErrorInvalidValue;
+  switch (nr) {
+    case 1: e = fus::launch_relax_stage<T, 1>(bw, aw, aw_u, kind, tau, kappa_scalar, kappa, xi0, xin, acc, stride, u_base, vn, ur, nlocal, s); break;
+    case 2: e = fus::launch_relax_stage<T, 2>(bw, aw, aw_u, kind, tau, kappa_scalar, kappa, xi0, xin, acc, stride, u_base, vn, ur, nlocal, s); break;
+    case 3: e = fus::launch_relax_stage<T, 3>(bw, aw, aw_u, kind, tau, kappa_scalar, kappa, xi0, xin, acc, stride, u_base, vn, ur, nlocal, s); break;
+    default: e = fus::launch_relax_stage<T, 4>(bw, aw, aw_u, kind, tau, kappa_scalar, kappa, xi0, xin, acc, stride, u_base, vn, ur, nlocal, s); break;
+  }
+  return hip_rc(e);
 }
 
 }  // namespace
@@ -703,6 +729,10 @@ int fus_plan_mark_exclusive(void* workspace, int N, int entities_per_batch, int6
   int fus_bioheat_stage_##SUF(T bw, T aw, int kind, T gate, T t_a, double dt, const T* minv, const T* pr, const T* src, T* b, T* T0,       \
                               T* Tn, T* acc, double* cem43, T* tmax, int init, int64_t nlocal, int64_t ntotal, void* s) {                  \
     return bioheat_stage<T>(bw, aw, kind, gate, t_a, dt, minv, pr, src, b, T0, Tn, acc, cem43, tmax, init, nlocal, ntotal, s);             \
+  }                                                                                                                                        \
+  int fus_relax_stage_##SUF(T bw, T aw, T aw_u, int kind, int nr, const double* tau, const double* kappa_scalar, const T* kappa, T* xi0,    \
+                            T* xin, T* acc, int64_t stride, const T* u_base, const T* vn, T* ur, int64_t nlocal, void* s) {                \
+    return relax_stage<T>(bw, aw, aw_u, kind, nr, tau, kappa_scalar, kappa, xi0, xin, acc, stride, u_base, vn, ur, nlocal, s);             \
   }                                                                                                                                        \
   int fus_probe_eval_##SUF(const T* u, const int32_t* cells, int64_t npts, const int32_t* dofmap, int64_t ncells, const T* weights, int P, \
                            T* rec, int64_t capacity, int slot, double* pmax, double* pmin, double* hre, double* him, const double* coef,   \

@@ -47,6 +47,10 @@ def main():
                     help="absorbing sponge layer of CELLS cells inside the four lateral faces (y and z), which the reference leaves rigid "
                          "(sponge.SpongeLayer: one sparse damping launch per stage); default 0: off")
     ap.add_argument("--length", type=float, default=0.12, help="edge of the box in m (default: the reference's 0.12)")
+    ap.add_argument("--power-law", type=float, nargs=2, default=None, metavar=("ALPHA0", "Y"),
+                    help="tissue absorption ALPHA0 f^Y (dB/cm/MHz^Y, Y in 1 .. 1.5) through two relaxation mechanisms fitted between half and "
+                         "five times the source frequency (relaxation.fit_power_law, without a thermoviscous term: the linear model has "
+                         "none); prints the fit's largest relative error; default: no volume loss")
     ap.add_argument("--time-reversal", type=float, nargs=3, default=None, metavar=("FX", "FY", "FZ"),
                     help="time-reversal focusing on the point (FX, FY, FZ) through an aberrating slab (twice the speed of sound, one "
                          "wavelength thick, in front of the y > L/2 half of the aperture): a receive run with a virtual point source at the "
@@ -111,10 +115,25 @@ def main():
             raise SystemExit(f"--sponge: 1 .. {num_element // 2} cells")
         # the GLOBAL box, so every rank evaluates the same profile on its own dofs
         sponge = sp.SpongeLayer(sp.box_profile((0.0, 0.0, 0.0), mesh.length, a.sponge * domain_length / num_element, sp.LATERAL, speed_of_sound))
+    relaxation = None
+    if a.power_law:
+        rx = fusgpu_loader.submodule("relaxation")
+        fit = rx.fit_power_law(a.power_law[0], a.power_law[1], 0.5 * source_frequency, 5.0 * source_frequency, n=2,
+                               speed_of_sound=speed_of_sound, with_thermoviscous=False)
+        relaxation = rx.RelaxationAbsorption(fit.tau, fit.kappa)
+        try:
+            relaxation.check_time_step(dt)  # a coarse mesh (few --cells) steps past the fastest mechanism
+        except ValueError as e:
+            raise SystemExit(f"--power-law: {e}") from None
+        if rank == 0:
+            print(f"Power law {a.power_law[0]:g} dB/cm/MHz^{a.power_law[1]:g}: tau = {fit.tau}, kappa = {fit.kappa}, largest relative error of "
+                  f"the fit {fit.max_rel_error:.4f}; alpha_r(f0) = {relaxation.alpha(source_frequency, speed_of_sound):.4g} Np/m", flush=True)
     if a.time_reversal:
+        if relaxation is not None:
+            raise SystemExit("--power-law does not compose with --time-reversal")
         return time_reversal_run(a, mesh, sponge, float_type, speed_of_sound, density, source_frequency, source_amplitude)
     solver = ls.LinearSpectral3D(mesh, float_type, speed_of_sound, density, source_frequency, source_amplitude,
-                                 comm=comm, fused=not a.reference_sequence, source=source, sponge=sponge)
+                                 comm=comm, fused=not a.reference_sequence, source=source, sponge=sponge, relaxation=relaxation)
     solver.init()
     if sponge is not None:
         n_layer = solver._sponge[0].numel()

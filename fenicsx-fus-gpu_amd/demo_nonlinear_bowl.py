@@ -68,6 +68,11 @@ def main():
     ap.add_argument("--sponge", type=int, default=0, metavar="CELLS",
                     help="absorbing sponge layer of CELLS cells inside the four lateral faces (y and z), which the reference leaves rigid "
                          "(sponge.SpongeLayer: one sparse damping launch per stage); default 0: off")
+    ap.add_argument("--power-law", type=float, nargs=2, default=None, metavar=("ALPHA0", "Y"),
+                    help="tissue absorption ALPHA0 f^Y (dB/cm/MHz^Y, Y in 1 .. 1.5) in place of the f^2 law of the reference's "
+                         "attenuation coefficient: two relaxation mechanisms and the thermoviscous diffusivity fitted together between half "
+                         "and five times the source frequency (relaxation.fit_power_law); prints the fit's largest relative error; the "
+                         "heat deposition of --field-stats / --thermal is then relaxation.heat_deposition")
     a = ap.parse_args()
     if a.thermal is not None and (len(a.thermal) > 2 or min(a.thermal) < 0.0):
         ap.error("--thermal SECONDS_ON [SECONDS_OFF], both >= 0")
@@ -149,9 +154,26 @@ def main():
             raise SystemExit(f"--sponge: 1 .. {num_element // 2} cells")
         # the GLOBAL box, so every rank evaluates the same profile on its own dofs
         sponge = sp.SpongeLayer(sp.box_profile((0.0, 0.0, 0.0), mesh.length, a.sponge * L / num_element, sp.LATERAL, speed_of_sound))
+    relaxation = None
+    if a.power_law:
+        rx = fusgpu_loader.submodule("relaxation")
+        fit = rx.fit_power_law(a.power_law[0], a.power_law[1], 0.5 * source_frequency, 5.0 * source_frequency, n=2,
+                               speed_of_sound=speed_of_sound, with_thermoviscous=True)
+        relaxation = rx.RelaxationAbsorption(fit.tau, fit.kappa)
+        try:
+            relaxation.check_time_step(dt)  # a coarse mesh steps past the fastest mechanism
+        except ValueError as e:
+            raise SystemExit(f"--power-law: {e}") from None
+        # the fitted diffusivity as the solver's attenuation coefficient at the source frequency (compute_diffusivity_of_sound, inverted)
+        w0 = 2.0 * np.pi * source_frequency
+        attenuation_coefficient_dB = fit.delta * w0 * w0 / (2.0 * speed_of_sound**3) * 20.0 / np.log(10.0)
+        if rank == 0:
+            print(f"Power law {a.power_law[0]:g} dB/cm/MHz^{a.power_law[1]:g}: tau = {fit.tau}, kappa = {fit.kappa}, delta = {fit.delta:.4g} "
+                  f"(thermoviscous part {attenuation_coefficient_dB:.4g} dB/m at f0), largest relative error of the fit {fit.max_rel_error:.4f}",
+                  flush=True)
     solver = nls.WesterveltSpectral3D(mesh, float_type, speed_of_sound, density, source_frequency, source_amplitude,
                                       nonlinear_coefficient, attenuation_coefficient_dB, comm=comm, fused=not a.reference_sequence, source=source,
-                                      sponge=sponge,
+                                      sponge=sponge, relaxation=relaxation,
                                       in_kernel_geometry=True if (a.in_kernel_geometry or a.geometry == "kernel") else ("auto" if a.geometry == "auto" else False))
     solver.init()
     if sponge is not None:
@@ -277,7 +299,7 @@ def run_with_monitor(a, solver, mesh, comm, rank, world, float_type, t0, tf, dt,
         foc = fm.focus(h1, solver, 0.5, comm if world > 1 else None)
         host = lambda x: x.cpu().numpy()  # noqa: E731
         out.update(pmax=host(m.peak()[0]), pmin=host(m.peak()[1]), H1=host(h1), H2=host(m.harmonic_amplitude(2)),
-                   u_mean_square=host(m.mean_square("u")), q=host(m.heat_deposition(solver)), focus_max=foc["max"], focus_dof=foc["dof"],
+                   u_mean_square=host(m.mean_square("u")), q=host(_heat_deposition(m, solver)), focus_max=foc["max"], focus_dof=foc["dof"],
                    focus_rank=foc["rank"], focus_position=np.asarray(foc["position"] if foc["position"] is not None else [np.nan] * 3),
                    focus_volume=foc["volume"], focus_level=foc["level"])
     if a.field_stats:
@@ -296,6 +318,15 @@ def run_with_monitor(a, solver, mesh, comm, rank, world, float_type, t0, tf, dt,
         run_thermal(a, solver, m, mesh, comm, rank, world, float_type)
     if world > 1:
         dist.destroy_process_group()
+
+
+def _heat_deposition(monitor, solver):
+    """The absorbed power density of the last period: with --power-law the mechanisms' part beside the thermoviscous one."""
+    if solver.relaxation is None:
+        return monitor.heat_deposition(solver)
+    import fusgpu_loader
+
+    return fusgpu_loader.submodule("relaxation").heat_deposition(monitor, solver)
 
 
 def run_intensity(solver, monitor, comm, rank, world):
@@ -325,7 +356,7 @@ def run_thermal(a, solver, monitor, mesh, comm, rank, world, float_type):
 
     fm, bh = fusgpu_loader.submodule("field_monitor"), fusgpu_loader.submodule("bioheat")
     th = bh.BioheatSpectral3D(mesh, float_type, comm=comm)
-    th.set_heat_source(bh.heat_source_from(monitor, solver, th))
+    th.set_heat_source(bh.heat_source_from(monitor, solver, th) if solver.relaxation is None else _heat_deposition(monitor, solver).to(th.tdt))
     dt = th.stable_time_step()
     t_on, t_off = a.thermal[0], (a.thermal[1] if len(a.thermal) > 1 else 0.0)
     t, steps = th.advance(0.0, t_on, dt)

@@ -55,7 +55,7 @@ class LinearSpectral3D(SpectralSolver3D):
                  source_frequency=0.5e6, source_amplitude=60000.0, comm=None, fused=True,
                  source_time="tn", overlap=True, halo_kernels=None, affine="auto", in_kernel_geometry="auto",
                  halo_plan=None, defer_setup_exchange=False, reference_speed_of_sound=None, keep_G=False, source=None,
-                 sponge=None, point_source=None, point_claim=None):
+                 sponge=None, point_source=None, point_claim=None, relaxation=None):
         """``speed_of_sound`` / ``density``: scalars, or one value per cell (heterogeneous medium: the DG0 material arrays of
         the reference's drivers, in the caller's cell order).  ``reference_speed_of_sound``: the c of the source term
         ``p0 w0 / c cos(w0 t)`` (cuda/demo_linear_box.py:515-530 uses the scalar of its homogeneous medium); default: the
@@ -73,10 +73,14 @@ class LinearSpectral3D(SpectralSolver3D):
         time); it coexists with ``source``, the scalar source and ``sponge``; ``source_amplitude=0.0`` silences the facet source for a
         receive run (the virtual source of a time-reversal run, receivers.py).  ``None`` keeps every launch as it is.
         ``point_claim``: this rank's row of ``sources.claim_points`` when several ranks are driven from one process (handed in like
-        ``halo_plan``); ranks in different processes agree through one gather."""
+        ``halo_plan``); ranks in different processes agree through one gather.  ``relaxation``: a
+        ``relaxation.RelaxationAbsorption`` (power-law absorption: memory variables xi' = kappa v - xi / tau per mechanism, the stiffness
+        apply acts on u_n + sum xi, one streaming launch per stage); ``speed_of_sound`` is then the EQUILIBRIUM (low-frequency) speed,
+        the phase speed rises with frequency (``RelaxationAbsorption.phase_speed``).  ``None`` keeps every launch as it is."""
         c_cells, rho_cells = per_cell(speed_of_sound, mesh, "speed_of_sound"), per_cell(density, mesh, "density")
         bd1, bd2, D, G_d, detJ_d, (dF1_d, dF2_d) = self._init_common(mesh, float_type, comm, fused, source_time)
         self._init_sponge(sponge)
+        self._init_relaxation(relaxation)
         self.c0, self.rho0 = float(c_cells.mean()), float(rho_cells.mean())
         self.rho_cells, self.c_cells = rho_cells, c_cells  # per cell, the mesh's cell order (intensity.py)
         self.f0, self.p0 = float(source_frequency), float(source_amplitude)
@@ -143,6 +147,7 @@ class LinearSpectral3D(SpectralSolver3D):
         ops.fill(1.0, self.minv)
         ops.pointwise_divide(self.minv, self.m, self.minv)  # owned entries are what the fused kernel reads
         self._bind_sponge(self.m)  # m is complete only now
+        yield from self._bind_relaxation()
 
     def source_value(self, t):
         """Window x p0 w0 / c0 x cos(w0 t) (cuda/demo_linear_box.py:515-530)."""
@@ -186,10 +191,11 @@ class LinearSpectral3D(SpectralSolver3D):
             self._sponge_terms(self.u_n, self.v_n)
             self._point_terms(ts)
 
-        yield from self._cell_terms(self.u_n, self.v_n, facets)
+        yield from self._cell_terms(self._stiffness_input(self.u_n), self.v_n, facets)
         ops.pointwise_divide(self.b, self.m, self.kv)
         axpy(B_RUNGE[i] * dt, self.ku, self.u)
         axpy(B_RUNGE[i] * dt, self.kv, self.v)
+        self._relax_reference(i, dt)
 
     # -- fused: one vector kernel per stage (csrc/rk4.hpp) -------------------------------------------
     def _vector_pass(self, bw, aw, new_step):

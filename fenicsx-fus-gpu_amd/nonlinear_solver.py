@@ -33,7 +33,7 @@ class WesterveltSpectral3D(SpectralSolver3D):
                  attenuation_coefficient_dB=0.2, comm=None, source_time="tn", overlap=True, fused=False,
                  in_kernel_geometry="auto", uniform_ratio="auto", halo_plan=None, defer_setup_exchange=False,
                  reference_speed_of_sound=None, reference_density=None, keep_G=False, source=None, sponge=None,
-                 point_source=None, point_claim=None):
+                 point_source=None, point_claim=None, relaxation=None):
         """``speed_of_sound``, ``density``, ``nonlinear_coefficient``, ``attenuation_coefficient_dB``: scalars, or one value per
         cell in the caller's cell order (the DG0 material arrays of cuda/demo_nonlinear_bowl.py:166-178 -- water / skull / ...).
         ``reference_speed_of_sound`` / ``reference_density``: the scalars of the source term and of the default source amplitude
@@ -48,12 +48,18 @@ class WesterveltSpectral3D(SpectralSolver3D):
         effective damping is then 2 sigma m0 / (m0 + w2 u_n), by definition; ``None`` keeps every launch as it is.  ``point_source`` /
         ``point_claim``: a ``sources.PointSources`` (monopoles inside the volume), as ``LinearSpectral3D``; it coexists with ``source``,
         the scalar source and ``sponge``, and ``source_amplitude=0.0`` silences the facet source for a receive run; ``None`` keeps
-        every launch as it is."""
+        every launch as it is.  ``relaxation``: a ``relaxation.RelaxationAbsorption`` (power-law absorption), as ``LinearSpectral3D``:
+        K(c3) acts on u_n + sum xi, K(c4) on v_n as before, and the thermoviscous ``attenuation_coefficient_dB`` adds its f^2 part
+        (``relaxation.fit_power_law`` fits both together); ``speed_of_sound`` is then the EQUILIBRIUM (low-frequency) speed.  The
+        single-gather form is out of scope: with ``uniform_ratio=True`` a ``ValueError``.  ``None`` keeps every launch as it is."""
+        if relaxation is not None and uniform_ratio is True:
+            raise ValueError("WesterveltSpectral3D: relaxation= with uniform_ratio=True (the single-gather form w = u_n + kappa v_n) is not supported")
         c_cells, rho_cells = per_cell(speed_of_sound, mesh, "speed_of_sound"), per_cell(density, mesh, "density")
         beta_cells = per_cell(nonlinear_coefficient, mesh, "nonlinear_coefficient")
         att_cells = per_cell(attenuation_coefficient_dB, mesh, "attenuation_coefficient_dB")
         bd1, bd2, D, G_d, detJ_d, (dF1_d, dF2_d) = self._init_common(mesh, float_type, comm, fused, source_time)
         self._init_sponge(sponge)
+        self._init_relaxation(relaxation)
         self.f0 = float(source_frequency)
         self.w0 = 2 * np.pi * self.f0
         self._init_point_source(point_source, point_claim)
@@ -100,7 +106,9 @@ class WesterveltSpectral3D(SpectralSolver3D):
         self.mass_facet = ops.mass_operator(n * n, ft)
         self.axpy = ops.axpy(self.ndofs)
         # the reverse closures of the set-up exchange of the three assembled diagonals (m0, w2, w5) with the others
-        self.fwd_v, self.fwd_w = self._init_halo(halo_plan, forward=2, reverse=2, overlap=overlap)
+        # (the reference launch sequence with relaxation mechanisms scatters ur beside u_n, which the lumped mass still reads)
+        self.fwd_v, self.fwd_w, *more = self._init_halo(halo_plan, forward=2 if relaxation is None else 3, reverse=2, overlap=overlap)
+        self.fwd_r = more[0] if more else None
         if self.halo is not None:
             self.fwd_u, self.rev_m = self.halo.fwd, self._rev_setup[1]
         z = lambda: torch.zeros(self.ndofs, dtype=self.tdt, device=dev)  # noqa: E731
@@ -169,6 +177,7 @@ class WesterveltSpectral3D(SpectralSolver3D):
     def setup_schedule(self):
         yield from self._reverse_setup((self.m0, self.w2, self.w5))
         self._bind_sponge(self.m0)  # m0 is complete only now
+        yield from self._bind_relaxation()
 
     def source_values(self, t):
         """g and dg/dt (cuda/demo_nonlinear_bowl.py:560-595)."""
@@ -238,6 +247,8 @@ class WesterveltSpectral3D(SpectralSolver3D):
             self.fwd_u(self.u_n)
             self.fwd_v(self.v_n)
             self.fwd_w(self.w_n)
+            if self.relaxation is not None:
+                self.fwd_r(self._relax_bound().ur)
         # unsteady lumped mass
         fill(0.0, self.m)
         self.mass_cell(self.u_n, self.cc2, self.m, self.detJ, self.dofmap)
@@ -246,7 +257,7 @@ class WesterveltSpectral3D(SpectralSolver3D):
         axpy(1.0, self.m0, self.m)
         # right-hand side
         fill(0.0, self.b)
-        self.stiff(self.u_n, self.cc3, self.b, self.G, self.dofmap)
+        self.stiff(self._stiffness_input(self.u_n), self.cc3, self.b, self.G, self.dofmap)
         self.stiff(self.v_n, self.cc4, self.b, self.G, self.dofmap)
         self.mass_cell(self.w_n, self.cc5, self.b, self.detJ, self.dofmap)
         if self.source is None:
@@ -262,4 +273,5 @@ class WesterveltSpectral3D(SpectralSolver3D):
         ops.pointwise_divide(self.b, self.m, self.kv)
         axpy(B_RUNGE[i] * dt, self.ku, self.u)
         axpy(B_RUNGE[i] * dt, self.kv, self.v)
+        self._relax_reference(i, dt)
         yield from ()  # the base class's stage protocol is a generator; this sequence has nothing to post

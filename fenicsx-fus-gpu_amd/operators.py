@@ -653,6 +653,48 @@ def sponge_terms(y, u, v, bound):
                "fus_sponge_terms")
 
 
+RELAX_FIRST, RELAX_MIDDLE, RELAX_LAST = 0, 1, 2  # csrc/relax_table.hpp
+
+
+def relax_stage(bw, aw, aw_u, kind, tau, kappa, xi0, xin, acc, u_base, vn, ur, nlocal):
+    """The relaxation mechanisms' pass of one RK4 stage in one streaming launch (csrc/relaxation.hpp, ``fus_relax_stage_*``): per owned
+    dof and mechanism, with ``k = kappa vn - xin / tau`` of the stage's inputs,
+
+        FIRST   acc = xi0 + bw k ; xin = xi0 + aw k      MIDDLE   acc += bw k ; xin = xi0 + aw k      LAST   xi0 = acc + bw k
+
+    and ``ur = (u_base + aw_u vn) + sum`` of the variables the next stage sees.  ``tau``: host array [NR] (fp64); ``kappa``: a host
+    array [NR] (one scalar weight per mechanism: no weight vector is read) or a device tensor [NR, stride]; ``xi0`` / ``xin`` /
+    ``acc``: device tensors [NR, stride], stride >= nlocal; ``u_base`` / ``vn`` / ``ur``: at least ``nlocal`` entries."""
+    dt = xi0.dtype if isinstance(xi0, torch.Tensor) else None
+    for name, t in (("xi0", xi0), ("xin", xin), ("acc", acc), ("u_base", u_base), ("vn", vn), ("ur", ur)):
+        _req(t, dt, name)
+    tau = np.ascontiguousarray(tau, dtype=np.float64)
+    nr = tau.size
+    if tau.ndim != 1 or not 1 <= nr <= 4 or xi0.ndim != 2 or xi0.shape[0] != nr or xin.shape != xi0.shape or acc.shape != xi0.shape:
+        raise ValueError("relax_stage: 1 to 4 relaxation times, and xi0, xin, acc of one shape [NR, stride]")
+    stride, nlocal = int(xi0.shape[1]), int(nlocal)
+    if not 0 <= nlocal <= stride or min(u_base.numel(), vn.numel(), ur.numel()) < nlocal:
+        raise ValueError("relax_stage: 0 <= nlocal <= stride, and u_base, vn, ur of at least nlocal entries")
+    if isinstance(kappa, torch.Tensor):
+        _req(kappa, dt, "kappa")
+        if kappa.shape != xi0.shape:
+            raise ValueError("relax_stage: per-dof weights have the shape of the state, [NR, stride]")
+        ks, kd = None, kappa.data_ptr()
+    else:
+        ks = np.ascontiguousarray(kappa, dtype=np.float64)
+        if ks.shape != (nr,):
+            raise ValueError("relax_stage: one scalar weight per mechanism")
+        kd = None
+    if any(t.device != xi0.device for t in (xin, acc, u_base, vn, ur) + ((kappa,) if ks is None else ())):
+        raise ValueError("relax_stage: every operand must be on xi0's device")
+    if int(kind) not in (RELAX_FIRST, RELAX_MIDDLE, RELAX_LAST):
+        raise ValueError(f"relax_stage: kind 0 (FIRST), 1 (MIDDLE) or 2 (LAST), got {kind}")
+    fn = getattr(_lib.load(), f"fus_relax_stage_{_lib.suffix(dt)}")
+    _lib.check(fn(float(bw), float(aw), float(aw_u), int(kind), nr, tau.ctypes.data, None if ks is None else ks.ctypes.data, kd,
+                  xi0.data_ptr(), xin.data_ptr(), acc.data_ptr(), stride, u_base.data_ptr(), vn.data_ptr(), ur.data_ptr(), nlocal,
+                  _lib.stream_ptr()), "fus_relax_stage")
+
+
 def point_source_terms(y, bound, stage):
     """The point sources' terms of one RK4 stage in one launch (csrc/point_source.hpp, ``fus_point_source_*``): with ``bound`` a
     ``sources.BoundPointSources`` (the probe's tables ``cells`` / ``rows`` / ``weights`` and per-point ``amplitude`` / ``phase`` /

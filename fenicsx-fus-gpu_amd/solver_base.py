@@ -16,6 +16,13 @@ in its constructor and ``_bind_sponge(mass)`` at the end of ``setup_schedule``, 
 ``point_source=`` (monopoles inside the volume, sources.PointSources) one more again, ``_point_terms(t)`` at the stage's source time, in
 the same two places; a solver calls ``_init_point_source`` in its constructor.
 
+With ``relaxation=`` (power-law absorption through relaxation mechanisms, relaxation.py) every stiffness apply of a stage acts on
+``self._relax.ur = u_n + sum xi`` in the place of ``u_n`` (``_stiffness_input``; on a partitioned mesh ``ur`` is what travels), and a
+stage has one more streaming launch, ``_relax_pass``: before the vector pass in stages 1-3 (it reads ``u0`` and the stage's ``v_n``,
+which that pass overwrites), after it in stage 4 (it reads the new ``u0``).  A solver calls ``_init_relaxation`` in its constructor and
+``yield from self._bind_relaxation()`` at the end of ``setup_schedule`` (the per-dof weights are a lumped projection: its reverse
+exchange).  The lumped mass, the quadratic term, the facet terms, the sponge and the point sources still see ``u_n`` and ``v_n``.
+
 ``rk4_schedule`` and ``rk4_graph`` record through one hook, ``_recording`` (the steps and their factors: ``recording.py``);
 ``run_schedule`` drives one rank's schedule generator to its value (``rk4``, ``bioheat.py``, ``field_monitor.py``), ``run_lockstep``
 those of several ranks of one process.  ``MeshSolver3D`` is the set-up these solvers share with ``bioheat.py``.
@@ -244,10 +251,47 @@ class SpectralSolver3D(MeshSolver3D):
         if self._points is not None:
             ops.point_source_terms(self.b, self._points, self._points.stage_scalars(t))
 
+    # -- relaxation mechanisms (relaxation.RelaxationAbsorption): one streaming launch per stage, ur in the place of u_n ---------------
+    def _init_relaxation(self, relaxation):
+        """``relaxation``: a ``relaxation.RelaxationAbsorption`` or None.  Its state on the device needs the cell mass operator and, for
+        per-cell weights on a partitioned mesh, a reverse exchange: it is bound in ``setup_schedule`` (``_bind_relaxation``)."""
+        self.relaxation, self._relax = relaxation, None
+
+    def _bind_relaxation(self):
+        """Generator (it yields after posting each reverse exchange of the weights' lumped projection)."""
+        if self.relaxation is not None:
+            self._relax = yield from self.relaxation.bind_schedule(self)
+
+    def _relax_bound(self):
+        if self._relax is None:
+            raise _lib.FusGpuError("relaxation: the set-up exchange (setup_schedule) has not run, the mechanisms are not bound yet")
+        return self._relax
+
+    def _stiffness_input(self, u_n):
+        """What the stiffness applies of a stage act on: ``u_n``, or with relaxation mechanisms ``ur = u_n + sum xi``."""
+        return u_n if self.relaxation is None else self._relax_bound().ur
+
+    def _relax_pass(self, i, dt, u_base, vn):
+        """The mechanisms' pass of stage ``i``: xi through the stage (FIRST, MIDDLE, MIDDLE, LAST) and the next stage's ``ur`` =
+        ``u_base + a_{i+1} dt vn + sum xi`` (stage 4: ``u_base`` is the new u, nothing is added to it)."""
+        aw = 0.0 if i == 3 else A_RUNGE[i + 1] * dt
+        self._relax.stage(ops.RELAX_LAST if i == 3 else (ops.RELAX_FIRST if i == 0 else ops.RELAX_MIDDLE), B_RUNGE[i] * dt, aw, aw, u_base, vn)
+
+    def _relax_reference(self, i, dt):
+        """The pass in the reference launch sequence, at the end of stage ``i``: ``ku`` holds the stage's v_n, ``u`` the new u after stage 4."""
+        if self.relaxation is not None:
+            self._relax_pass(i, dt, self.u if i == 3 else self.u0, self.ku)
+
+    def _check_relaxation_step(self, dt):
+        if self.relaxation is not None:
+            self.relaxation.check_time_step(dt)
+
     def init(self):
-        """u = v = 0 (cuda/demo_linear_box.py:434-435)."""
+        """u = v = 0 (cuda/demo_linear_box.py:434-435); with relaxation mechanisms their memory variables too."""
         for t in (self.u, self.v, self.ku, self.kv):
             ops.fill(0.0, t)
+        if self.relaxation is not None:
+            self._relax_bound().zero()
 
     def _stage_time(self, t, i, dt):
         """The time stage ``i`` of the step from ``t`` evaluates its source at: the stage time (``source_time="tn"``) or,
@@ -298,7 +342,7 @@ class SpectralSolver3D(MeshSolver3D):
                 before_points()
                 self._point_terms(t)
 
-        yield from self._cell_terms(u_n, v_n, facets)
+        yield from self._cell_terms(self._stiffness_input(u_n), v_n, facets)
 
     def _fused_step(self, t, dt):
         """The 8 launches of one fused RK4 step from ``t``: the first stage reads (u0, v0) themselves, the others the stage
@@ -311,7 +355,11 @@ class SpectralSolver3D(MeshSolver3D):
                                                 stage_dev=self._sstage[i] if self.source is not None else None)
             else:
                 yield from self._operator_fused(self._stage_time(t, i, dt), u_n, v_n)
+            if self.relaxation is not None and i < 3:  # before the vector pass overwrites the stage's v_n (and, lean stage 3, u0)
+                self._relax_pass(i, dt, self.u0, v_n)
             self._vector_pass(*self._stage_args(i, dt))
+            if self.relaxation is not None and i == 3:  # after it: u0 is the new u; neither LAST kind writes ku
+                self._relax_pass(i, dt, self.u0, v_n)
 
     def _fused_enter(self):
         """Before a fused step loop: between steps the solution lives in (u0, v0), the first stage's inputs as they stand;
@@ -319,6 +367,8 @@ class SpectralSolver3D(MeshSolver3D):
         ops.fill(0.0, self.b)
         ops.copy(self.u, self.u0)
         ops.copy(self.v, self.v0)
+        if self.relaxation is not None:
+            self._relax_bound().enter(self.u0)
 
     def _fused_exit(self):
         ops.copy(self.u0, self.u)
@@ -375,9 +425,12 @@ class SpectralSolver3D(MeshSolver3D):
         mid-run through ``sensors`` (see ``rk4``; on a partitioned mesh a recording step posts a forward exchange of the
         field first, with a yield) or, over every owned dof, through ``monitor`` (no exchange, no yield)."""
         t, step = float(start_time), 0
+        self._check_relaxation_step(dt)
         record = self._recording(sensors, monitor, t, final_time, dt, max_steps, record_from, receivers)
         if self.fused:
             self._fused_enter()
+        elif self.relaxation is not None:
+            self._relax_bound().enter(self.u)
         for t0, h in rk4_steps(t, final_time, dt, max_steps):
             if self.fused:
                 yield from self._fused_step(t0, h)
@@ -395,7 +448,7 @@ class SpectralSolver3D(MeshSolver3D):
     # -- hipGraph replay (launch-bound meshes) -----------------------------------------------------------------------------
     def _graph_state(self):
         """The tensors a fused step mutates (saved / restored around the warm-up step of a capture)."""
-        return (self.u, self.v, self.u0, self.v0, self.ku, self.un, self.b)
+        return (self.u, self.v, self.u0, self.v0, self.ku, self.un, self.b) + (self._relax_bound().state() if self.relaxation is not None else ())
 
     def _step_graph(self, dt):
         g = self._graphs.get(dt)
@@ -437,6 +490,7 @@ class SpectralSolver3D(MeshSolver3D):
         if self._points is not None:
             raise _lib.FusGpuError("rk4_graph: a solver with point_source= cannot be replayed from a captured graph (the point sources' "
                                    "stage time is a host argument of their launch): use rk4")
+        self._check_relaxation_step(dt)
         t, tf = float(start_time), float(final_time)
         rows, ends = [], []
         record = self._recording(sensors, monitor, t, tf, dt, max_steps, record_from, receivers)

@@ -29,6 +29,7 @@
 
 #include "fus_gpu.h"
 #include "fus_gpu_array.h"
+#include "fus_gpu_relaxation.h"
 
 namespace fus_gpu {
 
@@ -488,6 +489,37 @@ class ElementReceive {
   const T* wgt_;
   const int64_t* offsets_;
   int64_t nelem_;
+};
+
+// Relaxation stage (fus_relax_stage_*): the streaming pass that advances the memory variables of ``nr`` relaxation mechanisms
+// (xi' = kappa v - xi / tau) through one RK4 stage and writes ur = u_n + sum xi of the next stage.  ``tau`` / ``kappa_scalar`` [nr]: host
+// arrays (fp64); ``kappa`` [nr][stride]: per-dof weights on the device, or null (then ``kappa_scalar``); ``xi0`` / ``xin`` / ``acc``
+// [nr][stride]: the state on the device, caller-owned and zeroed by the caller before the first step.
+template <typename T>
+class RelaxStage {
+ public:
+  enum Kind { FIRST = 0, MIDDLE = 1, LAST = 2 };
+  RelaxStage(int nr, const double* tau, const double* kappa_scalar, const T* kappa, T* xi0, T* xin, T* acc, int64_t stride, int64_t nlocal)
+      : nr_(nr), tau_(tau), ks_(kappa_scalar), kappa_(kappa), xi0_(xi0), xin_(xin), acc_(acc), stride_(stride), nlocal_(nlocal) {
+    check_abi();
+  }
+  // stage ``i`` in 0..3 of the step of length ``dt``: ur = (u_base + a_{i+1} dt vn) + sum of the next stage's variables.  Stages 0..2 run
+  // BEFORE the stage's vector pass (u_base = u0, vn = the stage's v_n), stage 3 after it (u_base = the new u0, vn = the stage's v_n)
+  void operator()(int i, double dt, const T* u_base, const T* vn, T* ur, void* stream = nullptr) const {
+    static const double a[4] = {0.0, 0.5, 0.5, 1.0}, bq[4] = {1.0 / 6.0, 1.0 / 3.0, 1.0 / 3.0, 1.0 / 6.0};
+    const int kind = i == 3 ? LAST : (i == 0 ? FIRST : MIDDLE);
+    const T aw = (T)(i == 3 ? 0.0 : a[i + 1] * dt);
+    check(detail::typed<T>(fus_relax_stage_f64, fus_relax_stage_f32)((T)(bq[i] * dt), aw, aw, kind, nr_, tau_, ks_, kappa_, xi0_, xin_, acc_, stride_,
+                                                                     u_base, vn, ur, nlocal_, stream),
+          "fus_relax_stage");
+  }
+
+ private:
+  int nr_;
+  const double *tau_, *ks_;
+  const T* kappa_;
+  T *xi0_, *xin_, *acc_;
+  int64_t stride_, nlocal_;
 };
 
 }  // namespace fus_gpu

@@ -3,6 +3,7 @@
 ``-Rpass-analysis=kernel-resource-usage`` remarks (no GPU needed: hipcc cross-compiles gfx950).
 
     python tools/resource_usage.py [regex ...]      # compile (if stale) and print matching kernels
+    python tools/resource_usage.py relaxation        # the relaxation pass (csrc/relaxation.hpp: relax_stage_kernel)
 
 ``parse()`` / ``compile_remarks()`` are what tests/test_resource_usage.py pins the shipped builds with."""
 import os
@@ -70,7 +71,7 @@ def cached_remarks():
     """Remarks of the current sources, cached under csrc/_asm keyed on source mtimes."""
     cache = os.path.join(CSRC, "_asm", "resource_usage_device.txt")
     srcs = [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith((".hip", ".hpp"))]
-    srcs += [os.path.join(ROOT, "include", h) for h in ("fus_gpu.h", "fus_gpu_array.h")]
+    srcs += [os.path.join(ROOT, "include", h) for h in ("fus_gpu.h", "fus_gpu_array.h", "fus_gpu_relaxation.h")]
     newest = max(os.path.getmtime(p) for p in srcs)
     if os.path.exists(cache) and os.path.getmtime(cache) >= newest:
         return open(cache).read()
@@ -81,8 +82,12 @@ def cached_remarks():
     return text
 
 
+# names for a kernel family that its kernels' own names do not contain
+ALIASES = {"relaxation": "relax_stage_kernel"}
+
+
 def main():
-    pats = [re.compile(p) for p in sys.argv[1:]] or [re.compile("stiffness_plan|westervelt_cell|sponge_terms|point_source|element_receive")]
+    pats = [re.compile(ALIASES.get(p, p)) for p in sys.argv[1:]] or [re.compile("stiffness_plan|westervelt_cell|sponge_terms|point_source|element_receive")]
     table = parse(cached_remarks())
     for name, d in table.items():
         if any(p.search(name) for p in pats):
