@@ -382,6 +382,11 @@ def bootstrap_of(comm):
     return comm if hasattr(comm, "allgather_bytes") else None
 
 
+def comm_size(comm):
+    """The number of ranks a gather over ``comm`` spans (``None``: one)."""
+    return int(getattr(comm, "size", 1))
+
+
 def gather_arrays(comm, arrays, what, instead):
     """The named numpy ``arrays`` of every rank through the communicator's bootstrap (``allgather_bytes``): one dict per rank, in
     rank order.  Ranks driven from one process have none: ``ValueError`` naming the caller (``what``) and what to use ``instead``."""

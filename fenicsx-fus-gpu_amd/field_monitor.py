@@ -75,7 +75,7 @@ class FieldMonitor:
     def expect_steps(self, start_time, final_time, dt, max_steps=None, record_from=None):
         """Upload, in one copy, the harmonic factors of every step an ``rk4(start_time, final_time, dt, max_steps)`` call will
         record (``recording.record_times``: the steps that end after ``record_from``), as ``PointSensors.expect_steps`` does."""
-        self.factors.plan(record_times(start_time, final_time, dt, max_steps, record_from))
+        self.factors.plan_steps(start_time, final_time, dt, max_steps, record_from)
 
     def record(self, u, v=None, t=0.0):
         """One launch: the owned dofs of ``u`` (and ``v``, for its mean square) at time ``t`` into every accumulator."""
@@ -119,10 +119,8 @@ class FieldMonitor:
         return acc / float(self.nacc)
 
     def _harmonic(self, k):
-        if k not in self.harmonics:
-            raise ValueError(f"harmonic {k} is not accumulated (harmonics={self.harmonics})")
+        h = self.factors.index(k)
         self._recorded("harmonic")
-        h = self.harmonics.index(k)
         return self._hre[h, : self.nlocal], self._him[h, : self.nlocal]
 
     def harmonic_amplitude(self, k):
@@ -246,12 +244,12 @@ def focus(field, solver, level=0.5, comm=None):
     ``max, dof, rank, position, level, volume``.  Torch reductions on the device.  ``comm``: reduce over its ranks through the
     bootstrap's ``allgather_bytes``, as ``PointSensors.gather``; without it the record is this rank's and also carries the
     candidates of the global volume (``values``, ``volumes`` of the dofs above ITS threshold) for ``merge_focus``."""
+    from .scatterer import comm_size, gather_arrays
+
     vol = dof_volumes(solver)
     rec = _focus_local(field, solver, level, vol)
-    size = int(getattr(comm, "size", 1)) if comm is not None else 1
-    if size == 1:
+    if comm_size(comm) == 1:
         return rec
-    from .scatterer import gather_arrays
 
     def gather(d):
         return gather_arrays(comm, {k: np.asarray(v, dtype=np.float64) for k, v in d.items()}, "focus", "merge_focus")

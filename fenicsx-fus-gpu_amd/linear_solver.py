@@ -79,13 +79,12 @@ class LinearSpectral3D(SpectralSolver3D):
         the phase speed rises with frequency (``RelaxationAbsorption.phase_speed``).  ``None`` keeps every launch as it is."""
         c_cells, rho_cells = per_cell(speed_of_sound, mesh, "speed_of_sound"), per_cell(density, mesh, "density")
         bd1, bd2, D, G_d, detJ_d, (dF1_d, dF2_d) = self._init_common(mesh, float_type, comm, fused, source_time)
-        self._init_sponge(sponge)
         self._init_relaxation(relaxation)
         self.c0, self.rho0 = float(c_cells.mean()), float(rho_cells.mean())
         self.rho_cells, self.c_cells = rho_cells, c_cells  # per cell, the mesh's cell order (intensity.py)
         self.f0, self.p0 = float(source_frequency), float(source_amplitude)
         self.w0 = 2.0 * np.pi * self.f0
-        self._init_point_source(point_source, point_claim)
+        self._init_terms(sponge, point_source, point_claim)
         P, n, dev, ft = self.P, self.P + 1, self.dev, self.tdt_np
         self.D = D
         rho, c = rho_cells.astype(ft), c_cells.astype(ft)
@@ -103,12 +102,10 @@ class LinearSpectral3D(SpectralSolver3D):
         self.G, self.detJ, self.dofmap = G_d, detJ_d, td(mesh.dofmap)
         self.detJ_f1, self.detJ_f2 = dF1_d, dF2_d
         self.fdm1, self.fdm2 = td(mesh.facet_dofmap(bd1)), td(mesh.facet_dofmap(bd2))
-        # the fused stage's facet sets: M_f1(g c1) 1 with g = source_value(t), M_f2(c2) v_n
-        self._source_set = (self.facet_coeff1, None, self.detJ_f1, self.fdm1)
+        # the fused stage's facet sets: M_f1(g c1) 1 with g = source_value(t) -- or, with a phased-array source (sources.py), through
+        # fus_facet_source_array_* with g = p0 w0 / c0 per element -- and M_f2(c2) v_n
+        self._init_source(source, bd1, self.p0 * self.w0 / self.c0, (self.facet_coeff1, None, self.detJ_f1, self.fdm1))
         self._absorbing_set = (self.facet_coeff2, self.detJ_f2, self.fdm2)
-        # phased-array source (sources.py): the source-facet term through fus_facet_source_array_* with g = p0 w0 / c0 per element
-        self.source = None if source is None else source.bind(mesh, bd1, ft, dev, frequency=self.f0, scale=self.p0 * self.w0 / self.c0,
-                                                              coeff1=self.facet_coeff1, detJ=self.detJ_f1, dofmap=self.fdm1)
 
         # ---- operators and halo ---------------------------------------------------------------------
         self.stiff, self.G, self.affine, self.in_kernel_geometry, self.G_array = stiffness_form(
@@ -146,7 +143,7 @@ class LinearSpectral3D(SpectralSolver3D):
         yield from self._reverse_setup([self.m])
         ops.fill(1.0, self.minv)
         ops.pointwise_divide(self.minv, self.m, self.minv)  # owned entries are what the fused kernel reads
-        self._bind_sponge(self.m)  # m is complete only now
+        self._bind_terms(self.m)  # m is complete only now
         yield from self._bind_relaxation()
 
     def source_value(self, t):
@@ -176,20 +173,19 @@ class LinearSpectral3D(SpectralSolver3D):
         axpy(A_RUNGE[i] * dt, self.kv, self.vn)
         copy(self.vn, self.ku)  # f0
         ts = self._stage_time(t, i, dt)
-        if self.source is None:
+        if self.source is None:  # the reference's own launches: g filled into a vector, then its facet mass apply
             fill(self.source_value(ts), self.g)
+            source_facets = lambda: self._mass_facet_stage(self.g, self.facet_coeff1, self.b, self.detJ_f1, self.fdm1)  # noqa: E731
+        else:  # the array's source facets alone (no set B) replace both
+            source_facets = lambda: self._facet_source.launch(self.b, None, t=ts)  # noqa: E731
         copy(self.un, self.u_n)
         copy(self.vn, self.v_n)
         fill(0.0, self.b)
 
         def facets():
-            if self.source is None:
-                self._mass_facet_stage(self.g, self.facet_coeff1, self.b, self.detJ_f1, self.fdm1)
-            else:  # the array's source facets alone (no set B): replaces filling g and its facet mass apply
-                ops.facet_source_terms(self.b, self.source, None, stage=self.source.stage_scalars(ts))
+            source_facets()
             self._mass_facet_stage(self.v_n, self.facet_coeff2, self.b, self.detJ_f2, self.fdm2)
-            self._sponge_terms(self.u_n, self.v_n)
-            self._point_terms(ts)
+            self._extra_terms(self.u_n, self.v_n, ts)
 
         yield from self._cell_terms(self._stiffness_input(self.u_n), self.v_n, facets)
         ops.pointwise_divide(self.b, self.m, self.kv)

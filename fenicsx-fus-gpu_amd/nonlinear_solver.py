@@ -58,11 +58,10 @@ class WesterveltSpectral3D(SpectralSolver3D):
         beta_cells = per_cell(nonlinear_coefficient, mesh, "nonlinear_coefficient")
         att_cells = per_cell(attenuation_coefficient_dB, mesh, "attenuation_coefficient_dB")
         bd1, bd2, D, G_d, detJ_d, (dF1_d, dF2_d) = self._init_common(mesh, float_type, comm, fused, source_time)
-        self._init_sponge(sponge)
         self._init_relaxation(relaxation)
         self.f0 = float(source_frequency)
         self.w0 = 2 * np.pi * self.f0
-        self._init_point_source(point_source, point_claim)
+        self._init_terms(sponge, point_source, point_claim)
         pick = (lambda a: float(a[bd1[:, 0]].mean())) if bd1.shape[0] else (lambda a: float(a.mean()))
         self.c0 = float(reference_speed_of_sound) if reference_speed_of_sound is not None else (
             float(speed_of_sound) if np.ndim(speed_of_sound) == 0 else pick(c_cells))
@@ -93,12 +92,10 @@ class WesterveltSpectral3D(SpectralSolver3D):
         self.dF1, self.dF2 = dF1_d, dF2_d
         self.fdm1 = torch.from_numpy(mesh.facet_dofmap(bd1)).to(dev)
         self.fdm2 = torch.from_numpy(mesh.facet_dofmap(bd2)).to(dev)
-        # the fused stage's facet sets: M_f1(fc1_1 g + fc2_1 dg) 1 with (g, dg) = source_values(t), M_f2(fc2_2) v_n
-        self._source_set = (self.fc1_1, self.fc2_1, self.dF1, self.fdm1)
+        # the fused stage's facet sets: M_f1(fc1_1 g + fc2_1 dg) 1 with (g, dg) = source_values(t) -- or, with a phased-array source
+        # (sources.py), g = 2 p0 w0 / c0 per element and its derivative through fus_facet_source_array_* -- and M_f2(fc2_2) v_n
+        self._init_source(source, bd1, 2.0 * self.p0 * self.w0 / self.c0, (self.fc1_1, self.fc2_1, self.dF1, self.fdm1))
         self._absorbing_set = (self.fc2_2, self.dF2, self.fdm2)
-        # phased-array source (sources.py): g = 2 p0 w0 / c0 per element and its derivative through fus_facet_source_array_*
-        self.source = None if source is None else source.bind(mesh, bd1, ft, dev, frequency=self.f0, scale=2.0 * self.p0 * self.w0 / self.c0,
-                                                              coeff1=self.fc1_1, coeff2=self.fc2_1, detJ=self.dF1, dofmap=self.fdm1)
         self.stiff = ops.stiffness_operator(P, D.flatten(), ft)
         # detJ never changes in the life of a solver: the reference-sequence stage applies the cell mass operator twice per stage
         # with it (cuda/demo_nonlinear_bowl.py:612-616, 630-632) -- streamed from a row-ordered copy instead of gathered
@@ -176,7 +173,7 @@ class WesterveltSpectral3D(SpectralSolver3D):
 
     def setup_schedule(self):
         yield from self._reverse_setup((self.m0, self.w2, self.w5))
-        self._bind_sponge(self.m0)  # m0 is complete only now
+        self._bind_terms(self.m0)  # m0 is complete only now
         yield from self._bind_relaxation()
 
     def source_values(self, t):
@@ -236,10 +233,16 @@ class WesterveltSpectral3D(SpectralSolver3D):
         axpy(A_RUNGE[i] * dt, self.kv, self.vn)
         copy(self.vn, self.ku)
         ts = self._stage_time(t, i, dt)
-        if self.source is None:
+        if self.source is None:  # the reference's own launches: g and dg filled into vectors, then their facet mass applies
             gv, dgv = self.source_values(ts)
             fill(gv, self.g)
             fill(dgv, self.dg)
+
+            def source_facets():
+                self.mass_facet(self.g, self.fc1_1, self.b, self.dF1, self.fdm1)
+                self.mass_facet(self.dg, self.fc2_1, self.b, self.dF1, self.fdm1)
+        else:  # the array's g and dg terms in one launch (no set B) replace all four
+            source_facets = lambda: self._facet_source.launch(self.b, None, t=ts)  # noqa: E731
         copy(self.un, self.u_n)
         copy(self.vn, self.v_n)
         ops.square(self.vn, self.w_n)
@@ -260,14 +263,9 @@ class WesterveltSpectral3D(SpectralSolver3D):
         self.stiff(self._stiffness_input(self.u_n), self.cc3, self.b, self.G, self.dofmap)
         self.stiff(self.v_n, self.cc4, self.b, self.G, self.dofmap)
         self.mass_cell(self.w_n, self.cc5, self.b, self.detJ, self.dofmap)
-        if self.source is None:
-            self.mass_facet(self.g, self.fc1_1, self.b, self.dF1, self.fdm1)
-            self.mass_facet(self.dg, self.fc2_1, self.b, self.dF1, self.fdm1)
-        else:  # the array's g and dg terms in one launch (no set B)
-            ops.facet_source_terms(self.b, self.source, None, stage=self.source.stage_scalars(ts))
+        source_facets()
         self.mass_facet(self.v_n, self.fc2_2, self.b, self.dF2, self.fdm2)
-        self._sponge_terms(self.u_n, self.v_n)
-        self._point_terms(ts)
+        self._extra_terms(self.u_n, self.v_n, ts)
         if self.halo is not None:
             self.halo.rev(self.b)
         ops.pointwise_divide(self.b, self.m, self.kv)

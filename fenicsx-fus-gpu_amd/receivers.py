@@ -24,7 +24,7 @@ from __future__ import annotations
 
 import numpy as np
 
-from .recording import HarmonicFactors, record_times
+from .recording import SeriesRecorder
 from .sources import SourceArray
 
 
@@ -61,7 +61,7 @@ def merge(per_rank):
         return np.where(area > 0, total / np.where(area > 0, area, 1.0), np.nan)
 
 
-class ElementReceivers:
+class ElementReceivers(SeriesRecorder):
     """The elements of a receiving array on ``mesh`` (see the module docstring).
 
     ``element_of_facet`` / ``n_elements``: as ``sources.SourceArray`` (the assignment IS ``SourceArray.assign``); ``facets``: the
@@ -73,26 +73,20 @@ class ElementReceivers:
                  facets=None, detJ=None):
         import torch
 
-        from . import _lib
-
-        self._lib = _lib
         self.element_of_facet = element_of_facet
         bd = mesh.boundary_facets([getattr(mesh, "source_tag", 2)]) if facets is None else np.asarray(facets).reshape(-1, 2)
         self.array = SourceArray(element_of_facet, n_elements=n_elements)
         self.ids = self.array.assign(mesh, bd)
         self.n_elements = E = self.array.n_elements
-        self.ndofs = int(mesh.ndofs)
-        self.tdt_np, self.tdt = np.dtype(float_type), _lib.torch_dtype(float_type)
-        self.capacity = int(capacity)
-        if self.capacity < 0:
-            raise ValueError("capacity must be >= 0")
-        self.factors = HarmonicFactors(harmonics, frequency)
-        self.harmonics, self.omega = self.factors.harmonics, self.factors.omega
-        self.dev = dev = torch.device("cuda", torch.cuda.current_device())
+        super().__init__(float_type, mesh.ndofs, E, capacity, harmonics, frequency)
+        dev = self.dev
         fdm = np.asarray(mesh.facet_dofmap(bd)).reshape(bd.shape[0], (int(mesh.P) + 1) ** 2)
         if fdm.size and int(fdm.max()) >= self.ndofs:
             raise ValueError("facet dofmap entry outside the local vector")
-        detJ = self._facet_detJ(mesh, bd) if detJ is None else detJ
+        if detJ is None:  # as the solvers' set-up forms it
+            from .solver_base import device_facet_detJ
+
+            detJ, = device_facet_detJ(mesh, int(mesh.P), self.tdt_np, dev, [bd])
         detJ = detJ.detach().cpu().numpy() if isinstance(detJ, torch.Tensor) else np.asarray(detJ)
         dof, wgt, self.offsets = element_entries(self.ids, fdm, detJ.astype(self.tdt_np), E)
         # the area of an element is the sum of the weights the kernel multiplies with (those of the field's type), in double
@@ -101,62 +95,17 @@ class ElementReceivers:
         if dof.size == 0:  # no entries on this rank: the kernel reads none, and the C ABI takes no null list
             dof, wgt = np.zeros(1, np.int32), np.zeros(1, self.tdt_np)
         self._dof, self._wgt, self._offsets = td(dof), td(wgt), td(self.offsets)
-        H = len(self.harmonics)
-        self._rec = torch.zeros((self.capacity, E), dtype=self.tdt, device=dev) if self.capacity else None
-        self._hre = torch.empty((H, E), dtype=torch.float64, device=dev) if H else None
-        self._him = torch.empty((H, E), dtype=torch.float64, device=dev) if H else None
         self.reset()
 
-    def _facet_detJ(self, mesh, bd):
-        """The scaled facet detJ of ``bd`` on the device, as the solvers' set-up forms it (solver_base.device_geometry)."""
-        import torch
-
-        from .gll import tabulate_1d, tensor_weights_2d
-        from .precompute import compute_boundary_facets_scaled_jacobian_determinant_device, tabulate_facet_gradients
-
-        ft, n = self.tdt_np, int(mesh.P) + 1
-        dF = torch.zeros((bd.shape[0], n * n), dtype=self.tdt, device=self.dev)
-        if bd.shape[0]:
-            td = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(self.dev)  # noqa: E731
-            pts, wts, _ = tabulate_1d(int(mesh.P), ft)
-            compute_boundary_facets_scaled_jacobian_determinant_device(
-                dF, (td(mesh.x_dofs), td(mesh.x_g)), td(bd.astype(np.int32)), td(tabulate_facet_gradients(pts, ft)),
-                td(tensor_weights_2d(wts).astype(ft)))
-        return dF
-
     # -- device --------------------------------------------------------------------------------------------------------
-    def reset(self):
-        """Clear the series and the accumulators."""
-        self.nrec = 0  # rows written to the series
-        self.nacc = 0  # records accumulated into the harmonics
-        if self._hre is not None:
-            self._hre.zero_()
-            self._him.zero_()
-
-    @property
-    def full(self):
-        """True once every row of the series is written (a set without a series is never full)."""
-        return self.capacity > 0 and self.nrec >= self.capacity
-
-    def expect_steps(self, start_time, final_time, dt, max_steps=None, record_from=None):
-        """Upload, in one copy, the harmonic factors of every step an ``rk4`` call will record (``PointSensors.expect_steps``)."""
-        room = self.capacity - self.nrec if self.capacity else 1 << 16
-        self.factors.plan(record_times(start_time, final_time, dt, max_steps, record_from, limit=room))
-
     def record(self, u, t):
         """One launch: row ``nrec`` of the series and the harmonic terms of the elements' integrals of ``u`` (device, owned + ghosts,
         ghosts current) at time ``t``."""
         from . import operators as ops
 
-        self._lib.require_device_tensor(u, self.tdt, "u")
-        if u.numel() < self.ndofs:
-            raise ValueError(f"u: {u.numel()} values, the mesh has {self.ndofs} local dofs")
-        if self.full:
-            raise ValueError(f"record: the series is full ({self.capacity} rows)")
+        self._check_record(u)
         ops.element_receive(u, self._dof, self._wgt, self._offsets, self._rec, self.nrec, self._hre, self._him, self.factors.row(t))
-        if self._rec is not None:
-            self.nrec += 1
-        self.nacc += 1
+        self._recorded()
 
     # -- host accessors ------------------------------------------------------------------------------------------------
     def areas(self):
@@ -171,9 +120,7 @@ class ElementReceivers:
 
     def harmonic_sums(self, k):
         """``sum_t S_e(t) e^{-i k w t}`` over the records, complex ``[E]``: this rank's part, not normalised."""
-        if k not in self.harmonics:
-            raise ValueError(f"harmonic {k} is not accumulated (harmonics={self.harmonics})")
-        h = self.harmonics.index(k)
+        h = self.factors.index(k)
         return self._hre[h].cpu().numpy() + 1j * self._him[h].cpu().numpy()
 
     def series(self):
@@ -188,12 +135,11 @@ class ElementReceivers:
     def gather(self, comm, values=None):
         """The area averages over the whole elements from every rank's parts (``values``: this rank's integrals, default
         ``integrals()``; elements on the last axis) through the communicator's bootstrap.  Ranks driven from one process: ``merge``."""
-        values = self.integrals().astype(np.float64) if values is None else np.asarray(values)
-        size = int(getattr(comm, "size", 1)) if comm is not None else 1
-        if size == 1:
-            return merge([(self._areas, values)])
-        from .scatterer import gather_arrays
+        from .scatterer import comm_size, gather_arrays
 
+        values = self.integrals().astype(np.float64) if values is None else np.asarray(values)
+        if comm_size(comm) == 1:
+            return merge([(self._areas, values)])
         every = gather_arrays(comm, {"areas": self._areas, "values": values}, "ElementReceivers.gather", "receivers.merge")
         return merge([(z["areas"], z["values"]) for z in every])
 

@@ -1,6 +1,7 @@
 """
 Which steps of an RK4 run are recorded (``rk4_steps``, ``record_times``) and the harmonic factors of those steps on the device
-(``HarmonicFactors``): the host side that ``sensors.PointSensors`` and ``field_monitor.FieldMonitor`` share.
+(``HarmonicFactors``): the host side that ``sensors.PointSensors``, ``receivers.ElementReceivers`` and
+``field_monitor.FieldMonitor`` share; the first two also their life cycle (``SeriesRecorder``).
 
 A recorder's kernel reads the 2H factors of its step from device memory.  A host->device copy ordered between the launches of a
 step costs more than the recorder's launch, so a time loop announces its steps first (``expect_steps`` -> ``plan``: one pinned
@@ -76,6 +77,16 @@ class HarmonicFactors:
         """How many planned rows ``row`` has not handed out yet."""
         return len(self._plan_t) - self._plan_i
 
+    def index(self, k):
+        """The accumulator row of harmonic ``k``."""
+        if k not in self.harmonics:
+            raise ValueError(f"harmonic {k} is not accumulated (harmonics={self.harmonics})")
+        return self.harmonics.index(k)
+
+    def plan_steps(self, start_time, final_time, dt, max_steps=None, record_from=None, limit=None):
+        """``plan`` the steps an ``rk4(start_time, final_time, dt, max_steps)`` call records (``record_times``)."""
+        self.plan(record_times(start_time, final_time, dt, max_steps, record_from, limit))
+
     def plan(self, times):
         """Upload, in one copy, the rows of ``times``: the records to come, in their order.  Replaces the previous plan."""
         if not self.harmonics:
@@ -113,3 +124,70 @@ class HarmonicFactors:
         self._ring_ev[k] = torch.cuda.Event()
         self._ring_ev[k].record()
         return self._coef
+
+
+SERIES_LESS_STEPS = 1 << 16  # the most steps a recorder without a series (never full) plans factors for in one rk4 call
+
+
+class SeriesRecorder:
+    """What the two series recorders share (``sensors.PointSensors``, ``receivers.ElementReceivers``): a series of ``capacity`` rows of
+    ``width`` values in the field's type, the harmonic accumulators [H, width] (fp64) with their factors, and the counters.  A
+    subclass launches in ``record`` between ``_check_record(u)`` and ``_recorded()``."""
+
+    def __init__(self, float_type, ndofs, width, capacity, harmonics, frequency):
+        import torch
+
+        from . import _lib
+
+        self._lib = _lib
+        self.ndofs = int(ndofs)
+        self.tdt_np, self.tdt = np.dtype(float_type), _lib.torch_dtype(float_type)
+        self.capacity = int(capacity)
+        if self.capacity < 0:
+            raise ValueError("capacity must be >= 0")
+        self.factors = HarmonicFactors(harmonics, frequency)
+        self.harmonics, self.omega = self.factors.harmonics, self.factors.omega
+        self.dev = dev = torch.device("cuda", torch.cuda.current_device())
+        H = len(self.harmonics)
+        self._rec = torch.zeros((self.capacity, width), dtype=self.tdt, device=dev) if self.capacity else None
+        self._hre = torch.empty((H, width), dtype=torch.float64, device=dev) if H else None
+        self._him = torch.empty((H, width), dtype=torch.float64, device=dev) if H else None
+
+    def reset(self):
+        """Clear the series and the accumulators."""
+        self.nrec = 0  # rows written to the series
+        self.nacc = 0  # records accumulated into the harmonics (and whatever ``_reset_more`` clears)
+        if self._hre is not None:
+            self._hre.zero_()
+            self._him.zero_()
+        self._reset_more()
+
+    def _reset_more(self):
+        pass
+
+    @property
+    def full(self):
+        """True once every row of the series is written (a set without a series is never full)."""
+        return self.capacity > 0 and self.nrec >= self.capacity
+
+    def expect_steps(self, start_time, final_time, dt, max_steps=None, record_from=None):
+        """Upload, in one copy, the harmonic factors of every step an ``rk4(start_time, final_time, dt, max_steps)`` call
+        will record (``record_times``: the steps that end after ``record_from``, while the series has room);
+        ``record`` then reads them from that table.  The solvers call this at the start of ``rk4``."""
+        room = self.capacity - self.nrec if self.capacity else SERIES_LESS_STEPS
+        self.factors.plan_steps(start_time, final_time, dt, max_steps, record_from, limit=room)
+
+    def _check_field(self, u):
+        self._lib.require_device_tensor(u, self.tdt, "u")
+        if u.numel() < self.ndofs:
+            raise ValueError(f"u: {u.numel()} values, the mesh has {self.ndofs} local dofs")
+
+    def _check_record(self, u):
+        self._check_field(u)
+        if self.full:
+            raise ValueError(f"record: the series is full ({self.capacity} rows)")
+
+    def _recorded(self):
+        if self._rec is not None:
+            self.nrec += 1
+        self.nacc += 1

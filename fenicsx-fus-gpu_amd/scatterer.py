@@ -45,7 +45,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from .comm import NativeComm, TorchComm, as_comm, bootstrap_of, default_comm, gather_arrays, gather_floats, vote  # noqa: F401
+from .comm import NativeComm, TorchComm, as_comm, bootstrap_of, comm_size, default_comm, gather_arrays, gather_floats, vote  # noqa: F401
 from .halo_apply import HaloApply  # noqa: F401
 from .utils import to_flat
 

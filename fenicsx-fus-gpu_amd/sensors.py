@@ -27,7 +27,7 @@ import numpy as np
 
 from .gll import gll_points_weights
 from .point_evaluation import CellLocator, _invert, _lagrange_1d
-from .recording import HarmonicFactors, harmonic_coefficients, record_times  # noqa: F401  (harmonic_coefficients: re-exported)
+from .recording import SeriesRecorder, harmonic_coefficients  # noqa: F401  (harmonic_coefficients: re-exported)
 
 
 @dataclass
@@ -94,7 +94,7 @@ def merge(per_rank, npoints=None):
     return out
 
 
-class PointSensors:
+class PointSensors(SeriesRecorder):
     """A fixed set of points of ``mesh``, evaluated on the device (``fus_probe_eval_*``).
 
     ``capacity``: rows of the time series (``record`` writes one per call; 0 = no series); ``peak``: running max / min;
@@ -103,60 +103,29 @@ class PointSensors:
     def __init__(self, mesh, points, float_type=np.float64, capacity=0, peak=False, harmonics=(), frequency=None, locator=None):
         import torch
 
-        from . import _lib
-
-        self._lib = _lib
         self.P = int(mesh.P)
-        self.ndofs = int(mesh.ndofs)
         self.npoints = int(_as_points(points).shape[0])
         self.setup = sensor_setup(mesh, points, locator)
         self.point_ids, self.points = self.setup.point_ids, self.setup.points
-        self.tdt_np = np.dtype(float_type)
-        self.tdt = _lib.torch_dtype(float_type)
-        self.capacity = int(capacity)
-        if self.capacity < 0:
-            raise ValueError("capacity must be >= 0")
-        self.factors = HarmonicFactors(harmonics, frequency)
-        self.harmonics, self.omega = self.factors.harmonics, self.factors.omega
+        self.m = m = self.point_ids.size
+        super().__init__(float_type, mesh.ndofs, m, capacity, harmonics, frequency)
         if self.setup.rows.size and int(self.setup.rows.max()) >= self.ndofs:
             raise ValueError("dofmap row outside the local vector")
-        dev = torch.device("cuda", torch.cuda.current_device())
-        self.dev = dev
-        m, H = self.point_ids.size, len(self.harmonics)
-        self.m = m
+        dev = self.dev
         td = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)  # noqa: E731
         self._cells = td(self.setup.cell_index)
         self._rows = td(self.setup.rows)
         self._w = td(self.setup.weights.astype(self.tdt_np))
-        self._rec = torch.zeros((max(self.capacity, 1), m), dtype=self.tdt, device=dev) if self.capacity else None
         self._pmax = torch.empty(m, dtype=torch.float64, device=dev) if peak else None
         self._pmin = torch.empty(m, dtype=torch.float64, device=dev) if peak else None
-        self._hre = torch.empty((H, m), dtype=torch.float64, device=dev) if H else None
-        self._him = torch.empty((H, m), dtype=torch.float64, device=dev) if H else None
-        self._fn = getattr(_lib.load(), f"fus_probe_eval_{_lib.suffix(self.tdt)}")
+        self._fn = getattr(self._lib.load(), f"fus_probe_eval_{self._lib.suffix(self.tdt)}")
         self.reset()
 
     # -- device --------------------------------------------------------------------------------------------------------
-    def reset(self):
-        """Clear the series and the accumulators."""
-        self.nrec = 0  # rows written to the series
-        self.nacc = 0  # records accumulated into the peaks / harmonics
+    def _reset_more(self):
         if self._pmax is not None:
             self._pmax.fill_(-np.inf)
             self._pmin.fill_(np.inf)
-        if self._hre is not None:
-            self._hre.zero_()
-            self._him.zero_()
-
-    @property
-    def full(self):
-        """True once every row of the series is written (a set without a series is never full)."""
-        return self.capacity > 0 and self.nrec >= self.capacity
-
-    def _check_field(self, u):
-        self._lib.require_device_tensor(u, self.tdt, "u")
-        if u.numel() < self.ndofs:
-            raise ValueError(f"u: {u.numel()} values, the mesh has {self.ndofs} local dofs")
 
     def _launch(self, u, rec, capacity, slot, pmax=None, pmin=None, hre=None, him=None, coef=None, H=0):
         ptr = lambda t: None if t is None else t.data_ptr()  # noqa: E731
@@ -177,23 +146,12 @@ class PointSensors:
         self._launch(u, out, 1, 0)
         return out[0]
 
-    def expect_steps(self, start_time, final_time, dt, max_steps=None, record_from=None):
-        """Upload, in one copy, the harmonic factors of every step an ``rk4(start_time, final_time, dt, max_steps)`` call
-        will record (``recording.record_times``: the steps that end after ``record_from``, while the series has room);
-        ``record`` then reads them from that table.  The solvers call this at the start of ``rk4``."""
-        room = self.capacity - self.nrec if self.capacity else 1 << 16
-        self.factors.plan(record_times(start_time, final_time, dt, max_steps, record_from, limit=room))
-
     def record(self, u, t):
         """One launch: row ``nrec`` of the series, the peaks and the harmonic terms of the field ``u`` at time ``t``."""
-        self._check_field(u)
-        if self.full:
-            raise ValueError(f"record: the series is full ({self.capacity} rows)")
+        self._check_record(u)
         coef, H = self.factors.row(t), len(self.harmonics)
         self._launch(u, self._rec, self.capacity, self.nrec, self._pmax, self._pmin, self._hre, self._him, coef, H)
-        if self._rec is not None:
-            self.nrec += 1
-        self.nacc += 1
+        self._recorded()
 
     # -- host accessors ------------------------------------------------------------------------------------------------
     def series(self):
@@ -211,9 +169,7 @@ class PointSensors:
     def harmonic_amplitude(self, k):
         """``(2 / N) |sum p e^{-i k w t}|`` over the N records: the amplitude of the k-th harmonic, exact for a periodic
         field sampled at N equal steps over one period (the solvers' ``dt = period / steps_per_period``)."""
-        if k not in self.harmonics:
-            raise ValueError(f"harmonic {k} is not accumulated (harmonics={self.harmonics})")
-        h = self.harmonics.index(k)
+        h = self.factors.index(k)
         if self.nacc == 0:
             return np.zeros(self.m)
         re, im = self._hre[h].cpu().numpy(), self._him[h].cpu().numpy()
@@ -223,11 +179,10 @@ class PointSensors:
         """``values`` (default: ``series()``; points on the last axis) of every rank merged over the global point list
         through the communicator's bootstrap (``scatterer.gather_arrays``).  Ranks driven from one process have none: use
         ``merge``."""
-        values = self.series() if values is None else np.asarray(values)
-        size = int(getattr(comm, "size", 1)) if comm is not None else 1
-        if size == 1:
-            return merge([(self.point_ids, values)], self.npoints)
-        from .scatterer import gather_arrays
+        from .scatterer import comm_size, gather_arrays
 
+        values = self.series() if values is None else np.asarray(values)
+        if comm_size(comm) == 1:
+            return merge([(self.point_ids, values)], self.npoints)
         every = gather_arrays(comm, {"ids": self.point_ids, "values": values}, "gather", "sensors.merge")
         return merge([(z["ids"], z["values"]) for z in every], self.npoints)

@@ -7,14 +7,21 @@ physics through hooks:
   ``_stage_reference(i, t, dt)``        generator: stage ``i`` as the reference's launch sequence
   ``_cell_terms(u_n, v_n, facets)``     generator: the cell part of a fused stage into ``b``, then ``facets()``
   ``_vector_pass(bw, aw, kind)``        the fused stage's vector kernel (csrc/rk4.hpp)
-  ``_source_scalars(t)``                ``(s1, s2)`` of the source facet term at time ``t``
-  ``_source_set`` / ``_absorbing_set``  ``(c1, c2 or None, detJ, dofmap)`` / ``(c, detJ, dofmap)`` of the two facet sets
+  ``_source_scalars(t)``                ``(s1, s2)`` of the scalar source facet term at time ``t``
+  ``_absorbing_set``                    ``(c, detJ, dofmap)`` of the absorbing facet set (set B of the facet launch)
 
-With ``sponge=`` (an absorbing layer, sponge.py) a stage has one more launch, ``_sponge_terms(u_n, v_n)`` over the layer's owned
-dofs: appended to ``facets()`` in the fused stage, after the facet applies in ``_stage_reference``; a solver calls ``_init_sponge``
-in its constructor and ``_bind_sponge(mass)`` at the end of ``setup_schedule``, when its lumped mass is complete.  With
-``point_source=`` (monopoles inside the volume, sources.PointSources) one more again, ``_point_terms(t)`` at the stage's source time, in
-the same two places; a solver calls ``_init_point_source`` in its constructor.
+and, in its constructor, ``_init_source(source, facets, scale, source_set)`` and ``_init_terms(sponge, point_source, point_claim)``;
+at the end of ``setup_schedule``, when its lumped mass is complete, ``_bind_terms(mass)``.
+
+The source-facet term is one SOURCE OBJECT, ``self._facet_source``: ``sources.ScalarFacetSource`` (set A, ``(c1, c2 or None, detJ,
+dofmap)``, with ``_source_scalars``) or the ``sources.BoundSourceArray`` of ``source=``.  It answers ``stage_row(t)`` (the host row of
+a stage time), ``stage_slot(dtype, device)`` (the zeroed [4, width] device tensor a captured step reads) and ``launch(b, field, t=None,
+slot=None)`` (set A with set B in one launch).  What is ADDED to a stage's right-hand side besides is a list of STAGE TERMS,
+``self._terms``: objects with ``bind(solver, mass)``, ``launch(b, u_n, v_n, t)`` and ``capturable`` (``refusal`` says why not).  The
+sponge layer (``sponge=``, sponge.SpongeTerm: one sparse launch over the layer's owned dofs) and the point sources (``point_source=``,
+sources.BoundPointSources: one launch at the stage's source time) are the two, in this order; ``_extra_terms(u_n, v_n, t)`` launches
+them after the facet launch, in ``facets()`` of the fused stage and after the facet applies in ``_stage_reference``.  Relaxation is not
+a stage term: it replaces the stiffness input and adds a pass on either side of the vector pass, so it keeps hooks of its own.
 
 With ``relaxation=`` (power-law absorption through relaxation mechanisms, relaxation.py) every stiffness apply of a stage acts on
 ``self._relax.ur = u_n + sum xi`` in the place of ``u_n`` (``_stiffness_input``; on a partitioned mesh ``ur`` is what travels), and a
@@ -33,9 +40,9 @@ nothing to gain from 1 M dofs up, where consecutive stream launches overlap thei
 launch of a fused step takes fixed device pointers and constants except the source values g(t), dg/dt of the boundary-facet
 terms; with ``fus_facet_terms_dev_*`` those are read from device memory, so the step is captured once
 (``torch.cuda.CUDAGraph`` = hipStreamBeginCapture / hipGraphLaunch) and replayed with one 16-byte-per-stage device copy of
-the step's source values.  A solver with a phased-array source (``self.source``, sources.py) reads a fp64 stage block per
-stage instead (``fus_facet_source_array_dev_*``): ``_sstage`` [4, 6] beside ``_scal``, rewritten before each replay in its
-place.  The reference drives every launch from Python (cuda/demo_linear_box.py:487-566: 12 launches + 5 host syncs per
+the step's source values into ``_stage_slot``.  A solver with a phased-array source (``self.source``, sources.py) reads a fp64
+stage block per stage instead (``fus_facet_source_array_dev_*``): its slot is [4, 6], rewritten before each replay in the
+same way.  The reference drives every launch from Python (cuda/demo_linear_box.py:487-566: 12 launches + 5 host syncs per
 stage); this is its launch-bound regime taken to one graph launch per step.
 """
 
@@ -56,6 +63,8 @@ from .precompute import (
     tabulate_hex_p1_gradients,
 )
 from .recording import rk4_steps  # also for bioheat.py and the tests, which take it from here
+from .sources import ScalarFacetSource
+from .sponge import SpongeTerm
 
 A_RUNGE = (0.0, 0.5, 0.5, 1.0)
 B_RUNGE = (1.0 / 6.0, 1.0 / 3.0, 1.0 / 3.0, 1.0 / 6.0)
@@ -74,28 +83,39 @@ def per_cell(value, mesh, name):
     return np.ascontiguousarray(mesh.permute_cells(a) if hasattr(mesh, "permute_cells") else a)
 
 
+def _to(dev):
+    return lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)
+
+
+def device_facet_detJ(mesh, P, ft, dev, facet_sets, gm=None):
+    """The scaled facet detJ of each of the given boundary_data sets (``(cell, local facet)`` rows), computed on the device;
+    ``gm``: ``(x_dofs, x_g)`` on the device where the caller holds them (the solvers' set-up; ``receivers.ElementReceivers``
+    does not)."""
+    n, td = P + 1, _to(dev)
+    pts, wts, _ = tabulate_1d(P, ft)
+    gm = (td(mesh.x_dofs), td(mesh.x_g)) if gm is None else gm
+    dphi_f, w2 = td(tabulate_facet_gradients(pts, ft)), td(tensor_weights_2d(wts).astype(ft))
+    out = []
+    for bd in facet_sets:
+        dF = torch.zeros((bd.shape[0], n * n), dtype=_lib.torch_dtype(ft), device=dev)
+        if bd.shape[0]:
+            compute_boundary_facets_scaled_jacobian_determinant_device(dF, gm, td(bd.astype(np.int32)), dphi_f, w2)
+        out.append(dF)
+    return out
+
+
 def device_geometry(mesh, P, ft, dev, facet_sets):
     """G, detJ and the facet detJ of the given boundary_data sets, computed on the device
     (csrc/geometry.hpp; the reference does this with numba on the host,
     cuda/demo_linear_box.py:245-317)."""
-    n = P + 1
+    n, td, tdt = P + 1, _to(dev), _lib.torch_dtype(ft)
     pts, wts, D = tabulate_1d(P, ft)
-    td = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)  # noqa: E731
-    tdt = torch.float64 if np.dtype(ft) == np.float64 else torch.float32
-    w3, w2 = td(tensor_weights_3d(wts).astype(ft)), td(tensor_weights_2d(wts).astype(ft))
-    dphi_g = td(tabulate_hex_p1_gradients(tensor_points_3d(pts), ft))
-    dphi_f = td(tabulate_facet_gradients(pts, ft))
     gm = (td(mesh.x_dofs), td(mesh.x_g))
     G = torch.empty((mesh.ncells, n**3, 6), dtype=tdt, device=dev)
     detJ = torch.empty((mesh.ncells, n**3), dtype=tdt, device=dev)
-    compute_scaled_geometrical_factor_device(G, gm, mesh.ncells, dphi_g, w3, detJ=detJ)
-    out = []
-    for bd in facet_sets:
-        dF = torch.zeros((bd.shape[0], n * n), dtype=tdt, device=dev)
-        if bd.shape[0]:
-            compute_boundary_facets_scaled_jacobian_determinant_device(dF, gm, td(bd.astype(np.int32)), dphi_f, w2)
-        out.append(dF)
-    return D, G, detJ, out
+    compute_scaled_geometrical_factor_device(G, gm, mesh.ncells, td(tabulate_hex_p1_gradients(tensor_points_3d(pts), ft)),
+                                             td(tensor_weights_3d(wts).astype(ft)), detJ=detJ)
+    return D, G, detJ, device_facet_detJ(mesh, P, ft, dev, facet_sets, gm)
 
 
 # in_kernel_geometry="auto": from this degree; below it G is not the dominant stream and the kernel form loses (DESIGN 3.2)
@@ -219,37 +239,41 @@ class SpectralSolver3D(MeshSolver3D):
         bd2 = mesh.boundary_facets([getattr(mesh, "absorbing_tag", 3)])
         return (bd1, bd2) + self._init_mesh(mesh, float_type, comm, (bd1, bd2))
 
-    # -- absorbing sponge layer (sponge.py): one sparse launch per stage, placed with the facet terms ----------------------
-    def _init_sponge(self, sponge):
-        """``sponge``: a ``sponge.SpongeLayer`` or None.  Its list of this rank's owned layer dofs is built here (host); its
-        coefficients need the COMPLETE lumped mass, so they are bound at the end of ``setup_schedule`` (``_bind_sponge``)."""
-        self.sponge, self._sponge = sponge, None
-        self._sponge_list = None if sponge is None else sponge.build(self.mesh)
+    # -- the source-facet term: one source object, the scalar waveform or a phased array (sources.py) ----------------------------------
+    def _init_source(self, source, facets, scale, source_set):
+        """``source``: a ``sources.SourceArray`` or None, bound here to this rank's source ``facets`` with the source constant ``scale``
+        (needs ``self.f0``) and set A, ``source_set = (c1, c2 or None, detJ, dofmap)``: ``self.source`` (None without an array).
+        ``self._facet_source`` is what the stages launch either way: that, or the ``ScalarFacetSource`` of ``_source_scalars``."""
+        c1, c2, detJ, dofmap = source_set
+        self.source = None if source is None else source.bind(self.mesh, facets, self.tdt_np, self.dev, frequency=self.f0, scale=scale,
+                                                              coeff1=c1, coeff2=c2, detJ=detJ, dofmap=dofmap)
+        self._facet_source = ScalarFacetSource(source_set, self._source_scalars) if source is None else self.source
 
-    def _bind_sponge(self, mass):
-        if self.sponge is not None:
-            self._sponge = self.sponge.bind(mass, self.tdt, self.dev, built=self._sponge_list)
-
-    def _sponge_terms(self, u_n, v_n):
-        """b[j] -= cv[j] v_n[j] + cu[j] u_n[j] over the layer's owned dofs; nothing without a layer."""
-        if self.sponge is None:
-            return
-        if self._sponge is None:
-            raise _lib.FusGpuError("sponge layer: the set-up exchange (setup_schedule) has not run, the layer is not bound yet")
-        ops.sponge_terms(self.b, u_n, v_n, self._sponge)
-
-    # -- point sources (sources.PointSources): one more launch per stage, placed where the sponge layer's is -----------------------
-    def _init_point_source(self, point_source, point_claim=None):
-        """``point_source``: a ``sources.PointSources`` or None, bound here to the points this rank injects (needs ``self.f0``).
-        ``point_claim``: this rank's row of ``sources.claim_points`` for ranks driven from one process (they have no gather)."""
-        self.point_source = point_source
+    # -- additive stage terms: the sponge layer (sponge.py), then the point sources (sources.PointSources) -----------------------------
+    def _init_terms(self, sponge, point_source, point_claim=None):
+        """``sponge``: a ``sponge.SpongeLayer`` or None.  ``point_source``: a ``sources.PointSources`` or None, bound here to the points
+        this rank injects (needs ``self.f0``); ``point_claim``: this rank's row of ``sources.claim_points`` for ranks driven from one
+        process (they have no gather)."""
+        self.sponge, self.point_source = sponge, point_source
+        self._sponge_term = None if sponge is None else SpongeTerm(sponge, self.mesh)
         self._points = None if point_source is None else point_source.bind(
             self.mesh, self.tdt_np, self.dev, self.f0, comm=self.comm, claim=point_claim)
+        self._terms = [term for term in (self._sponge_term, self._points) if term is not None]
 
-    def _point_terms(self, t):
-        """b[dofmap[c][ijk]] += g_p(t) Lx[i] Ly[j] Lz[k] over this rank's points; nothing without point sources."""
-        if self._points is not None:
-            ops.point_source_terms(self.b, self._points, self._points.stage_scalars(t))
+    @property
+    def _sponge(self):
+        """``(idx, cu, cv)`` of the bound layer; None without one, and until the set-up exchange has run."""
+        return None if self._sponge_term is None else self._sponge_term.bound
+
+    def _bind_terms(self, mass):
+        """At the end of ``setup_schedule``: ``mass``, the solver's assembled lumped mass, is complete only then."""
+        for term in self._terms:
+            term.bind(self, mass)
+
+    def _extra_terms(self, u_n, v_n, t):
+        """The terms' launches of a stage with inputs ``(u_n, v_n)`` and source time ``t`` (None: a capture) into ``b``."""
+        for term in self._terms:
+            term.launch(self.b, u_n, v_n, t)
 
     # -- relaxation mechanisms (relaxation.RelaxationAbsorption): one streaming launch per stage, ur in the place of u_n ---------------
     def _init_relaxation(self, relaxation):
@@ -309,50 +333,24 @@ class SpectralSolver3D(MeshSolver3D):
         return B_RUNGE[i] * dt, 0.0 if last else A_RUNGE[i + 1] * dt, 3 if last else (2 if i == 0 else 0)
 
     # -- fused stage: the cell pass with the facet terms in one launch, then one vector pass -------------------------------
-    def _operator_fused(self, t, u_n, v_n, scalars=None, stage_dev=None):
+    def _operator_fused(self, t, u_n, v_n, slot=None):
         """b += the cell terms of (u_n, v_n) + the facet terms of the source at time ``t`` and M_f2(c) v_n, in one facet
-        launch.  ``scalars``: device tensor the source values are read from instead of being evaluated at ``t`` (graph
-        capture); ``stage_dev``: the same for a phased-array source (its fp64 stage block)."""
-        field = (v_n,) + self._absorbing_set
-        if self.source is not None:  # M_f1(g_e c1 [+ dg_e c2]) 1 per element + M_f2(c) v_n
-            stage = None if stage_dev is not None else self.source.stage_scalars(t)
-
-            def facets():
-                ops.facet_source_terms(self.b, self.source, field, stage=stage, stage_dev=stage_dev)
-        else:  # M_f1(s1 c1 [+ s2 c2]) 1 + M_f2(c) v_n (the reference fills g into a vector)
-            c1, c2, detJ, dofmap = self._source_set
-            s1, s2 = (0.0, 0.0) if scalars is not None else self._source_scalars(t)
-
-            def facets():
-                ops.facet_terms(self.b, (c1, s1, c2, s2, detJ, dofmap), field, scalars=scalars)
-
-        if self.sponge is not None:  # the layer's launch follows the facet launch wherever a schedule (or a capture) places that
-            facet_launch = facets
-
-            def facets():
-                facet_launch()
-                self._sponge_terms(u_n, v_n)
-
-        if self._points is not None:  # ... and the point sources' launch: before the reverse scatter of b (a point's cell may hold ghost dofs)
-            if t is None:
-                raise _lib.FusGpuError("point sources take their stage time from the host: a step with a point source cannot be captured")
-            before_points = facets
-
-            def facets():
-                before_points()
-                self._point_terms(t)
+        launch, + the additive terms.  ``slot`` (graph capture, ``t`` is None): the device row the source's kernel reads its
+        stage values from instead of their being evaluated at ``t``."""
+        def facets():  # wherever a schedule (or a capture) places the facet launch, the terms' launches follow it
+            self._facet_source.launch(self.b, (v_n,) + self._absorbing_set, t=t, slot=slot)
+            self._extra_terms(u_n, v_n, t)
 
         yield from self._cell_terms(self._stiffness_input(u_n), v_n, facets)
 
     def _fused_step(self, t, dt):
         """The 8 launches of one fused RK4 step from ``t``: the first stage reads (u0, v0) themselves, the others the stage
         buffers (un, ku == v_n).  ``t=None`` (graph capture): every argument is a fixed pointer or a constant, the source
-        values of stage ``i`` are read from ``self._scal[i]`` (a phased-array source: its stage block from ``self._sstage[i]``)."""
+        values of stage ``i`` are read from ``self._stage_slot[i]``."""
         for i in range(4):
             u_n, v_n = (self.u0, self.v0) if i == 0 else (self.un, self.ku)
             if t is None:
-                yield from self._operator_fused(None, u_n, v_n, scalars=self._scal[i],
-                                                stage_dev=self._sstage[i] if self.source is not None else None)
+                yield from self._operator_fused(None, u_n, v_n, slot=self._stage_slot[i])
             else:
                 yield from self._operator_fused(self._stage_time(t, i, dt), u_n, v_n)
             if self.relaxation is not None and i < 3:  # before the vector pass overwrites the stage's v_n (and, lean stage 3, u0)
@@ -389,7 +387,7 @@ class SpectralSolver3D(MeshSolver3D):
         self.check_halo_health(f"{type(self).__name__}.rk4")
         return result
 
-    def _recording(self, sensors, monitor, start_time, final_time, dt, max_steps, record_from, receivers=None):
+    def _recording(self, start_time, final_time, dt, max_steps, record_from, sensors, monitor, receivers):
         """Plan the recorders for this ``rk4`` call (``expect_steps``) and return ``record(t)``: the generator that records what is
         due after a step ending at ``t``.  On a partitioned mesh the ghost entries of the field are not current after a step: the
         forward exchange the sensors and the receivers read after is posted first -- once, if either is due -- with a ``yield`` after
@@ -426,7 +424,7 @@ class SpectralSolver3D(MeshSolver3D):
         field first, with a yield) or, over every owned dof, through ``monitor`` (no exchange, no yield)."""
         t, step = float(start_time), 0
         self._check_relaxation_step(dt)
-        record = self._recording(sensors, monitor, t, final_time, dt, max_steps, record_from, receivers)
+        record = self._recording(t, final_time, dt, max_steps, record_from, sensors, monitor, receivers)
         if self.fused:
             self._fused_enter()
         elif self.relaxation is not None:
@@ -487,31 +485,25 @@ class SpectralSolver3D(MeshSolver3D):
         stage block for them does not exist yet): ``FusGpuError``.  Returns ``(t, steps)``."""
         if not self.fused or self.halo is not None:
             raise _lib.FusGpuError("rk4_graph: single-rank fused path only")
-        if self._points is not None:
-            raise _lib.FusGpuError("rk4_graph: a solver with point_source= cannot be replayed from a captured graph (the point sources' "
-                                   "stage time is a host argument of their launch): use rk4")
+        for term in self._terms:
+            if not term.capturable:
+                raise _lib.FusGpuError(f"rk4_graph: {term.refusal}: use rk4")
         self._check_relaxation_step(dt)
         t, tf = float(start_time), float(final_time)
         rows, ends = [], []
-        record = self._recording(sensors, monitor, t, tf, dt, max_steps, record_from, receivers)
-        src = self.source
+        record = self._recording(t, tf, dt, max_steps, record_from, sensors, monitor, receivers)
         for t0, h in rk4_steps(t, tf, dt, max_steps):
             if h != dt:
                 break
-            ts = [self._stage_time(t0, i, dt) for i in range(4)]
-            rows.append([self._source_scalars(x) for x in ts] if src is None else [src.stage_scalars(x) for x in ts])
+            rows.append([self._facet_source.stage_row(self._stage_time(t0, i, dt)) for i in range(4)])
             t = t0 + h
             ends.append(t)
         if rows:
             if not hasattr(self, "_graphs"):
                 self._graphs = {}
-                self._scal = torch.zeros((4, 2), dtype=self.tdt, device=self.dev)
-                if src is not None:
-                    self._sstage = torch.zeros((4, len(rows[0][0])), dtype=torch.float64, device=self.dev)
-            if src is None:
-                table, slot = torch.from_numpy(np.asarray(rows, dtype=np.float64).astype(self.tdt_np)).to(self.dev), self._scal
-            else:  # the stage blocks stay fp64 for fp32 fields too
-                table, slot = torch.from_numpy(np.asarray(rows, dtype=np.float64)).to(self.dev), self._sstage
+                self._stage_slot = self._facet_source.stage_slot(self.tdt, self.dev)
+            slot = self._stage_slot
+            table = torch.from_numpy(np.asarray(rows, dtype=np.float64)).to(slot.dtype).to(self.dev)  # rounded on the host
             graph = self._step_graph(dt)
             self._fused_enter()
             for k in range(len(rows)):

@@ -25,6 +25,9 @@ from dataclasses import dataclass
 
 import numpy as np
 
+from . import _lib
+from . import operators as ops
+
 ALPHA = 4.0  # ramp length in periods (linear_solver.source_value, nonlinear_solver.source_values)
 STAGE_WORDS = 6  # t, w0, A, f0, alpha, D  (csrc/source_array.hpp SourceStage)
 
@@ -202,6 +205,39 @@ class BoundSourceArray:
     def stage_scalars(self, t):
         return self.array.stage_scalars(t, self.frequency, self.scale)
 
+    # -- the source object of a solver (``ScalarFacetSource`` is the other) ----------------------
+    stage_row = stage_scalars
+
+    def stage_slot(self, dtype, device):
+        """The stage blocks of the four stages of a captured step: fp64 for fp32 fields too."""
+        import torch
+
+        return torch.zeros((4, STAGE_WORDS), dtype=torch.float64, device=device)
+
+    def launch(self, b, field, t=None, slot=None):
+        ops.facet_source_terms(b, self, field, stage=None if slot is not None else self.stage_scalars(t), stage_dev=slot)
+
+
+class ScalarFacetSource:
+    """The solvers' one waveform on the source facets as a source object: what a solver asks of its source is the host row of a stage
+    time (``stage_row(t)``), the zeroed device tensor [4, width] a captured step reads its four rows from (``stage_slot``), and the
+    facet launch of set A together with set B (``launch(b, field, t=None, slot=None)``: the row evaluated at ``t``, or read by the
+    kernel from ``slot``, one stage's row of the slot tensor; ``field`` = set B or None).  ``source_set``: set A, ``(c1, c2 or
+    None, detJ, dofmap)``; ``scalars``: the solver's ``_source_scalars``, ``t -> (s1, s2)``."""
+
+    def __init__(self, source_set, scalars):
+        self.source_set, self.stage_row = source_set, scalars
+
+    def stage_slot(self, dtype, device):
+        import torch
+
+        return torch.zeros((4, 2), dtype=dtype, device=device)
+
+    def launch(self, b, field, t=None, slot=None):
+        c1, c2, detJ, dofmap = self.source_set
+        s1, s2 = (0.0, 0.0) if slot is not None else self.stage_row(t)
+        ops.facet_terms(b, (c1, s1, c2, s2, detJ, dofmap), field, scalars=slot)
+
 
 # -- point sources -----------------------------------------------------------------------------
 class PointSources:
@@ -255,19 +291,17 @@ class PointSources:
         import torch
 
         from . import _lib
+        from .scatterer import comm_size, gather_arrays
 
         self.check_duration(frequency)
         su = setup if setup is not None else self.setup(mesh, locator)
-        size = int(getattr(comm, "size", 1)) if comm is not None else 1
         if claim is None:
-            if size == 1:
+            if comm_size(comm) == 1:
                 if su.point_ids.size != self.npoints:
                     lost = np.setdiff1d(np.arange(self.npoints), su.point_ids)
                     raise ValueError(f"point source(s) {lost.tolist()} lie outside the mesh")
                 claim = np.ones(self.npoints, dtype=bool)
             else:
-                from .scatterer import gather_arrays
-
                 every = gather_arrays(comm, {"ids": su.point_ids}, "PointSources.bind", "claim=claim_points(setups, npoints)[rank]")
                 claim = claim_points([z["ids"] for z in every], self.npoints)[int(comm.rank)]
         claim = np.asarray(claim, dtype=bool)
@@ -326,6 +360,21 @@ class BoundPointSources:
     def stage_scalars(self, t):
         """The fp64 stage block ``{t, w0, A = 1, f0, alpha, D}`` of the kernel."""
         return self.sources.stage_scalars(t, self.frequency, 1.0)
+
+    # -- a stage term of a solver (solver_base): placed after the facet launch, before the reverse scatter of b (a point's cell may
+    # hold ghost dofs) ----------------------------------------------------------------------------
+    capturable = False
+    refusal = ("a solver with point_source= cannot be replayed from a captured graph (the point sources' "
+               "stage time is a host argument of their launch)")
+
+    def bind(self, solver, mass):
+        pass  # bound where the solver was constructed: nothing here waits for the mass
+
+    def launch(self, b, u_n, v_n, t):
+        """b[dofmap[c][ijk]] += g_p(t) Lx[i] Ly[j] Lz[k] over this rank's points."""
+        if t is None:
+            raise _lib.FusGpuError("point sources take their stage time from the host: a step with a point source cannot be captured")
+        ops.point_source_terms(b, self, self.stage_scalars(t))
 
 
 # -- geometry helpers --------------------------------------------------------------------------

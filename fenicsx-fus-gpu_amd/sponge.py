@@ -29,6 +29,7 @@ import numpy as np
 import torch
 
 from . import _lib
+from . import operators as ops
 
 # faces of the box by name -> (axis, side); LATERAL: the four faces the reference leaves rigid around its x-directed beam
 FACES = {"-x": (0, 0), "+x": (0, 1), "-y": (1, 0), "+y": (1, 1), "-z": (2, 0), "+z": (2, 1)}
@@ -122,3 +123,23 @@ class SpongeLayer:
         cv = ((2.0 * sig_d) * m).to(dtype).contiguous()
         cu = ((sig_d * sig_d) * m).to(dtype).contiguous()
         return idx_d, cu, cv
+
+
+class SpongeTerm:
+    """A ``SpongeLayer`` as a stage term of one solver (solver_base): its list of the rank's owned layer dofs is built at construction
+    (host); its coefficients need the COMPLETE lumped mass, so ``bound`` -- ``(idx, cu, cv)`` -- stays None until the solver's set-up
+    exchange has run.  Every argument of the launch is a fixed pointer: a captured step replays it."""
+
+    capturable = True
+
+    def __init__(self, layer, mesh):
+        self.layer, self.built, self.bound = layer, layer.build(mesh), None
+
+    def bind(self, solver, mass):
+        self.bound = self.layer.bind(mass, solver.tdt, solver.dev, built=self.built)
+
+    def launch(self, b, u_n, v_n, t):
+        """b[j] -= cv[j] v_n[j] + cu[j] u_n[j] over the layer's owned dofs."""
+        if self.bound is None:
+            raise _lib.FusGpuError("sponge layer: the set-up exchange (setup_schedule) has not run, the layer is not bound yet")
+        ops.sponge_terms(b, u_n, v_n, self.bound)
