@@ -24,6 +24,9 @@ EXTENSION_HEADER_PATHS = (os.path.join(os.path.dirname(_HERE), "include", "fus_g
 # ... and the headers added since THAT set was pinned in its turn (tests/test_point_sources.py pins EXTENSIONS to fus_gpu_array.h's four
 # functions): every later extension header goes here, its functions into ADDITIONS
 ADDITION_HEADER_PATHS = (os.path.join(os.path.dirname(_HERE), "include", "fus_gpu_relaxation.h"),)
+# ... and, ADDITIONS being pinned too (tests/test_relaxation.py), the open tier: the path of EVERY later header is appended here, its
+# functions land in LATER, and no test pins that set to what it holds today
+LATER_HEADER_PATHS = (os.path.join(os.path.dirname(_HERE), "include", "fus_gpu_nodal.h"),)
 
 
 class FusGpuError(RuntimeError):
@@ -90,6 +93,22 @@ ADDITIONS = {name: decl for path in ADDITION_HEADER_PATHS for name, decl in _rea
 if set(ADDITIONS) & (set(EXTENSIONS) | set(DECLARATIONS)):
     raise FusGpuError(f"declared in two headers of the C ABI: {sorted(set(ADDITIONS) & (set(EXTENSIONS) | set(DECLARATIONS)))}")
 
+
+def declared_later(paths, earlier):
+    """{name: (restype, [argtypes])} of the functions the headers at ``paths`` declare; a name that ``earlier`` (the names of the
+    tiers before) or a header before it in ``paths`` holds already is refused."""
+    tier = {}
+    for path in paths:
+        functions = _read_header(path)[0]
+        twice = set(functions) & (set(earlier) | set(tier))
+        if twice:
+            raise FusGpuError(f"declared in two headers of the C ABI: {sorted(twice)} ({path})")
+        tier.update(functions)
+    return tier
+
+
+LATER = declared_later(LATER_HEADER_PATHS, set(DECLARATIONS) | set(EXTENSIONS) | set(ADDITIONS))
+
 ABI_VERSION = _DEFINES["FUS_ABI_VERSION"]
 ERR_COMM = _DEFINES["FUS_ERR_COMM"]
 ERR_UNSUPPORTED_ENTITY = _DEFINES["FUS_ERR_UNSUPPORTED_ENTITY"]
@@ -112,7 +131,7 @@ _lib = None
 def bind(cdll):
     """Set ``argtypes`` and ``restype`` of every declared function (include/fus_gpu.h and its extension headers) on a loaded library;
     AttributeError if it lacks one."""
-    for name, (restype, argtypes) in {**DECLARATIONS, **EXTENSIONS, **ADDITIONS}.items():
+    for name, (restype, argtypes) in {**DECLARATIONS, **EXTENSIONS, **ADDITIONS, **LATER}.items():
         fn = getattr(cdll, name)
         fn.argtypes, fn.restype = argtypes, restype
     return cdll

@@ -5,6 +5,7 @@
 #include "../../include/fus_gpu.h"
 #include "../../include/fus_gpu_array.h"
 #include "../../include/fus_gpu_relaxation.h"
+#include "../../include/fus_gpu_nodal.h"
 
 #include <hip/hip_runtime.h>
 
@@ -619,6 +620,11 @@ int fus_plan_mark_exclusive(void* workspace, int N, int entities_per_batch, int6
   int fus_stiffness_apply_planned_geom_##SUF(const T* x, const T* cc, T* y, const T* x_g, const int32_t* x_dofs, const T* pts,             \
                                              const T* wts, const void* ws, const T* dphi, int P, int64_t ncell, void* s) {                 \
     return stiffness_apply_planned_geom<T>(x, cc, y, x_g, x_dofs, pts, wts, ws, dphi, P, ncell, s);                                        \
+  }                                                                                                                                        \
+  int fus_stiffness_apply_planned_geom_nodal_##SUF(const T* x, const T* cc, const T* nodal, T* y, const T* x_g, const int32_t* x_dofs,    \
+                                                   const T* pts, const T* wts, const void* ws, const T* dphi, int P, int64_t ncell,        \
+                                                   void* s) {                                                                              \
+    return stiffness_apply_planned_geom_nodal<T>(x, cc, nodal, y, x_g, x_dofs, pts, wts, ws, dphi, P, ncell, s);                           \
   }                                                                                                                                        \
   int fus_gradient_apply_planned_geom_##SUF(const T* x, const T* cc, T* y, int64_t ystride, const T* x_g, const int32_t* x_dofs,           \
                                             const T* pts, const T* wts, const void* ws, const T* dphi, int P, int64_t ncell, void* s) {    \

@@ -9,6 +9,7 @@ replaces dolfinx's ``create_box``.
     python fenicsx-fus-gpu_amd/demo_linear_box.py --array 8,8 --focus 0.06,0.05,0.06     # phased array focused on a point
     python fenicsx-fus-gpu_amd/demo_linear_box.py --length 0.012 --cells 8 --time-reversal 0.011 0.0063 0.0058 --elements 3 3
                                                    # listen to a virtual source at the focus through an aberrating slab, fire back
+    python fenicsx-fus-gpu_amd/demo_linear_box.py --nodal-lens                             # c and rho given at the dofs: a smooth inclusion
     python -m torch.distributed.run --nproc-per-node 8 fenicsx-fus-gpu_amd/demo_linear_box.py   # one rank per GPU
 
 Prints the reference's progress / timing lines (cuda/demo_linear_box.py:125,183,569-581) and
@@ -57,10 +58,16 @@ def main():
                          "focus (sources.PointSources, receivers.ElementReceivers), then transmit runs with the conjugate phases "
                          "(receivers.time_reversal) and with the geometric ones (sources.focus_phases); prints the first-harmonic "
                          "amplitude at the focus of both.  One rank; composes with --sponge")
+    ap.add_argument("--nodal-lens", action="store_true",
+                    help="a nodal medium (nodal_medium.NodalMedium): c and rho given at the dofs, not per cell -- a smooth Gaussian inclusion "
+                         "(c 1500 -> 1800 m/s, rho 1000 -> 1200 kg/m^3, radius L/6) at the centre of the box; the stiffness apply takes 1/rho "
+                         "inside its contraction (csrc/stiffness_geom_nodal.hpp).  Composes with --sponge, --array, --power-law and ranks")
     ap.add_argument("--elements", type=int, nargs=2, default=(4, 4), metavar=("NY", "NZ"), help="elements of the --time-reversal array (default 4 4)")
     a = ap.parse_args()
     if a.focus and not a.array:
         ap.error("--focus needs --array")
+    if a.time_reversal and a.nodal_lens:
+        ap.error("--time-reversal builds its own (per-cell) medium")
     if a.time_reversal and (a.array or int(os.environ.get("WORLD_SIZE", "1")) > 1):
         ap.error("--time-reversal runs on one rank and builds its own array (--elements)")
 
@@ -86,12 +93,20 @@ def main():
     num_element = a.cells if a.cells is not None else int(2 * domain_length / wave_length)
     grid = boxmesh.default_grid(world)
     mesh = boxmesh.BoxMesh(a.degree, num_element, grid=grid, rank=rank, length=domain_length, dtype=float_type)
+    medium = None
+    if a.nodal_lens:
+        # callables of position: every rank evaluates them at its own dofs, ghosts included, so the values agree across ranks
+        centre, r2 = 0.5 * np.asarray(mesh.length), (domain_length / 6.0) ** 2
+        bump = lambda xyz: np.exp(-np.sum((xyz - centre) ** 2, axis=1) / r2)  # noqa: E731
+        medium = fusgpu_loader.submodule("nodal_medium").NodalMedium(lambda xyz: speed_of_sound + 300.0 * bump(xyz),
+                                                                     lambda xyz: density + 200.0 * bump(xyz))
+    # (the time-step rule takes the fastest speed of the medium)
     h = ls.time_step_parameters(mesh, a.degree, speed_of_sound, source_frequency, domain_length)
     if world > 1:
         hm = torch.tensor([h], dtype=torch.float64, device="cuda")
         dist.all_reduce(hm, op=dist.ReduceOp.MIN)  # comm.Allreduce(hmin, mesh_size, op=MPI.MIN), :108
         h = float(hm.item())
-    dt, tf, nstep = ls.snap_time_step(h, a.degree, speed_of_sound, source_frequency, domain_length)
+    dt, tf, nstep = ls.snap_time_step(h, a.degree, speed_of_sound + (300.0 if a.nodal_lens else 0.0), source_frequency, domain_length)
     if rank == 0:
         print(f"Number of steps: {nstep}", flush=True)
         print(f"Number of degrees-of-freedom: {mesh.ndofs_global}", flush=True)
@@ -133,8 +148,12 @@ def main():
             raise SystemExit("--power-law does not compose with --time-reversal")
         return time_reversal_run(a, mesh, sponge, float_type, speed_of_sound, density, source_frequency, source_amplitude)
     solver = ls.LinearSpectral3D(mesh, float_type, speed_of_sound, density, source_frequency, source_amplitude,
-                                 comm=comm, fused=not a.reference_sequence, source=source, sponge=sponge, relaxation=relaxation)
+                                 comm=comm, fused=not a.reference_sequence, source=source, sponge=sponge, relaxation=relaxation,
+                                 nodal_medium=medium)
     solver.init()
+    if medium is not None and rank == 0:
+        print(f"Nodal medium: c {solver.c_nodal.min():.1f} .. {solver.c_nodal.max():.1f} m/s, rho {solver.rho_nodal.min():.1f} .. "
+              f"{solver.rho_nodal.max():.1f} kg/m^3 at the dofs; reference speed of the source {solver.c0:.1f} m/s", flush=True)
     if sponge is not None:
         n_layer = solver._sponge[0].numel()
         print(f"Sponge layer (rank {rank}): {a.sponge} cell(s) wide, {n_layer} owned dofs, sigma_max dt = {sponge.sigma_max * dt:.3f}", flush=True)

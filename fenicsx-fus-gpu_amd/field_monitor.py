@@ -210,7 +210,8 @@ def heat_deposition_schedule(monitor, solver):
 def heat_deposition(monitor, solver):
     """The absorbed power density ``q = M(kappa) <v^2> / M(1) 1`` with ``kappa = delta / (rho c^4)`` per cell: the lumped-mass
     projection of ``kappa <(dp/dt)^2>``, well defined where the materials jump between cells (with GLL collocation
-    ``M(kappa) x = diag(M(kappa) 1) x``).  Device tensor [nlocal], fp64."""
+    ``M(kappa) x = diag(M(kappa) 1) x``).  A solver with a nodal medium (``nodal_medium=``) keeps the per-cell MEANS of its nodal
+    rho and c in ``rho_cells`` / ``c_cells``: those are the values seen here.  Device tensor [nlocal], fp64."""
     from .solver_base import run_schedule
 
     return run_schedule(heat_deposition_schedule(monitor, solver))

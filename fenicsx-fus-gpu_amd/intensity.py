@@ -131,7 +131,8 @@ def particle_velocity_schedule(monitor, solver, k):
 def particle_velocity(monitor, solver, k):
     """``(re, im)``, each ``[3, nlocal]`` fp64, of the particle velocity amplitude of the monitor's k-th harmonic:
     ``V_k = i grad(P_k) / (k w rho)`` (from ``rho dv/dt = -grad p`` with ``e^{i k w t}``), ``1 / rho`` per cell as the gradient
-    operator's cell constant."""
+    operator's cell constant (``solver.rho_cells``; of a solver with a nodal medium the per-cell mean of its nodal rho: exact nodal
+    rho here is out of scope)."""
     from .solver_base import run_schedule
 
     return run_schedule(particle_velocity_schedule(monitor, solver, k))

@@ -55,7 +55,7 @@ class LinearSpectral3D(SpectralSolver3D):
                  source_frequency=0.5e6, source_amplitude=60000.0, comm=None, fused=True,
                  source_time="tn", overlap=True, halo_kernels=None, affine="auto", in_kernel_geometry="auto",
                  halo_plan=None, defer_setup_exchange=False, reference_speed_of_sound=None, keep_G=False, source=None,
-                 sponge=None, point_source=None, point_claim=None, relaxation=None):
+                 sponge=None, point_source=None, point_claim=None, relaxation=None, nodal_medium=None):
         """``speed_of_sound`` / ``density``: scalars, or one value per cell (heterogeneous medium: the DG0 material arrays of
         the reference's drivers, in the caller's cell order).  ``reference_speed_of_sound``: the c of the source term
         ``p0 w0 / c cos(w0 t)`` (cuda/demo_linear_box.py:515-530 uses the scalar of its homogeneous medium); default: the
@@ -76,8 +76,30 @@ class LinearSpectral3D(SpectralSolver3D):
         ``halo_plan``); ranks in different processes agree through one gather.  ``relaxation``: a
         ``relaxation.RelaxationAbsorption`` (power-law absorption: memory variables xi' = kappa v - xi / tau per mechanism, the stiffness
         apply acts on u_n + sum xi, one streaming launch per stage); ``speed_of_sound`` is then the EQUILIBRIUM (low-frequency) speed,
-        the phase speed rises with frequency (``RelaxationAbsorption.phase_speed``).  ``None`` keeps every launch as it is."""
-        c_cells, rho_cells = per_cell(speed_of_sound, mesh, "speed_of_sound"), per_cell(density, mesh, "density")
+        the phase speed rises with frequency (``RelaxationAbsorption.phase_speed``).  ``None`` keeps every launch as it is.
+        ``nodal_medium``: a ``nodal_medium.NodalMedium`` -- c and rho at the DOFS (n times finer per axis than one value per cell, on
+        the same mesh) in place of ``speed_of_sound`` / ``density``, which must then be left scalar (arrays raise).  The stiffness
+        apply takes 1/rho inside its contraction (the nodal kernel with the geometry formed in the kernel, at every degree and on
+        affine boxes too; ``in_kernel_geometry=False``: the general kernel on a G array scaled once; ``affine=True`` raises); the
+        lumped mass is ``(M(1) 1, reverse-scattered) * 1/(rho c^2)``.  The facet terms keep ONE coefficient per facet, the mean of
+        the nodal coefficient (1/rho on the source facets, 1/(rho c) on the absorbing ones) over that facet's dofs: exact where the
+        medium is constant on a boundary facet, and the source and absorbing faces are expected to lie in the coupling medium.
+        ``rho_nodal`` / ``c_nodal`` hold the fields (host, float64, local dofs); ``rho_cells`` / ``c_cells`` the per-cell MEANS of the
+        nodal values, which is what ``intensity.py``, ``field_monitor.heat_deposition`` and per-cell relaxation weights then see.
+        ``reference_speed_of_sound`` defaults to the mean of c over the dofs of the source facets.  ``None`` keeps every launch as it
+        is."""
+        self.nodal_medium, self.c_nodal, self.rho_nodal = nodal_medium, None, None
+        if nodal_medium is not None:
+            if np.ndim(speed_of_sound) != 0 or np.ndim(density) != 0:
+                raise ValueError("nodal_medium= together with speed_of_sound= / density= arrays: the nodal medium is the medium, "
+                                 "leave the two per-cell arguments scalar")
+            from .nodal_medium import cell_means, facet_means
+
+            self.c_nodal, self.rho_nodal = nodal_medium.evaluate(mesh)
+            speed_of_sound, density = cell_means(self.c_nodal, mesh.dofmap), cell_means(self.rho_nodal, mesh.dofmap)
+            c_cells, rho_cells = speed_of_sound, density  # already in the mesh's cell order
+        else:
+            c_cells, rho_cells = per_cell(speed_of_sound, mesh, "speed_of_sound"), per_cell(density, mesh, "density")
         bd1, bd2, D, G_d, detJ_d, (dF1_d, dF2_d) = self._init_common(mesh, float_type, comm, fused, source_time)
         self._init_relaxation(relaxation)
         self.c0, self.rho0 = float(c_cells.mean()), float(rho_cells.mean())
@@ -90,18 +112,31 @@ class LinearSpectral3D(SpectralSolver3D):
         rho, c = rho_cells.astype(ft), c_cells.astype(ft)
         if reference_speed_of_sound is not None:
             self.c0 = float(reference_speed_of_sound)
+        elif nodal_medium is not None:
+            if bd1.shape[0]:
+                self.c0 = float(self.c_nodal[mesh.facet_dofmap(bd1)].mean())
         elif np.ndim(speed_of_sound) == 0:
             self.c0 = float(speed_of_sound)
         elif bd1.shape[0]:
             self.c0 = float(c_cells[bd1[:, 0]].mean())
         td = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)  # noqa: E731
-        self.cell_coeff1 = td(1.0 / rho / c / c)  # :336
-        self.cell_coeff2 = td(-1.0 / rho)  # :337
-        self.facet_coeff1 = td((1.0 / rho[bd1[:, 0]]).astype(ft))  # :339-341
-        self.facet_coeff2 = td((-1.0 / rho[bd2[:, 0]] / c[bd2[:, 0]]).astype(ft))  # :343-345
+        fd1, fd2 = mesh.facet_dofmap(bd1), mesh.facet_dofmap(bd2)
+        if nodal_medium is None:
+            self.cell_coeff1 = td(1.0 / rho / c / c)  # :336
+            self.cell_coeff2 = td(-1.0 / rho)  # :337
+            self.facet_coeff1 = td((1.0 / rho[bd1[:, 0]]).astype(ft))  # :339-341
+            self.facet_coeff2 = td((-1.0 / rho[bd2[:, 0]] / c[bd2[:, 0]]).astype(ft))  # :343-345
+            kappa = None
+        else:  # the medium sits in the operators' nodal factors: unit cell constants (-1 for the stiffness), one mean per facet
+            self.cell_coeff1 = td(np.ones(mesh.ncells, dtype=ft))
+            self.cell_coeff2 = td(np.full(mesh.ncells, -1.0, dtype=ft))
+            self.facet_coeff1 = td(facet_means(1.0 / self.rho_nodal, fd1).astype(ft))
+            self.facet_coeff2 = td((-facet_means(1.0 / (self.rho_nodal * self.c_nodal), fd2)).astype(ft))
+            kappa = (1.0 / self.rho_nodal).astype(ft)
+            self._mass_factor = td((1.0 / (self.rho_nodal * self.c_nodal**2)).astype(ft))  # the diagonal of the lumped mass
         self.G, self.detJ, self.dofmap = G_d, detJ_d, td(mesh.dofmap)
         self.detJ_f1, self.detJ_f2 = dF1_d, dF2_d
-        self.fdm1, self.fdm2 = td(mesh.facet_dofmap(bd1)), td(mesh.facet_dofmap(bd2))
+        self.fdm1, self.fdm2 = td(fd1), td(fd2)
         # the fused stage's facet sets: M_f1(g c1) 1 with g = source_value(t) -- or, with a phased-array source (sources.py), through
         # fus_facet_source_array_* with g = p0 w0 / c0 per element -- and M_f2(c2) v_n
         self._init_source(source, bd1, self.p0 * self.w0 / self.c0, (self.facet_coeff1, None, self.detJ_f1, self.fdm1))
@@ -109,7 +144,7 @@ class LinearSpectral3D(SpectralSolver3D):
 
         # ---- operators and halo ---------------------------------------------------------------------
         self.stiff, self.G, self.affine, self.in_kernel_geometry, self.G_array = stiffness_form(
-            mesh, P, D, G_d, ft, affine, in_kernel_geometry, keep_G)
+            mesh, P, D, G_d, ft, affine, in_kernel_geometry, keep_G, nodal=kappa)
         del G_d
         if self.in_kernel_geometry:
             self.x_dofs = self.G
@@ -128,7 +163,7 @@ class LinearSpectral3D(SpectralSolver3D):
         self.un, self.vn, self.ku, self.kv = z(), z(), z(), z()
         self.u_n, self.v_n, self.g, self.b, self.m = z(), z(), z(), z(), z()
 
-        # ---- lumped mass: m = M(1/(rho c^2)) 1, reverse-scattered (:421-428) ---------------------
+        # ---- lumped mass: m = M(1/(rho c^2)) 1, reverse-scattered (:421-428); a nodal medium: M(1) 1, its factor after the exchange
         ops.fill(1.0, self.g)
         # the default operator (atomic-free, bitwise reproducible): nothing else adds into m while it runs -- the reverse scatter
         # of m follows it in stream order
@@ -141,6 +176,8 @@ class LinearSpectral3D(SpectralSolver3D):
         """Generator: post the set-up exchange (reverse scatter of the lumped mass), yield, complete it and
         form 1/m.  One rank per process exhausts it in the constructor."""
         yield from self._reverse_setup([self.m])
+        if self.nodal_medium is not None:  # m = (M(1) 1, assembled) * 1/(rho c^2): one pointwise product over the owned dofs
+            self.m[: self.nlocal].mul_(self._mass_factor[: self.nlocal])
         ops.fill(1.0, self.minv)
         ops.pointwise_divide(self.minv, self.m, self.minv)  # owned entries are what the fused kernel reads
         self._bind_terms(self.m)  # m is complete only now

@@ -840,9 +840,13 @@ class _CellOperator:
 class _StiffnessOperator(_CellOperator, _Launchable):
     """Returned by ``stiffness_operator``; callable both ways."""
 
-    def __init__(self, P: int, float_type, dphi=None, affine_weights=None, geometry=None):
+    def __init__(self, P: int, float_type, dphi=None, affine_weights=None, geometry=None, nodal=None):
+        if nodal is not None and geometry is None:  # (before anything is put on a device)
+            raise ValueError("stiffness_operator(nodal=...) needs geometry=(x_dofs, x_g, pts, wts): the nodal kernel forms G from the "
+                             "cell vertices.  For the general-G kernels scale the array once, nodal_medium.scale_G(G, kappa, dofmap), "
+                             "and apply the plain operator to it")
         super().__init__(P, float_type, dphi)
-        self._fn = self._entry("stiffness_apply")
+        self._fn =self._entry("stiffness_apply")
         self._fn_planned = self._entry("stiffness_apply_planned")
         self._dphi_src = None
         # opt-in affine-cell fast path: tensor quadrature weights [n^3] of the rule G was built with
@@ -859,6 +863,13 @@ class _StiffnessOperator(_CellOperator, _Launchable):
         if geometry is not None:
             self._geom = (self._check_x_dofs(_to_device(geometry[0], torch.int32), None),) + self._geometry(*geometry[1:])
             self._fn_geom = self._entry("stiffness_apply_planned_geom")
+        # opt-in nodal coefficient (in-kernel geometry only): kappa in the dof numbering of x, held by the operator, so that the call
+        # surface stays op(x, cell_constants, y, G, dofmap) -- cell_constants a further factor per cell -- and a cell sub-range of a
+        # halo schedule, which slices the per-cell tensors and passes x whole, needs nothing new
+        self.nodal = None
+        if nodal is not None:
+            self.nodal = _to_device(nodal, self.dtype).reshape(-1)
+            self._fn_nodal = self._entry("stiffness_apply_planned_geom_nodal")
 
     def _apply(self, x, cell_constants, y, G, dofmap, dphi_t):
         ncell, nd = self._check(dofmap, (("cell_constants", cell_constants),), (("x", x), ("y", y)))
@@ -871,11 +882,19 @@ class _StiffnessOperator(_CellOperator, _Launchable):
             if isinstance(G, torch.Tensor) and G.dtype == torch.int32:
                 xd = G
             self._check_x_dofs(xd, ncell)
+            if self.nodal is not None and (self.nodal.numel() != x.numel() or self.nodal.device != x.device):
+                raise ValueError(f"the operator's nodal coefficient has {self.nodal.numel()} entries on {self.nodal.device}, "
+                                 f"x has {x.numel()} on {x.device}: one value per dof of x")
         if ncell == 0:
             return
         head = (x.data_ptr(), cell_constants.data_ptr(), y.data_ptr())
         tail = (dphi_t.data_ptr(), self.P, int(ncell), _lib.stream_ptr())
-        if self._geom is not None:
+        if self.nodal is not None:
+            ws, _ = _PLANS.get(dofmap, strips=True)
+            _lib.check(self._fn_nodal(x.data_ptr(), cell_constants.data_ptr(), self.nodal.data_ptr(), y.data_ptr(), xg.data_ptr(),
+                                      xd.data_ptr(), pt.data_ptr(), wt.data_ptr(), ws.data_ptr(), *tail),
+                       "fus_stiffness_apply_planned_geom_nodal")
+        elif self._geom is not None:
             ws, _ = _PLANS.get(dofmap, strips=True)
             _lib.check(self._fn_geom(*head, xg.data_ptr(), xd.data_ptr(), pt.data_ptr(), wt.data_ptr(), ws.data_ptr(), *tail),
                        "fus_stiffness_apply_planned_geom")
@@ -910,7 +929,7 @@ class _StiffnessOperator(_CellOperator, _Launchable):
         self._apply(x, entity_constants, y, G_entity, entity_dofmap, self._dphi_cuda)
 
 
-def stiffness_operator(P, *args, affine_weights=None, geometry=None):
+def stiffness_operator(P, *args, affine_weights=None, geometry=None, nodal=None):
     """``stiffness_operator(P, dphi, float_type)`` (numba-cpu/operators.py:71) or
     ``stiffness_operator(P, float_type)`` (cuda/operators.py:73).
 
@@ -921,12 +940,19 @@ def stiffness_operator(P, *args, affine_weights=None, geometry=None):
     ``geometry`` (keyword, no reference counterpart): ``(x_dofs, x_g, pts, wts)`` -- the reference's
     mesh pair of numba-cpu/precompute.py:115 plus the 1-D GLL points / weights; the operator then
     forms G in the kernel from the 8 vertices of each (trilinear) cell and ignores its ``G``
-    argument.  ``x_dofs`` rows must be in the dofmap's cell order."""
+    argument.  ``x_dofs`` rows must be in the dofmap's cell order.
+
+    ``nodal`` (keyword, needs ``geometry``; no reference counterpart): a coefficient ``kappa`` with one value per dof of ``x``
+    (owned and ghost dofs, the numbering of ``x``).  The operator becomes ``y += K(cell_constants * kappa) x`` with kappa taken at
+    the quadrature points, which the GLL rule collocates with the dofs (csrc/stiffness_geom_nodal.hpp); ``cell_constants`` stays
+    a factor per cell.  The operator holds kappa as a device tensor of its type (``op.nodal``) and checks its length against
+    ``x`` at every apply.  Without ``geometry`` this raises: the general-G kernels compute the same operator from
+    ``nodal_medium.scale_G(G, kappa, dofmap)``."""
     if len(args) == 2:
         dphi, float_type = args
-        return _StiffnessOperator(P, float_type, dphi, affine_weights, geometry)
+        return _StiffnessOperator(P, float_type, dphi, affine_weights, geometry, nodal)
     if len(args) == 1:
-        return _StiffnessOperator(P, args[0], None, affine_weights, geometry)
+        return _StiffnessOperator(P, args[0], None, affine_weights, geometry, nodal)
     raise TypeError("stiffness_operator(P, dphi, float_type) or stiffness_operator(P, float_type)")
 
 

@@ -214,7 +214,8 @@ def heat_deposition(monitor, solver):
 
     This is the PLANE-WAVE form ``2 alpha I`` with ``I = |P|^2 / (2 rho c)`` per harmonic -- an approximation wherever the field is
     not a progressive plane wave (standing waves, the near field) -- with ``alpha_r`` the first-order absorption of the mechanisms
-    per cell.  Torch math on the monitor's maps; device tensor [nlocal], fp64."""
+    per cell (of a solver with a nodal medium: from the per-cell means of its nodal rho and c, as its per-cell weights' lumped
+    projection).  Torch math on the monitor's maps; device tensor [nlocal], fp64."""
     from .solver_base import run_schedule
 
     return run_schedule(heat_deposition_schedule(monitor, solver))

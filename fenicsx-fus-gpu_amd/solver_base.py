@@ -128,13 +128,28 @@ def vertex_geometry(mesh, P, dev):
     return (torch.from_numpy(np.ascontiguousarray(mesh.x_dofs)).to(dev), mesh.x_g) + gll_points_weights(P)
 
 
-def stiffness_form(mesh, P, D, G, float_type, affine="auto", in_kernel_geometry="auto", keep_G=False):
+def stiffness_form(mesh, P, D, G, float_type, affine="auto", in_kernel_geometry="auto", keep_G=False, nodal=None):
     """The stiffness operator of ``LinearSpectral3D`` / ``BioheatSpectral3D``: ``(operator, what travels in the G position of its
     call, affine, in_kernel_geometry, G_array)``.  Affine cells (every box mesh of the reference's demos): the constant-G fast path,
     after checking that the geometry factors really are affine (``"auto"``), or on request / never.  Otherwise, on request or by
     ``IN_KERNEL_GEOMETRY_FROM_DEGREE``: G formed in the kernel; the rows of ``x_dofs`` then travel in the G position (cell sub-ranges
-    slice them) and ``G_array``, the reference's array, is ``None`` unless ``keep_G`` (6 n^3 values per cell: 945 MB at config 3)."""
+    slice them) and ``G_array``, the reference's array, is ``None`` unless ``keep_G`` (6 n^3 values per cell: 945 MB at config 3).
+    ``nodal``: a coefficient per local dof inside the contraction (nodal_medium.py) -- the nodal kernel with G formed in the kernel, at
+    every degree and on affine boxes too (an affine box is a trilinear mesh), unless ``in_kernel_geometry`` is ``False``: then the
+    general kernel on the G array scaled once (``nodal_medium.scale_G``), which is what travels and what ``G_array`` is.  The
+    constant-G path reads one record per cell and cannot carry it: ``affine=True`` raises."""
     ft = np.dtype(float_type)
+    if nodal is not None:
+        if affine is True:
+            raise ValueError("affine=True with a nodal medium: the affine fast path reads one geometric record per cell, a nodal "
+                             "coefficient varies inside the cell")
+        if in_kernel_geometry is False:
+            from .nodal_medium import scale_G
+
+            Gs = scale_G(G, nodal, mesh.dofmap)
+            return ops.stiffness_operator(P, D.flatten(), ft), Gs, False, False, Gs
+        geometry = vertex_geometry(mesh, P, G.device)
+        return ops.stiffness_operator(P, D.flatten(), ft, geometry=geometry, nodal=nodal), geometry[0], False, True, G if keep_G else None
     w3 = tensor_weights_3d(gll_points_weights(P)[1])
     affine = bool(affine) if affine != "auto" else ops.is_affine_geometry(G, w3, rtol=1e-11 if ft == np.float64 else 1e-5)
     if in_kernel_geometry == "auto":

@@ -30,6 +30,7 @@
 #include "fus_gpu.h"
 #include "fus_gpu_array.h"
 #include "fus_gpu_relaxation.h"
+#include "fus_gpu_nodal.h"
 
 namespace fus_gpu {
 
@@ -310,6 +311,40 @@ private:
   const T* x_g_ = nullptr;
   const int32_t* x_dofs_ = nullptr;
   const T *pts_ = nullptr, *wts_ = nullptr, *dphi_ = nullptr;
+  detail::Plan plan_;
+};
+
+/// y += K(coeffs * nodal) x: the stiffness operator with a NODAL coefficient inside its contraction and the geometry formed in the kernel
+/// (fus_stiffness_apply_planned_geom_nodal_*, include/fus_gpu_nodal.h; no reference counterpart: its coefficients are per cell).
+/// ``nodal`` is a device vector in the dof numbering of x; the GLL rule is collocated, so it is the coefficient at the quadrature points.
+template <typename T, int P>
+class NodalStiffnessSpectral3D {
+  static_assert(std::is_same<T, double>::value || std::is_same<T, float>::value, "T: float or double");
+  static_assert(P >= FUS_MIN_DEGREE && P <= FUS_MAX_DEGREE, "degree out of range");
+
+public:
+  static constexpr int Nd = (P + 1) * (P + 1) * (P + 1);
+  /// x_g [nvert][3], x_dofs [ncells][8], pts / wts: 1-D GLL points on [0, 1] and weights T[P+1], dphi T[P+1][P+1], nodal T[ndofs]: device arrays
+  NodalStiffnessSpectral3D(const int32_t* dofmap, int64_t ncells, const T* x_g, const int32_t* x_dofs, const T* pts, const T* wts,
+                           const T* dphi, const T* nodal, hipStream_t stream = nullptr)
+      : Nc(ncells), x_g_(x_g), x_dofs_(x_dofs), pts_(pts), wts_(wts), dphi_(dphi), nodal_(nodal) {
+    check_abi();
+    plan_.build(dofmap, Nd, Nc, stream);
+  }
+  NodalStiffnessSpectral3D(const NodalStiffnessSpectral3D&) = delete;
+  NodalStiffnessSpectral3D& operator=(const NodalStiffnessSpectral3D&) = delete;
+  /// y += K x   (coeffs: device T[ncells], a further factor per cell)
+  void operator()(const T* x, const T* coeffs, T* y, hipStream_t stream = nullptr) const {
+    check(detail::typed<T>(fus_stiffness_apply_planned_geom_nodal_f64, fus_stiffness_apply_planned_geom_nodal_f32)(
+              x, coeffs, nodal_, y, x_g_, x_dofs_, pts_, wts_, plan_.ws, dphi_, P, Nc, stream),
+          "fus_stiffness_apply_planned_geom_nodal");
+  }
+
+private:
+  int64_t Nc;
+  const T* x_g_ = nullptr;
+  const int32_t* x_dofs_ = nullptr;
+  const T *pts_ = nullptr, *wts_ = nullptr, *dphi_ = nullptr, *nodal_ = nullptr;
   detail::Plan plan_;
 };
 
