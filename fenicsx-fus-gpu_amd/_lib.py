@@ -26,7 +26,8 @@ EXTENSION_HEADER_PATHS = (os.path.join(os.path.dirname(_HERE), "include", "fus_g
 ADDITION_HEADER_PATHS = (os.path.join(os.path.dirname(_HERE), "include", "fus_gpu_relaxation.h"),)
 # ... and, ADDITIONS being pinned too (tests/test_relaxation.py), the open tier: the path of EVERY later header is appended here, its
 # functions land in LATER, and no test pins that set to what it holds today
-LATER_HEADER_PATHS = (os.path.join(os.path.dirname(_HERE), "include", "fus_gpu_nodal.h"),)
+LATER_HEADER_PATHS = (os.path.join(os.path.dirname(_HERE), "include", "fus_gpu_nodal.h"),
+                      os.path.join(os.path.dirname(_HERE), "include", "fus_gpu_westervelt_nodal.h"))
 
 
 class FusGpuError(RuntimeError):

@@ -118,6 +118,10 @@ template <typename T>
 int stiffness_apply_planned_geom_nodal(const T* x, const T* cc, const T* nodal, T* y, const T* x_g, const int32_t* x_dofs, const T* pts,
                                        const T* wts, const void* ws, const T* dphi, int P, int64_t ncell, void* stream);  // dispatch_stiffness_nodal.hip
 template <typename T>
+int westervelt_stiffness_apply_planned_geom_nodal(const T* u, const T* v, const T* c3, const T* c4, const T* nodal3, const T* nodal4, T* b,
+                                                  const T* x_g, const int32_t* x_dofs, const T* pts, const T* wts, const void* ws,
+                                                  const T* dphi, int P, int64_t ncell, void* stream);  // dispatch_westervelt_nodal.hip
+template <typename T>
 int westervelt_cell(const T* u, const T* v, const T* c2, const T* c3, const T* c4, const T* c5, T* b, T* m, const T* G, const T* detJ,
                     const void* ws, const T* dphi, int P, int64_t ncell, void* stream);
 template <typename T>

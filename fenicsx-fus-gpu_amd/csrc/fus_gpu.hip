@@ -6,6 +6,7 @@
 #include "../../include/fus_gpu_array.h"
 #include "../../include/fus_gpu_relaxation.h"
 #include "../../include/fus_gpu_nodal.h"
+#include "../../include/fus_gpu_westervelt_nodal.h"
 
 #include <hip/hip_runtime.h>
 
@@ -638,6 +639,13 @@ int fus_plan_mark_exclusive(void* workspace, int N, int entities_per_batch, int6
                                                    const T* x_g, const int32_t* x_dofs, const T* pts, const T* wts, const void* ws,        \
                                                    const T* dphi, int P, int64_t ncell, void* s) {                                         \
     return westervelt_cell_geom<T>(u, v, c2, c3, c4, c5, b, m, x_g, x_dofs, pts, wts, ws, dphi, P, ncell, s);                              \
+  }                                                                                                                                        \
+  int fus_westervelt_stiffness_apply_planned_geom_nodal_##SUF(const T* u, const T* v, const T* c3, const T* c4, const T* nodal3,           \
+                                                              const T* nodal4, T* b, const T* x_g, const int32_t* x_dofs, const T* pts,    \
+                                                              const T* wts, const void* ws, const T* dphi, int P, int64_t ncell,           \
+                                                              void* s) {                                                                   \
+    return westervelt_stiffness_apply_planned_geom_nodal<T>(u, v, c3, c4, nodal3, nodal4, b, x_g, x_dofs, pts, wts, ws, dphi, P, ncell,    \
+                                                            s);                                                                            \
   }                                                                                                                                        \
   int fus_mass_apply_##SUF(const T* x, const T* c, T* y, const T* detJ, const int32_t* dofmap, int N, int64_t nent, void* s) {             \
     return mass_apply<T>(x, c, y, detJ, dofmap, N, nent, s);                                                                               \

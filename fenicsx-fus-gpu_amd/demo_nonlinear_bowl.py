@@ -14,6 +14,7 @@ cells (G varies per quadrature point; P1 geometry, cuda/demo_nonlinear_bowl.py:3
     python fenicsx-fus-gpu_amd/demo_nonlinear_bowl.py --sensor-plane 61,61 --peak-out FILE --array 6,6 --focus 0.008,0.006,0.006
     python fenicsx-fus-gpu_amd/demo_nonlinear_bowl.py --field-stats maps.npz     # last-period maps of every dof, accumulated on the device
     python fenicsx-fus-gpu_amd/demo_nonlinear_bowl.py --intensity                # the focus of the intensity |I| and the peak radiation force density |F|
+    python fenicsx-fus-gpu_amd/demo_nonlinear_bowl.py --nodal-lens               # c, rho, beta and alpha given at the dofs: a smooth inclusion
     python fenicsx-fus-gpu_amd/demo_nonlinear_bowl.py --thermal 10 20            # then heat for 10 s and cool for 20 s with the last period's q (bioheat.py)
     python -m torch.distributed.run --nproc-per-node 8 fenicsx-fus-gpu_amd/demo_nonlinear_bowl.py
 
@@ -73,7 +74,14 @@ def main():
                          "attenuation coefficient: two relaxation mechanisms and the thermoviscous diffusivity fitted together between half "
                          "and five times the source frequency (relaxation.fit_power_law); prints the fit's largest relative error; the "
                          "heat deposition of --field-stats / --thermal is then relaxation.heat_deposition")
+    ap.add_argument("--nodal-lens", action="store_true",
+                    help="a nodal medium (nodal_medium.NodalMedium): c, rho, beta and alpha given at the dofs, not per cell -- a smooth Gaussian "
+                         "inclusion (c 1480 -> 1780 m/s, rho 1000 -> 1200 kg/m^3, beta 3.5 -> 5, alpha 0.2 -> 5 dB/m, radius L/6) at the centre "
+                         "of the box; the cell pass takes 1/rho and delta/(rho c^2) inside its two contractions "
+                         "(csrc/westervelt_geom_nodal.hpp).  Composes with --sponge, --array, --field-stats, --intensity, --thermal and ranks")
     a = ap.parse_args()
+    if a.nodal_lens and (a.power_law or a.geometry == "array"):
+        ap.error("--nodal-lens: the nodal cell pass forms G in the kernel (not --geometry array), and --power-law fits its own attenuation")
     if a.thermal is not None and (len(a.thermal) > 2 or min(a.thermal) < 0.0):
         ap.error("--thermal SECONDS_ON [SECONDS_OFF], both >= 0")
     if (a.field_stats or a.thermal or a.intensity) and a.sensor_plane:
@@ -120,6 +128,16 @@ def main():
         return out
 
     mesh = boxmesh.BoxMesh(P, num_element, grid=grid, rank=rank, length=L, dtype=float_type, warp=bowl)
+    medium, fastest = None, speed_of_sound
+    if a.nodal_lens:
+        # callables of position: every rank evaluates them at its own dofs, ghosts included, so the values agree across ranks
+        centre, r2 = 0.5 * np.asarray(mesh.length), (L / 6.0) ** 2
+        bump = lambda xyz: np.exp(-np.sum((xyz - centre) ** 2, axis=1) / r2)  # noqa: E731
+        medium = fusgpu_loader.submodule("nodal_medium").NodalMedium(
+            lambda xyz: speed_of_sound + 300.0 * bump(xyz), lambda xyz: density + 200.0 * bump(xyz),
+            nonlinear_coefficient=lambda xyz: nonlinear_coefficient + 1.5 * bump(xyz),
+            attenuation_coefficient_dB=lambda xyz: attenuation_coefficient_dB + 4.8 * bump(xyz))
+        fastest = speed_of_sound + 300.0  # the time-step rule takes the fastest speed of the medium
     h = ls.time_step_parameters(mesh, P, speed_of_sound, source_frequency, L)
     if world > 1:
         hm = torch.tensor([h], dtype=torch.float64, device="cuda")
@@ -127,7 +145,7 @@ def main():
         h = float(hm.item())
     # :119-125 (CFL 0.40, an integer number of steps per period, final time L/c + 8/f)
     CFL = 0.40
-    dt = CFL * h / (speed_of_sound * P**2)
+    dt = CFL * h / (fastest * P**2)
     step_per_period = int(period / dt) + 1
     dt = period / step_per_period
     tf = L / speed_of_sound + 8.0 / source_frequency
@@ -173,9 +191,13 @@ def main():
                   flush=True)
     solver = nls.WesterveltSpectral3D(mesh, float_type, speed_of_sound, density, source_frequency, source_amplitude,
                                       nonlinear_coefficient, attenuation_coefficient_dB, comm=comm, fused=not a.reference_sequence, source=source,
-                                      sponge=sponge, relaxation=relaxation,
+                                      sponge=sponge, relaxation=relaxation, nodal_medium=medium,
                                       in_kernel_geometry=True if (a.in_kernel_geometry or a.geometry == "kernel") else ("auto" if a.geometry == "auto" else False))
     solver.init()
+    if medium is not None and rank == 0:
+        print(f"Nodal medium: c {solver.c_nodal.min():.1f} .. {solver.c_nodal.max():.1f} m/s, rho {solver.rho_nodal.min():.1f} .. "
+              f"{solver.rho_nodal.max():.1f} kg/m^3, beta {solver.beta_nodal.min():.2f} .. {solver.beta_nodal.max():.2f}, alpha "
+              f"{solver.att_nodal.min():.2f} .. {solver.att_nodal.max():.2f} dB/m at the dofs; cell pass: {solver.nodal_cell_pass if solver.fused else 'two launches (reference sequence)'}", flush=True)
     if sponge is not None:
         n_layer = solver._sponge[0].numel()
         print(f"Sponge layer (rank {rank}): {a.sponge} cell(s) wide, {n_layer} owned dofs, sigma_max dt = {sponge.sigma_max * dt:.3f}", flush=True)

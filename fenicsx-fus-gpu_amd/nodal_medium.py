@@ -11,6 +11,11 @@ same mesh, with no remeshing and no smaller time step.  ``LinearSpectral3D(..., 
   lumped mass   ``(M(1) 1, reverse-scattered) * 1/(rho c^2)``: diagonal
   facet terms   one value per facet, the mean of the nodal coefficient over the facet's dofs
 
+``WesterveltSpectral3D(..., nodal_medium=NodalMedium(c, rho, nonlinear_coefficient=beta, attenuation_coefficient_dB=alpha))`` takes the
+four fields of the nonlinear solver (``evaluate_westervelt``): 1/rho and delta/(rho c^2) inside the two contractions of ONE cell pass
+(csrc/westervelt_geom_nodal.hpp, ``operators.westervelt_cell_operator(..., geometry=, nodal=)``), three diagonals ``M(1) 1`` times a
+nodal factor, one mean coefficient per facet.
+
 ``sample_volume`` turns a voxel map (a CT-derived c / rho volume) into such an array.  No reference counterpart: its drivers take
 DG0 arrays only.
 """
@@ -28,13 +33,18 @@ class NodalMedium:
 
     On a partitioned mesh a ghost's value is computed by the rank that HOLDS it (from its own array or its own coordinates): nothing
     is exchanged, so the values a dof is given on different ranks must agree -- a callable of position, or arrays cut from one
-    global field, do.  Non-finite and non-positive values raise."""
+    global field, do.  Non-finite and non-positive values raise.
 
-    def __init__(self, speed_of_sound, density):
+    ``nonlinear_coefficient`` (beta) / ``attenuation_coefficient_dB`` (keywords, the Westervelt solver's fields; the linear solver
+    ignores them): the same three forms, finite and >= 0 (water has beta > 0, a lossless region alpha = 0); ``None`` takes the
+    solver's scalar (``evaluate_westervelt``)."""
+
+    def __init__(self, speed_of_sound, density, *, nonlinear_coefficient=None, attenuation_coefficient_dB=None):
         self.speed_of_sound, self.density = speed_of_sound, density
+        self.nonlinear_coefficient, self.attenuation_coefficient_dB = nonlinear_coefficient, attenuation_coefficient_dB
 
     @staticmethod
-    def _field(value, mesh, name, xyz):
+    def _field(value, mesh, name, xyz, positive=True):
         if callable(value):
             if xyz is None:
                 raise ValueError(f"{name}: a callable needs mesh.dof_coordinates(), which {type(mesh).__name__} does not have: "
@@ -51,8 +61,10 @@ class NodalMedium:
                                  f"got shape {a.shape}")
         if not np.all(np.isfinite(a)):
             raise ValueError(f"{name}: non-finite nodal values")
-        if not np.all(a > 0.0):
+        if positive and not np.all(a > 0.0):
             raise ValueError(f"{name}: nodal values must be positive (min {a.min()})")
+        if not positive and not np.all(a >= 0.0):
+            raise ValueError(f"{name}: nodal values must not be negative (min {a.min()})")
         return np.ascontiguousarray(a)
 
     def evaluate(self, mesh):
@@ -60,6 +72,20 @@ class NodalMedium:
         need_xyz = callable(self.speed_of_sound) or callable(self.density)
         xyz = mesh.dof_coordinates() if need_xyz and hasattr(mesh, "dof_coordinates") else None
         return (self._field(self.speed_of_sound, mesh, "speed_of_sound", xyz), self._field(self.density, mesh, "density", xyz))
+
+    def evaluate_westervelt(self, mesh, nonlinear_coefficient=None, attenuation_coefficient_dB=None):
+        """``(c, rho, beta, att_dB)``: float64 arrays ``[mesh.ndofs]`` in the mesh's dof numbering.  The two arguments are the
+        scalars a field left ``None`` takes (the solver passes its own); a field that is ``None`` in both places raises."""
+        fields = []
+        for name, own, default in (("nonlinear_coefficient", self.nonlinear_coefficient, nonlinear_coefficient),
+                                   ("attenuation_coefficient_dB", self.attenuation_coefficient_dB, attenuation_coefficient_dB)):
+            if own is None:
+                if default is None or np.ndim(default) != 0:
+                    raise ValueError(f"{name}: the medium leaves it None, so a scalar must be given")
+                own = default
+            xyz = mesh.dof_coordinates() if callable(own) and hasattr(mesh, "dof_coordinates") else None
+            fields.append(self._field(own, mesh, name, xyz, positive=False))
+        return self.evaluate(mesh) + tuple(fields)
 
 
 def cell_means(nodal, dofmap):

@@ -27,13 +27,18 @@ def compute_diffusivity_of_sound(frequency, speed, attenuationdB):
     return 2 * attenuationNp * speed**3 / frequency / frequency
 
 
+# The fused stage's cell pass with a nodal medium where ``nodal_cell_pass="auto"``: the one-pass kernel
+# (westervelt_cell_geom_nodal_kernel) or two launches of the nodal stiffness kernel (tools/time_westervelt_nodal.py decides)
+NODAL_CELL_PASS_DEFAULT = "fused"
+
+
 class WesterveltSpectral3D(SpectralSolver3D):
     def __init__(self, mesh, float_type=np.float64, speed_of_sound=1480.0, density=1000.0,
                  source_frequency=1.1e6, source_amplitude=None, nonlinear_coefficient=3.5,
                  attenuation_coefficient_dB=0.2, comm=None, source_time="tn", overlap=True, fused=False,
                  in_kernel_geometry="auto", uniform_ratio="auto", halo_plan=None, defer_setup_exchange=False,
                  reference_speed_of_sound=None, reference_density=None, keep_G=False, source=None, sponge=None,
-                 point_source=None, point_claim=None, relaxation=None):
+                 point_source=None, point_claim=None, relaxation=None, nodal_medium=None, nodal_cell_pass="auto"):
         """``speed_of_sound``, ``density``, ``nonlinear_coefficient``, ``attenuation_coefficient_dB``: scalars, or one value per
         cell in the caller's cell order (the DG0 material arrays of cuda/demo_nonlinear_bowl.py:166-178 -- water / skull / ...).
         ``reference_speed_of_sound`` / ``reference_density``: the scalars of the source term and of the default source amplitude
@@ -51,7 +56,43 @@ class WesterveltSpectral3D(SpectralSolver3D):
         every launch as it is.  ``relaxation``: a ``relaxation.RelaxationAbsorption`` (power-law absorption), as ``LinearSpectral3D``:
         K(c3) acts on u_n + sum xi, K(c4) on v_n as before, and the thermoviscous ``attenuation_coefficient_dB`` adds its f^2 part
         (``relaxation.fit_power_law`` fits both together); ``speed_of_sound`` is then the EQUILIBRIUM (low-frequency) speed.  The
-        single-gather form is out of scope: with ``uniform_ratio=True`` a ``ValueError``.  ``None`` keeps every launch as it is."""
+        single-gather form is out of scope: with ``uniform_ratio=True`` a ``ValueError``.  ``None`` keeps every launch as it is.
+        ``nodal_medium``: a ``nodal_medium.NodalMedium`` -- c, rho, beta and alpha at the DOFS in place of the four per-cell
+        arguments, which must then be left scalar (a field the medium leaves ``None`` takes the scalar).  With
+        ``delta = compute_diffusivity_of_sound(w0, c, alpha)`` at the dofs the cell pass is
+        ``b -= sum_q B_q^T G_q (1/rho grad u_n + delta/(rho c^2) grad v_n)``, the coefficients inside the contractions
+        (csrc/westervelt_geom_nodal.hpp; G formed in the kernel at every degree, ``in_kernel_geometry=False`` and
+        ``uniform_ratio=True`` raise), and the three diagonals are ONE unit-coefficient mass apply times nodal factors:
+        ``m0 = M(1)1 / (rho c^2)`` + the facet term, ``w2 = M(1)1 (-2 beta / (rho^2 c^4))``, ``w5 = -w2``.  The facet terms keep one
+        coefficient per facet, the mean over the facet's dofs of the nodal expression.  ``c_nodal`` ... ``att_nodal`` hold the fields,
+        ``c_cells`` / ``rho_cells`` / ``delta_cells`` the per-cell means, ``c0`` / ``rho0`` default to the means over the source facets'
+        dofs.  ``fused=False`` runs two launches of the nodal stiffness operator and pointwise products with ``w2`` / ``w5`` (no
+        reverse scatter of m).  ``nodal_cell_pass``: ``"fused"`` (the one-pass kernel), ``"two-launch"`` (the fused stage takes the
+        two launches of the nodal stiffness operator instead) or ``"auto"``: ``NODAL_CELL_PASS_DEFAULT``."""
+        self.nodal_medium = nodal_medium
+        if nodal_medium is not None:
+            given = {"speed_of_sound": speed_of_sound, "density": density, "nonlinear_coefficient": nonlinear_coefficient,
+                     "attenuation_coefficient_dB": attenuation_coefficient_dB}
+            arrays = [k for k, val in given.items() if np.ndim(val) != 0]
+            if arrays:
+                raise ValueError(f"nodal_medium= together with array(s) for {', '.join(arrays)}: the nodal medium is the medium, leave "
+                                 "the per-cell arguments scalar")
+            if uniform_ratio is True:
+                raise ValueError("nodal_medium= with uniform_ratio=True: the single-gather form needs one ratio delta / c^2 for the "
+                                 "whole medium")
+            if in_kernel_geometry is False:
+                raise ValueError("nodal_medium= with in_kernel_geometry=False: the nodal cell pass forms G in the kernel; two G arrays "
+                                 "scaled by the two coefficients (12 n^3 values per cell) are not worth carrying")
+            if nodal_cell_pass not in ("auto", "fused", "two-launch"):
+                raise ValueError(f"nodal_cell_pass={nodal_cell_pass!r}: 'auto', 'fused' or 'two-launch'")
+            from .nodal_medium import cell_means, facet_means
+
+            self.c_nodal, self.rho_nodal, self.beta_nodal, self.att_nodal = nodal_medium.evaluate_westervelt(
+                mesh, nonlinear_coefficient, attenuation_coefficient_dB)
+            self.delta_nodal = compute_diffusivity_of_sound(2 * np.pi * float(source_frequency), self.c_nodal, self.att_nodal)
+            speed_of_sound, density = cell_means(self.c_nodal, mesh.dofmap), cell_means(self.rho_nodal, mesh.dofmap)
+            nonlinear_coefficient = cell_means(self.beta_nodal, mesh.dofmap)
+            attenuation_coefficient_dB = cell_means(self.att_nodal, mesh.dofmap)
         if relaxation is not None and uniform_ratio is True:
             raise ValueError("WesterveltSpectral3D: relaxation= with uniform_ratio=True (the single-gather form w = u_n + kappa v_n) is not supported")
         c_cells, rho_cells = per_cell(speed_of_sound, mesh, "speed_of_sound"), per_cell(density, mesh, "density")
@@ -70,6 +111,14 @@ class WesterveltSpectral3D(SpectralSolver3D):
         self.p0 = float(source_amplitude) if source_amplitude is not None else self.rho0 * self.c0 * 0.38557513826589934
         self.beta = float(beta_cells.mean())
         delta_cells = compute_diffusivity_of_sound(self.w0, c_cells, att_cells)
+        if nodal_medium is not None:  # the means of the nodal fields (delta is not linear in c: the mean of delta, not delta of the means)
+            delta_cells = cell_means(self.delta_nodal, mesh.dofmap)
+            fd1 = mesh.facet_dofmap(bd1)
+            if bd1.shape[0] and reference_speed_of_sound is None:
+                self.c0 = float(self.c_nodal[fd1].mean())
+            if bd1.shape[0] and reference_density is None:
+                self.rho0 = float(self.rho_nodal[fd1].mean())
+            self.p0 = float(source_amplitude) if source_amplitude is not None else self.rho0 * self.c0 * 0.38557513826589934
         self.delta = float(delta_cells.mean())
         # per cell, in the mesh's cell order: what field_monitor.heat_deposition forms kappa = delta / (rho c^4) from
         self.delta_cells, self.rho_cells, self.c_cells = delta_cells, rho_cells, c_cells
@@ -87,6 +136,21 @@ class WesterveltSpectral3D(SpectralSolver3D):
         self.fc2_1 = td(delta[c1] / rho[c1] / c[c1] ** 2)
         self.fc1_2 = td(delta[c2] / rho[c2] / c[c2] ** 3)
         self.fc2_2 = td(-1.0 / rho[c2] / c[c2])
+        if nodal_medium is not None:
+            # the medium sits in nodal factors: unit cell constants (-1 for both stiffness inputs), one mean per facet; cc2 / cc5 are
+            # not applied (w2 / w5 come from M(1) 1)
+            rn, cn, bn, dn = self.rho_nodal, self.c_nodal, self.beta_nodal, self.delta_nodal
+            fd2 = mesh.facet_dofmap(bd2)
+            self.cc1 = td(np.ones(mesh.ncells))
+            self.cc3 = td(np.full(mesh.ncells, -1.0))
+            self.cc4 = td(np.full(mesh.ncells, -1.0))
+            self.cc2 = self.cc5 = None
+            self.fc1_1 = td(facet_means(1.0 / rn, fd1))
+            self.fc2_1 = td(facet_means(dn / rn / cn**2, fd1))
+            self.fc1_2 = td(facet_means(dn / rn / cn**3, fd2))
+            self.fc2_2 = td(-facet_means(1.0 / rn / cn, fd2))
+            self._kappa3, self._kappa4 = td(1.0 / rn), td(dn / rn / cn**2)
+            self._f0, self._f2 = td(1.0 / rn / cn**2), td(-2.0 * bn / rn**2 / cn**4)
         self.G, self.detJ = G_d, detJ_d
         self.dofmap = torch.from_numpy(mesh.dofmap).to(dev)
         self.dF1, self.dF2 = dF1_d, dF2_d
@@ -116,6 +180,12 @@ class WesterveltSpectral3D(SpectralSolver3D):
         # set-up applies on the default operator (atomic-free, bitwise reproducible), like the reference-sequence stage's two
         # cell mass applies: each runs alone on this stream, the reverse scatters follow in stream order
         self.mass_cell(self.g, self.cc1, self.m0, self.detJ, self.dofmap)
+        if nodal_medium is not None:
+            # m0 holds this rank's part of M(1) 1: the three diagonals are that times a nodal factor.  Ghost values of the factors agree
+            # across ranks (NodalMedium's contract), so the factor is applied BEFORE the reverse scatter and the one grouped exchange stays
+            self.w2, self.w5 = self.m0 * self._f2, z()
+            self.w5.sub_(self.w2)
+            self.m0.mul_(self._f0)
         self.mass_facet(self.g, self.fc1_2, self.m0, self.dF2, self.fdm2)
 
         self.cell_fused = ops.westervelt_cell_operator(P, D.flatten(), ft)
@@ -123,9 +193,10 @@ class WesterveltSpectral3D(SpectralSolver3D):
         # stage's two cell mass applies (M(c2) u_n for the lumped mass, M(c5) v_n^2 for the right-hand side,
         # cuda/demo_nonlinear_bowl.py:612-616,630-632) are pointwise products with two diagonals assembled
         # once, like m0; the cell pass is then the stiffness part alone and m needs no reverse scatter
-        self.w2, self.w5 = z(), z()
-        self.mass_cell(self.g, self.cc2, self.w2, self.detJ, self.dofmap)  # g == 1 here
-        self.mass_cell(self.g, self.cc5, self.w5, self.detJ, self.dofmap)
+        if nodal_medium is None:
+            self.w2, self.w5 = z(), z()
+            self.mass_cell(self.g, self.cc2, self.w2, self.detJ, self.dofmap)  # g == 1 here
+            self.mass_cell(self.g, self.cc5, self.w5, self.detJ, self.dofmap)
         # the reverse scatters of the three assembled diagonals, as one grouped exchange
         self._start_setup(defer_setup_exchange)
         # uniform ratio c4 / c3 (= delta / c^2: every homogeneous medium): K(c3) u + K(c4) v = K(c3)(u + kappa v),
@@ -151,7 +222,9 @@ class WesterveltSpectral3D(SpectralSolver3D):
         self.w = z() if self.kappa is not None else None
         # opt-in (fused mode): G and detJ formed in the cell kernel from the vertices -- the cells of
         # the reference's meshes are trilinear (P1 geometry, cuda/demo_nonlinear_bowl.py:317)
-        if in_kernel_geometry == "auto":
+        if nodal_medium is not None:
+            in_kernel_geometry = True  # at every degree, and in the reference launch sequence too: the nodal kernels form G themselves
+        elif in_kernel_geometry == "auto":
             in_kernel_geometry = self.fused and P >= IN_KERNEL_GEOMETRY_FROM_DEGREE
         self.in_kernel_geometry = bool(in_kernel_geometry)
         if self.in_kernel_geometry and self.fused and not keep_G:
@@ -163,10 +236,23 @@ class WesterveltSpectral3D(SpectralSolver3D):
             self.cell_fused_geom = ops.westervelt_cell_operator(P, D.flatten(), ft, geometry=geometry[1:])
             self.stiff_geom = ops.stiffness_operator(P, D.flatten(), ft, geometry=geometry)
             stiff, pair = self.stiff_geom, self.cell_fused_geom
+        self.nodal_cell_pass = None
+        if nodal_medium is not None:
+            self.nodal_cell_pass = NODAL_CELL_PASS_DEFAULT if nodal_cell_pass == "auto" else nodal_cell_pass
+            self.cell_nodal = ops.westervelt_cell_operator(P, D.flatten(), ft, geometry=geometry[1:], nodal=(self._kappa3, self._kappa4))
+            self.stiff_nodal3 = ops.stiffness_operator(P, D.flatten(), ft, geometry=geometry, nodal=self._kappa3)
+            self.stiff_nodal4 = ops.stiffness_operator(P, D.flatten(), ft, geometry=geometry, nodal=self._kappa4)
+            pair = self.cell_nodal
         # the fused stage's cell pass, one of four: single gather (K(c3) w, w = u_n + kappa v_n) or two (K(c3) u_n + K(c4) v_n),
         # each with the G array or G formed in the kernel (x_dofs rows travel in the G position)
         self._percell = (self.cc3, self.cc4, self.x_dofs if self.in_kernel_geometry else self.G, self.dofmap)
-        if self.kappa is not None:
+        if self.nodal_cell_pass == "two-launch":
+            def two_launches(u_n, v_n, c3, c4, G_, dm_):
+                self.stiff_nodal3(u_n, c3, self.b, G_, dm_)
+                self.stiff_nodal4(v_n, c4, self.b, G_, dm_)
+
+            self._cell_pass = two_launches
+        elif self.kappa is not None:
             self._cell_pass = lambda u_n, v_n, c3, c4, G_, dm_: stiff(self.w, c3, self.b, G_, dm_)
         else:
             self._cell_pass = lambda u_n, v_n, c3, c4, G_, dm_: pair.stiffness_only(u_n, v_n, c3, c4, self.b, G_, dm_)
@@ -252,23 +338,37 @@ class WesterveltSpectral3D(SpectralSolver3D):
             self.fwd_w(self.w_n)
             if self.relaxation is not None:
                 self.fwd_r(self._relax_bound().ur)
-        # unsteady lumped mass
-        fill(0.0, self.m)
-        self.mass_cell(self.u_n, self.cc2, self.m, self.detJ, self.dofmap)
-        if self.halo is not None:
-            self.halo.rev(self.m)
-        axpy(1.0, self.m0, self.m)
-        # right-hand side
-        fill(0.0, self.b)
-        self.stiff(self._stiffness_input(self.u_n), self.cc3, self.b, self.G, self.dofmap)
-        self.stiff(self.v_n, self.cc4, self.b, self.G, self.dofmap)
-        self.mass_cell(self.w_n, self.cc5, self.b, self.detJ, self.dofmap)
+        nl = self.nlocal
+        if self.nodal_medium is not None:
+            # nodal medium: the two cell mass applies are pointwise products with the assembled diagonals (complete at the owned dofs:
+            # no reverse scatter of m), the stiffness part two launches of the nodal stiffness operator
+            copy(self.m0, self.m)
+            ops.muladd(self.w2, self.u_n, self.m[:nl])
+            fill(0.0, self.b)
+            self.stiff_nodal3(self._stiffness_input(self.u_n), self.cc3, self.b, self.x_dofs, self.dofmap)
+            self.stiff_nodal4(self.v_n, self.cc4, self.b, self.x_dofs, self.dofmap)
+            ops.muladd(self.w5, self.w_n, self.b[:nl])
+        else:
+            # unsteady lumped mass
+            fill(0.0, self.m)
+            self.mass_cell(self.u_n, self.cc2, self.m, self.detJ, self.dofmap)
+            if self.halo is not None:
+                self.halo.rev(self.m)
+            axpy(1.0, self.m0, self.m)
+            # right-hand side
+            fill(0.0, self.b)
+            self.stiff(self._stiffness_input(self.u_n), self.cc3, self.b, self.G, self.dofmap)
+            self.stiff(self.v_n, self.cc4, self.b, self.G, self.dofmap)
+            self.mass_cell(self.w_n, self.cc5, self.b, self.detJ, self.dofmap)
         source_facets()
         self.mass_facet(self.v_n, self.fc2_2, self.b, self.dF2, self.fdm2)
         self._extra_terms(self.u_n, self.v_n, ts)
         if self.halo is not None:
             self.halo.rev(self.b)
-        ops.pointwise_divide(self.b, self.m, self.kv)
+        if self.nodal_medium is not None:  # m is formed at the owned dofs only
+            ops.pointwise_divide(self.b, self.m, self.kv[:nl])
+        else:
+            ops.pointwise_divide(self.b, self.m, self.kv)
         axpy(B_RUNGE[i] * dt, self.ku, self.u)
         axpy(B_RUNGE[i] * dt, self.kv, self.v)
         self._relax_reference(i, dt)

@@ -1081,9 +1081,52 @@ class _WesterveltCellGeomOperator(_WesterveltCellOperator):
         self._apply(u, v, None, c3, c4, None, b, None, x_dofs, dofmap)
 
 
-def westervelt_cell_operator(P, dphi, float_type, geometry=None):
+class _WesterveltCellNodalOperator(_WesterveltCellGeomOperator):
+    """The stiffness part of the Westervelt cell pass with NODAL coefficients (csrc/westervelt_geom_nodal.hpp):
+    ``b += sum_q B_q^T G_q (c3 kappa3 grad u + c4 kappa4 grad v)``, G formed in the kernel.  ``kappa3`` / ``kappa4`` (one value per
+    dof of ``u``, owned and ghost) are held by the operator as device tensors of its type (``op.nodal``), so that
+    ``stiffness_only`` keeps the call shape of the per-cell operator and a cell sub-range of a halo schedule needs nothing new.
+    The kernel has no mass part: the full form raises."""
+
+    _entry_name = "westervelt_stiffness_apply_planned_geom_nodal"
+
+    def __init__(self, P, dphi, float_type, x_g, pts, wts, nodal):
+        super().__init__(P, dphi, float_type, x_g, pts, wts)
+        if len(nodal) != 2:
+            raise ValueError("westervelt_cell_operator(nodal=(kappa3, kappa4)): two coefficient vectors")
+        self.nodal = tuple(_to_device(k, self.dtype).reshape(-1) for k in nodal)
+        if self.nodal[0].numel() != self.nodal[1].numel():
+            raise ValueError("westervelt_cell_operator(nodal=(kappa3, kappa4)): the two vectors differ in length")
+
+    def __call__(self, u, v, c2, c3, c4, c5, b, m, x_dofs, dofmap):
+        raise ValueError("the nodal Westervelt cell operator has no mass part (c2 / c5 / m): call stiffness_only and take the mass "
+                         "terms from diagonals, as the fused stage does")
+
+    def stiffness_only(self, u, v, c3, c4, b, x_dofs, dofmap):
+        """``b += K(c3 kappa3) u + K(c4 kappa4) v`` in one pass over the cells."""
+        ncell, nd = self._check(dofmap, (("c3", c3), ("c4", c4)), (("u", u), ("v", v), ("b", b)))
+        geometry = self._geometry_args(x_dofs, ncell, nd, False)
+        k3, k4 = self.nodal
+        if k3.numel() != u.numel() or k3.device != u.device or v.numel() != u.numel():
+            raise ValueError(f"the operator's nodal coefficients have {k3.numel()} entries on {k3.device}, u has {u.numel()} on "
+                             f"{u.device} and v {v.numel()}: one value per dof of u")
+        if ncell == 0:
+            return
+        ws, _ = _PLANS.get(dofmap, strips=self._strips)
+        _lib.check(self._fn(u.data_ptr(), v.data_ptr(), c3.data_ptr(), c4.data_ptr(), k3.data_ptr(), k4.data_ptr(), b.data_ptr(),
+                            *geometry, ws.data_ptr(), self._dphi.data_ptr(), self.P, int(ncell), _lib.stream_ptr()),
+                   "fus_" + self._entry_name)
+
+
+def westervelt_cell_operator(P, dphi, float_type, geometry=None, nodal=None):
     """``geometry=(x_g, pts, wts)``: the variant that forms G and detJ in the kernel (its call takes
-    ``x_dofs`` in place of ``G, detJ``)."""
+    ``x_dofs`` in place of ``G, detJ``).  ``nodal=(kappa3, kappa4)`` (needs ``geometry``): a coefficient per dof of ``u`` on
+    each input, inside the contraction (``_WesterveltCellNodalOperator``; ``stiffness_only`` alone)."""
+    if nodal is not None:
+        if geometry is None:  # (before anything is put on a device)
+            raise ValueError("westervelt_cell_operator(nodal=...) needs geometry=(x_g, pts, wts): the nodal kernel forms G from the "
+                             "cell vertices")
+        return _WesterveltCellNodalOperator(P, dphi, float_type, *geometry, nodal)
     if geometry is not None:
         return _WesterveltCellGeomOperator(P, dphi, float_type, *geometry)
     return _WesterveltCellOperator(P, dphi, float_type)
@@ -1198,7 +1241,24 @@ class _Scale(_Launchable):
     __call__ = launch
 
 
+class _MulAdd(_Launchable):
+    """y += w * x over the length of y  (``fus_muladd_*``, the kernel of ``DiagonalMassOperator``; no reference kernel: the product
+    of a field with an assembled diagonal, which the Westervelt reference sequence with a nodal medium takes in place of a cell mass
+    apply)."""
+
+    @staticmethod
+    def launch(w, x, y):
+        fn, _ = _vec("muladd", w, x, y)
+        n = y.numel()
+        if w.numel() < n or x.numel() < n:
+            raise ValueError("muladd: inputs shorter than output")
+        _lib.check(fn(w.data_ptr(), x.data_ptr(), y.data_ptr(), n, _lib.stream_ptr()), "fus_muladd")
+
+    __call__ = launch
+
+
 axpy = _Axpy()
+muladd = _MulAdd()
 scale = _Scale()
 copy = _Copy()
 fill = _Fill()

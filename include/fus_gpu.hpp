@@ -31,6 +31,7 @@
 #include "fus_gpu_array.h"
 #include "fus_gpu_relaxation.h"
 #include "fus_gpu_nodal.h"
+#include "fus_gpu_westervelt_nodal.h"
 
 namespace fus_gpu {
 
@@ -345,6 +346,41 @@ private:
   const T* x_g_ = nullptr;
   const int32_t* x_dofs_ = nullptr;
   const T *pts_ = nullptr, *wts_ = nullptr, *dphi_ = nullptr, *nodal_ = nullptr;
+  detail::Plan plan_;
+};
+
+/// b += sum_q B_q^T G_q (c3 nodal3 grad u + c4 nodal4 grad v): the stiffness part of the Westervelt cell pass with NODAL coefficients
+/// on both inputs and the geometry formed in the kernel (fus_westervelt_stiffness_apply_planned_geom_nodal_*,
+/// include/fus_gpu_westervelt_nodal.h; no reference counterpart).  ``nodal3`` / ``nodal4`` are device vectors in the dof numbering of u.
+template <typename T, int P>
+class WesterveltNodalStiffnessSpectral3D {
+  static_assert(std::is_same<T, double>::value || std::is_same<T, float>::value, "T: float or double");
+  static_assert(P >= FUS_MIN_DEGREE && P <= FUS_MAX_DEGREE, "degree out of range");
+
+public:
+  static constexpr int Nd = (P + 1) * (P + 1) * (P + 1);
+  /// x_g [nvert][3], x_dofs [ncells][8], pts / wts: 1-D GLL points on [0, 1] and weights T[P+1], dphi T[P+1][P+1], nodal3 / nodal4
+  /// T[ndofs]: device arrays
+  WesterveltNodalStiffnessSpectral3D(const int32_t* dofmap, int64_t ncells, const T* x_g, const int32_t* x_dofs, const T* pts,
+                                     const T* wts, const T* dphi, const T* nodal3, const T* nodal4, hipStream_t stream = nullptr)
+      : Nc(ncells), x_g_(x_g), x_dofs_(x_dofs), pts_(pts), wts_(wts), dphi_(dphi), nodal3_(nodal3), nodal4_(nodal4) {
+    check_abi();
+    plan_.build(dofmap, Nd, Nc, stream);
+  }
+  WesterveltNodalStiffnessSpectral3D(const WesterveltNodalStiffnessSpectral3D&) = delete;
+  WesterveltNodalStiffnessSpectral3D& operator=(const WesterveltNodalStiffnessSpectral3D&) = delete;
+  /// b += K(c3 nodal3) u + K(c4 nodal4) v   (c3, c4: device T[ncells], a further factor per cell)
+  void operator()(const T* u, const T* v, const T* c3, const T* c4, T* b, hipStream_t stream = nullptr) const {
+    check(detail::typed<T>(fus_westervelt_stiffness_apply_planned_geom_nodal_f64, fus_westervelt_stiffness_apply_planned_geom_nodal_f32)(
+              u, v, c3, c4, nodal3_, nodal4_, b, x_g_, x_dofs_, pts_, wts_, plan_.ws, dphi_, P, Nc, stream),
+          "fus_westervelt_stiffness_apply_planned_geom_nodal");
+  }
+
+private:
+  int64_t Nc;
+  const T* x_g_ = nullptr;
+  const int32_t* x_dofs_ = nullptr;
+  const T *pts_ = nullptr, *wts_ = nullptr, *dphi_ = nullptr, *nodal3_ = nullptr, *nodal4_ = nullptr;
   detail::Plan plan_;
 };
 
