@@ -125,6 +125,7 @@ TUNE_PLAN_RUNS = _DEFINES["FUS_TUNE_PLAN_RUNS"]
 TUNE_VECTOR_STREAM = _DEFINES["FUS_TUNE_VECTOR_STREAM"]
 TUNE_PLAN_ROWS = _DEFINES["FUS_TUNE_PLAN_ROWS"]
 TUNE_PLAN_XCD_GROUP = _DEFINES["FUS_TUNE_PLAN_XCD_GROUP"]
+TUNE_PLAN_SWEEP = _DEFINES["FUS_TUNE_PLAN_SWEEP"]
 
 _lib = None
 

@@ -62,7 +62,8 @@ int stiffness_apply_planned(const T* x, const T* cc, T* y, const T* G, const voi
   return planned_cell_entry<T>(args_ok, ws, P, ncell, [&](auto p, bool ord, bool runs) {
     constexpr int PP = decltype(p)::value;
     // placement of the batches on the XCDs, carried in the kernels' xcd_remap argument (stiffness.hpp: place_batch)
-    const int remap = chunks ? 1 : plan_xcd_group<T, PP>();
+    // ... and the direction of the sweep in its flag bit (fus_dispatch.hpp: plan_sweep_down flips the plan's parity when it alternates)
+    const int remap = (chunks ? 1 : plan_xcd_group<T, PP>()) | (plan_sweep_down<T>(ws, PP, ncell) ? fus::kPlaceReverse : 0);
     // Builds (profiles/r01d_ab_alias_by_degree.log, r02*_ab_*.log; pinned by tests/test_resource_usage.py):
     //   0  three LDS cubes + own x/y buffer           (P <= 3)
     //   1  LDS-aliased, whole G slab issued up front  (P = 4, 5: 4 workgroups per CU at P = 4)

@@ -10,6 +10,7 @@
 
 #include "plan.hpp"
 #include "plan_registry.hpp"
+#include "plan_sweep.hpp"
 
 namespace fus_abi {
 
@@ -48,6 +49,9 @@ inline std::atomic<int> g_plan_rows{1};
 // stiffness_apply_planned), 0 = off, a power of two from 2 to 256 = g.  g_xcd_remap = 1 wins over it.
 inline std::atomic<int> g_plan_xcd_group{-1};
 inline bool plan_xcd_group_valid(int v) { return v == -1 || v == 0 || (v >= 2 && v <= 256 && (v & (v - 1)) == 0); }
+// general-G planned apply, both kernels: the direction in which a launch walks its batches (plan_sweep.hpp).  -1 = auto, 0 = upwards,
+// 1 = every launch of a plan the other way than the one before it, 2 = downwards
+inline std::atomic<int> g_plan_sweep{plan_sweep_initial()};
 
 // The one workspace registry of the library (plan_registry.hpp) is defined in fus_gpu.hip, where the header type of the gather plans is
 // complete.  true if ``ws`` holds a batch plan for exactly this shape; ``ordered`` out
@@ -55,6 +59,22 @@ bool plan_check(const void* ws, int N, int epb, int64_t nent, bool* ordered, boo
 
 // runs per batch of the compact run tables if the plan at ``ws`` says that its rows are consecutive, else 0
 int plan_rows_stride(const void* ws);
+
+// flips the sweep parity of the batch plan at ``ws`` (one bit per workspace, under the registry's mutex) and returns the value before
+// the flip: 0, 1, 0, ...
+int plan_sweep_flip(const void* ws);
+
+// Is this general-G launch a downward one?  Host state only: no device allocation, no synchronisation, no global counter.  Every plan
+// has its own parity, so the sub-launches of a halo apply, which own separate plans, alternate independently.  Under stream capture the
+// flip happens at capture time and the direction is baked into the node: a captured step with an EVEN number of general-G applies on a
+// plan (RK4: four) ends where it began and alternates consistently across replays; an odd number repeats the last direction at the
+// seam between two replays and merely loses the gain on that pair.
+template <typename T>
+inline bool plan_sweep_down(const void* ws, int P, int64_t ncell) {
+  const int knob = g_plan_sweep.load(std::memory_order_relaxed);
+  if (plan_sweep_alternates(knob, P, (int)sizeof(T), ncell)) return plan_sweep_flip(ws) == 1;
+  return knob == 2;
+}
 
 inline int hip_rc(hipError_t e) { return e == hipSuccess ? FUS_OK : FUS_ERR_HIP_BASE - (int)e; }
 

@@ -406,6 +406,8 @@ int fus_abi::plan_rows_stride(const void* ws) {
   return (g_registry.get(ws, &p) && p.rows_consecutive) ? p.run_stride : 0;
 }
 
+int fus_abi::plan_sweep_flip(const void* ws) { return g_registry.flip_sweep(ws); }
+
 extern "C" {
 
 int fus_abi_version(void) { return FUS_ABI_VERSION; }
@@ -457,6 +459,10 @@ int fus_set_tuning(int key, int value) {
       if (!plan_xcd_group_valid(value)) return FUS_ERR_INVALID_ARGUMENT;
       g_plan_xcd_group = value;
       return FUS_OK;
+    case FUS_TUNE_PLAN_SWEEP:
+      if (!plan_sweep_valid(value)) return FUS_ERR_INVALID_ARGUMENT;
+      g_plan_sweep = value;
+      return FUS_OK;
     case FUS_TUNE_VECTOR_STREAM:
       if (value < 0 || value > 4) return FUS_ERR_INVALID_ARGUMENT;
       fus::vector_stream_mode() = value;
@@ -474,6 +480,7 @@ int fus_get_tuning(int key) {
     case FUS_TUNE_PLAN_RUNS: return g_plan_runs;
     case FUS_TUNE_PLAN_ROWS: return g_plan_rows;
     case FUS_TUNE_PLAN_XCD_GROUP: return g_plan_xcd_group;
+    case FUS_TUNE_PLAN_SWEEP: return g_plan_sweep;
     case FUS_TUNE_VECTOR_STREAM: return fus::vector_stream_mode();
   }
   return FUS_ERR_INVALID_ARGUMENT;

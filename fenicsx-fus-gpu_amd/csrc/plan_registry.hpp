@@ -22,6 +22,7 @@ struct PlanInfo {
   int64_t nbatch = 0, with_runs = 0;
   bool rows_consecutive = false;  // the header's word: every local row of every cell is consecutive dof numbers (plan.hpp: rowbase)
   int run_stride = 0;             // runs per batch of the compact copy of the run tables (plan.hpp: runs_c); 0: the plan has none
+  bool sweep_down = false;        // the next alternating general-G apply on this plan walks its batches downwards (flip_sweep)
 };
 
 // static companion of a transposed gather plan (detJ in row order), keyed by its own workspace address
@@ -55,6 +56,17 @@ class PlanRegistry {
     PlanInfo* p = it == map_.end() ? nullptr : std::get_if<PlanInfo>(&it->second);
     if (p) p->exclusive = true;
     return p != nullptr;
+  }
+  // flips the sweep direction of the batch plan at ``ws`` and returns the one from BEFORE the flip (0 upwards, 1 downwards: 0, 1, 0, ...
+  // per workspace; a build at the address starts at 0 again); -1 if there is no batch plan
+  int flip_sweep(const void* ws) {
+    std::lock_guard<std::mutex> lk(mu_);
+    const auto it = map_.find(ws);
+    PlanInfo* p = it == map_.end() ? nullptr : std::get_if<PlanInfo>(&it->second);
+    if (!p) return -1;
+    const bool was = p->sweep_down;
+    p->sweep_down = !was;
+    return was ? 1 : 0;
   }
   // forgets ``ws`` and every static companion of the plan at ``ws``; an unknown address is no error
   void release(const void* ws) {

@@ -124,10 +124,24 @@ __host__ __device__ __forceinline__ unsigned group_block(unsigned bid, unsigned 
   return ((m >> s) << (3 + s)) + (k << s) + (m & ((1u << s) - 1u));
 }
 
-// The planned general-G kernels carry the placement in their ``xcd_remap`` argument: 0 natural, 1 remap_block's contiguous eighths,
-// a power of two from 2 = group_block's g.
+// Sweep direction: batch b mirrored to nblocks - 1 - b.  A launch that walks the batches downwards needs first what an upward launch
+// before it touched last, i.e. what the memory-side cache may still hold of G ("sweep direction").  A bijection.
+__host__ __device__ __forceinline__ unsigned mirror_block(unsigned b, unsigned nblocks, bool reversed) {
+  return reversed ? nblocks - 1u - b : b;
+}
+
+// The planned general-G kernels carry the placement in their ``xcd_remap`` argument.  Low bits: 0 natural, 1 remap_block's contiguous
+// eighths, a power of two from 2 = group_block's g.  Bit kPlaceReverse: the placement's batch is mirrored, AFTER the placement, so the
+// chip still reads one front of G and the XCD groups stay whole (the blocks that shared an XCD's L2 still do), only walked downwards.
+// Scalar and uniform over the workgroup.
+constexpr int kPlaceReverse = 1 << 16;
+// the grouped placements (every low value but 1) with the direction bit; tests/test_sweep_placement.py runs it on the host
+__host__ __device__ __forceinline__ unsigned place_grouped(unsigned bid, unsigned nblocks, int xcd_remap) {
+  return mirror_block(group_block(bid, nblocks, xcd_remap & (kPlaceReverse - 1)), nblocks, (xcd_remap & kPlaceReverse) != 0);
+}
 __device__ __forceinline__ unsigned place_batch(unsigned bid, unsigned nblocks, int xcd_remap) {
-  return xcd_remap == 1 ? remap_block(bid, nblocks, 1) : group_block(bid, nblocks, xcd_remap);
+  return (xcd_remap & (kPlaceReverse - 1)) == 1 ? mirror_block(remap_block(bid, nblocks, 1), nblocks, (xcd_remap & kPlaceReverse) != 0)
+                                                : place_grouped(bid, nblocks, xcd_remap);
 }
 
 template <typename T, int P, int CPB>

@@ -78,7 +78,8 @@ int fus_device_info(int device, char* name, int* compute_units, int64_t* hbm_byt
 #define FUS_TUNE_PLAN_RUNS 5         /* which encoding of a plan's dof lists the apply kernels read: 0 the lists, 2 the run tables, 1 auto (default: fp64 run tables; fp32 run tables up to 125 dofs per entity, lists above); 0 at plan build = no run tables are built */
 #define FUS_TUNE_PLAN_ROWS 7         /* fp64 general-G planned apply on a plan whose local rows are all consecutive dof numbers (every box-mesh numbering): 1 (default) = read one 16-bit slot per local row and the compact run tables, 0 = one slot per dof and the full tables (A/B knob; same result) */
 #define FUS_TUNE_PLAN_XCD_GROUP 8    /* general-G planned apply: of the workgroups that share an XCD, g consecutive ones take g consecutive cell batches, so that batches sharing dofs of x meet in one L2: -1 (default) = auto per degree and type, 0 = off, a power of two from 2 to 256 = g; any other value is refused.  FUS_TUNE_XCD_REMAP = 1 wins over it (A/B knob; same sums per batch) */
-#define FUS_TUNE_VECTOR_STREAM 6      /* non-temporal accesses in the streaming vector kernels (fus_axpy ... fus_rk4_stage_*): 0 never, 1 auto (default: non-temporal loads and stores for operands > 24 MB), 2 always, 3 / 4 the same with non-temporal stores only -- a plain store leaves its line dirty in the memory-side cache, to be written back while the NEXT kernel runs (csrc/vecops.hpp) */
+#define FUS_TUNE_PLAN_SWEEP 9        /* general-G planned apply: the direction in which a launch walks its cell batches.  -1 (default) = auto: a launch whose algorithmic bytes exceed the 256 MiB memory-side cache walks the other way than the launch before it on the same plan, so that it starts on the part of G the cache still holds; a smaller launch walks upwards.  0 = always upwards, 1 = alternate on every launch, 2 = always downwards (A/B and tests); any other value is refused.  The parity is one bit per plan workspace, host state.  The environment variable FUS_TUNE_PLAN_SWEEP sets the initial value (same sums per batch) */
+#define FUS_TUNE_VECTOR_STREAM 6     /* non-temporal accesses in the streaming vector kernels (fus_axpy ... fus_rk4_stage_*): 0 never, 1 auto (default: non-temporal loads and stores for operands > 24 MB), 2 always, 3 / 4 the same with non-temporal stores only -- a plain store leaves its line dirty in the memory-side cache, to be written back while the NEXT kernel runs (csrc/vecops.hpp) */
 int fus_set_tuning(int key, int value);
 int fus_get_tuning(int key);
 
