@@ -12,9 +12,10 @@ pytestmark = pytest.mark.gpu
 
 GUARD, SENTINEL = 16, -7.25
 
-# cells per degree: not a multiple of cells_per_batch(P) (64, 28, 16, 10, 5, 2, 2 for P = 1, 2, 3, 4, 6, 9, 10) and at least two batches,
-# so that the last batch is partial and dofs are shared between batches
-SHAPES = {1: (5, 4, 4), 2: (4, 3, 3), 3: (4, 3, 3), 4: (3, 2, 2), 6: (3, 2, 2), 9: (3, 3, 1), 10: (3, 3, 1)}
+# cells per degree: not a multiple of cells_per_batch(P) (64, 28, 16, 10, 7, 5, 4, 3, 2, 2 for P = 1 .. 10: every degree the operator
+# dispatches) and at least two batches, so that the last batch is partial and dofs are shared between batches
+SHAPES = {1: (5, 4, 4), 2: (4, 3, 3), 3: (4, 3, 3), 4: (3, 2, 2), 5: (4, 2, 2), 6: (3, 2, 2), 7: (3, 3, 1), 8: (7, 1, 1), 9: (3, 3, 1),
+          10: (3, 3, 1)}
 
 
 def _np(t):
