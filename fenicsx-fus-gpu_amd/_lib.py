@@ -27,7 +27,8 @@ ADDITION_HEADER_PATHS = (os.path.join(os.path.dirname(_HERE), "include", "fus_gp
 # ... and, ADDITIONS being pinned too (tests/test_relaxation.py), the open tier: the path of EVERY later header is appended here, its
 # functions land in LATER, and no test pins that set to what it holds today
 LATER_HEADER_PATHS = (os.path.join(os.path.dirname(_HERE), "include", "fus_gpu_nodal.h"),
-                      os.path.join(os.path.dirname(_HERE), "include", "fus_gpu_westervelt_nodal.h"))
+                      os.path.join(os.path.dirname(_HERE), "include", "fus_gpu_westervelt_nodal.h"),
+                      os.path.join(os.path.dirname(_HERE), "include", "fus_gpu_waveform.h"))
 
 
 class FusGpuError(RuntimeError):

@@ -7,6 +7,7 @@
 #include "../../include/fus_gpu_relaxation.h"
 #include "../../include/fus_gpu_nodal.h"
 #include "../../include/fus_gpu_westervelt_nodal.h"
+#include "../../include/fus_gpu_waveform.h"
 
 #include <hip/hip_runtime.h>
 
@@ -27,6 +28,7 @@
 #include "relaxation.hpp"
 #include "rk4.hpp"
 #include "source_array.hpp"
+#include "source_wave.hpp"
 #include "sponge.hpp"
 #include "stiffness.hpp"
 #include "vecops.hpp"
@@ -274,6 +276,60 @@ int facet_source_array(T* y, const T* cA1, const T* cA2, const T* detJA, const i
   }
   return hip_rc(fus::launch_facet_source_array<T>(y, cA1, cA2, detJA, dmA, eid, nA, amp, phase, delay, xB, cB, detJB, dmB, nB, N, st,
                                                   dev ? stage : nullptr, static_cast<hipStream_t>(stream)));
+}
+
+// sampled waveforms (csrc/source_wave.hpp): the table of a launch, checked before any device work
+inline bool wave_table_ok(const double* table, int64_t R, int64_t Nt, double t0, double dt) {
+  // a NaN fails every comparison: dt must be positive and finite, t0 finite
+  return table && R >= 1 && Nt >= 2 && dt > 0.0 && dt <= 1.7976931348623157e308 && t0 >= -1.7976931348623157e308 &&
+         t0 <= 1.7976931348623157e308 && !misaligned(table, 16);
+}
+
+// point sources with a sampled waveform (csrc/source_wave.hpp): point_source with the value read from the table
+template <typename T>
+int point_source_wave(T* y, const int32_t* cells, int64_t npts, const int32_t* dofmap, int64_t ncells, const T* weights, int P,
+                      const double* amp, const double* delay, const int32_t* row_of, const double* table, int64_t R, int64_t Nt,
+                      double t0, double dt, const double* stage, void* stream) {
+  if (npts < 0 || ncells < 0) return FUS_ERR_INVALID_ARGUMENT;
+  if (P < FUS_MIN_DEGREE || P > FUS_MAX_DEGREE) return FUS_ERR_UNSUPPORTED_DEGREE;
+  if (npts == 0) return FUS_OK;
+  if (!y || !cells || !dofmap || !weights || !amp || !delay || !row_of || !stage) return FUS_ERR_INVALID_ARGUMENT;
+  if (!wave_table_ok(table, R, Nt, t0, dt)) return FUS_ERR_INVALID_ARGUMENT;
+  if (misaligned(y, sizeof(T)) || misaligned(weights, sizeof(T)) || misaligned(cells, sizeof(int32_t)) ||
+      misaligned(dofmap, sizeof(int32_t)) || misaligned(row_of, sizeof(int32_t)) || misaligned(stage, sizeof(double)) ||
+      misaligned(amp, sizeof(double)) || misaligned(delay, sizeof(double)))
+    return FUS_ERR_INVALID_ARGUMENT;
+  const fus::SourceStage st{stage[0], stage[1], stage[2], stage[3], stage[4], stage[5]};
+  const fus::WaveTable wt{table, R, Nt, t0, dt};
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  hipError_t e = hipErrorInvalidValue;
+  degree_dispatch(P, [&](auto p) {
+    e = fus::launch_point_source_wave<T, decltype(p)::value>(y, cells, dofmap, weights, npts, ncells, amp, delay, row_of, wt, st, s);
+  });
+  return hip_rc(e);
+}
+
+// source facets with a sampled waveform (csrc/source_wave.hpp): facet_source_array with the element value read from the table
+template <typename T>
+int facet_source_wave(T* y, const T* cA1, const T* cA2, const T* detJA, const int32_t* dmA, const int32_t* eid, int64_t nA,
+                      const double* amp, const double* delay, const int32_t* row_of, int64_t E, const double* table, int64_t R,
+                      int64_t Nt, double t0, double dt, const T* xB, const T* cB, const T* detJB, const int32_t* dmB, int64_t nB, int N,
+                      const double* stage, bool dev, void* stream) {
+  if (nA < 0 || nB < 0 || E < 0 || N < 1) return FUS_ERR_INVALID_ARGUMENT;
+  if (nA == 0 && nB == 0) return FUS_OK;
+  if (!y || !stage) return FUS_ERR_INVALID_ARGUMENT;
+  if (nA > 0 && (E < 1 || !cA1 || !detJA || !dmA || !eid || !amp || !delay || !row_of || !wave_table_ok(table, R, Nt, t0, dt)))
+    return FUS_ERR_INVALID_ARGUMENT;
+  if (nB > 0 && (!xB || !cB || !detJB || !dmB)) return FUS_ERR_INVALID_ARGUMENT;
+  if (misaligned(y, sizeof(T)) || misaligned(stage, sizeof(double)) || misaligned(amp, sizeof(double)) ||
+      misaligned(delay, sizeof(double)) || misaligned(eid, sizeof(int32_t)) || misaligned(row_of, sizeof(int32_t)))
+    return FUS_ERR_INVALID_ARGUMENT;
+  fus::SourceStage st{0.0, 0.0, 0.0, 1.0, 1.0, 0.0};
+  if (!dev) st = fus::SourceStage{stage[0], stage[1], stage[2], stage[3], stage[4], stage[5]};
+  // without set A the table is not read: R = 0 makes every row a silent one
+  const fus::WaveTable wt{table, nA > 0 ? R : 0, Nt, t0, dt};
+  return hip_rc(fus::launch_facet_source_wave<T>(y, cA1, cA2, detJA, dmA, eid, nA, amp, delay, row_of, wt, xB, cB, detJB, dmB, nB, N, st,
+                                                 dev ? stage : nullptr, static_cast<hipStream_t>(stream)));
 }
 
 // boundary facet terms (csrc/mass.hpp); the two scalars by value or, with ``dev``, from device memory
@@ -775,5 +831,32 @@ int fus_plan_mark_exclusive(void* workspace, int N, int entities_per_batch, int6
 FUS_TYPED(double, f64)
 FUS_TYPED(float, f32)
 #undef FUS_TYPED
+
+// include/fus_gpu_waveform.h
+#define FUS_WAVE(T, SUF)                                                                                                                   \
+  int fus_facet_source_wave_##SUF(T* y, const T* cA1, const T* cA2, const T* detJA, const int32_t* dmA, const int32_t* element_of_facet,   \
+                                  int64_t nentA, const double* amplitude, const double* delay, const int32_t* row_of_element,              \
+                                  int64_t nelem, const double* table, int64_t nrows, int64_t nt, double t0, double dt, const T* xB,        \
+                                  const T* cB, const T* detJB, const int32_t* dmB, int64_t nentB, int N, const double* stage, void* s) {   \
+    return facet_source_wave<T>(y, cA1, cA2, detJA, dmA, element_of_facet, nentA, amplitude, delay, row_of_element, nelem, table, nrows,   \
+                                nt, t0, dt, xB, cB, detJB, dmB, nentB, N, stage, false, s);                                                \
+  }                                                                                                                                        \
+  int fus_facet_source_wave_dev_##SUF(T* y, const T* cA1, const T* cA2, const T* detJA, const int32_t* dmA,                                \
+                                      const int32_t* element_of_facet, int64_t nentA, const double* amplitude, const double* delay,        \
+                                      const int32_t* row_of_element, int64_t nelem, const double* table, int64_t nrows, int64_t nt,        \
+                                      double t0, double dt, const T* xB, const T* cB, const T* detJB, const int32_t* dmB, int64_t nentB,   \
+                                      int N, const double* stage_dev, void* s) {                                                           \
+    return facet_source_wave<T>(y, cA1, cA2, detJA, dmA, element_of_facet, nentA, amplitude, delay, row_of_element, nelem, table, nrows,   \
+                                nt, t0, dt, xB, cB, detJB, dmB, nentB, N, stage_dev, true, s);                                             \
+  }                                                                                                                                        \
+  int fus_point_source_wave_##SUF(T* y, const int32_t* cells, int64_t npts, const int32_t* dofmap, int64_t ncells, const T* weights,       \
+                                  int P, const double* amplitude, const double* delay, const int32_t* row_of_point, const double* table,   \
+                                  int64_t nrows, int64_t nt, double t0, double dt, const double* stage, void* s) {                         \
+    return point_source_wave<T>(y, cells, npts, dofmap, ncells, weights, P, amplitude, delay, row_of_point, table, nrows, nt, t0, dt,      \
+                                stage, s);                                                                                                 \
+  }
+FUS_WAVE(double, f64)
+FUS_WAVE(float, f32)
+#undef FUS_WAVE
 
 }  // extern "C"

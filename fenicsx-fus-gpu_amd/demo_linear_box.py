@@ -9,6 +9,9 @@ replaces dolfinx's ``create_box``.
     python fenicsx-fus-gpu_amd/demo_linear_box.py --array 8,8 --focus 0.06,0.05,0.06     # phased array focused on a point
     python fenicsx-fus-gpu_amd/demo_linear_box.py --length 0.012 --cells 8 --time-reversal 0.011 0.0063 0.0058 --elements 3 3
                                                    # listen to a virtual source at the focus through an aberrating slab, fire back
+    python fenicsx-fus-gpu_amd/demo_linear_box.py --length 0.012 --cells 8 --time-reversal 0.011 0.0063 0.0058 --elements 3 3 --pulse 3
+                                                   # the same with a 3-cycle pulse: re-emit the recorded SIGNALS reversed in time
+    python fenicsx-fus-gpu_amd/demo_linear_box.py --source-waveform rows.npy 2.5e-8       # drive the source with sampled rows [R, Nt]
     python fenicsx-fus-gpu_amd/demo_linear_box.py --nodal-lens                             # c and rho given at the dofs: a smooth inclusion
     python -m torch.distributed.run --nproc-per-node 8 fenicsx-fus-gpu_amd/demo_linear_box.py   # one rank per GPU
 
@@ -62,10 +65,25 @@ def main():
                     help="a nodal medium (nodal_medium.NodalMedium): c and rho given at the dofs, not per cell -- a smooth Gaussian inclusion "
                          "(c 1500 -> 1800 m/s, rho 1000 -> 1200 kg/m^3, radius L/6) at the centre of the box; the stiffness apply takes 1/rho "
                          "inside its contraction (csrc/stiffness_geom_nodal.hpp).  Composes with --sponge, --array, --power-law and ranks")
+    ap.add_argument("--pulse", type=float, default=None, metavar="CYCLES",
+                    help="--time-reversal with a Gaussian-modulated pulse of CYCLES cycles instead of a continuous wave: the virtual source "
+                         "emits the pulse from a table (sources.SampledWaveform), the elements record every step, and the array re-emits the "
+                         "recorded signals reversed in time (receivers.time_reversed_waveform); prints the refocus time and the peak at the "
+                         "focus against the same pulse fired with geometric delays.  Without --pulse: the harmonic phases")
+    ap.add_argument("--source-waveform", nargs=2, default=None, metavar=("FILE.npy", "DT"),
+                    help="drive the source with the sampled rows of FILE.npy ([Nt] or [R, Nt], sample interval DT seconds, first sample at "
+                         "t = 0, zero after the last; sources.SampledWaveform) instead of the analytic waveform: the whole source face "
+                         "(R = 1) or, with --array, its elements (R = 1 or one row per element, on top of the focusing delays)")
     ap.add_argument("--elements", type=int, nargs=2, default=(4, 4), metavar=("NY", "NZ"), help="elements of the --time-reversal array (default 4 4)")
     a = ap.parse_args()
     if a.focus and not a.array:
         ap.error("--focus needs --array")
+    if a.pulse is not None and not a.time_reversal:
+        ap.error("--pulse needs --time-reversal")
+    if a.pulse is not None and not a.pulse > 0.0:
+        ap.error("--pulse: a positive number of cycles")
+    if a.source_waveform and a.time_reversal:
+        ap.error("--time-reversal builds its own sources")
     if a.time_reversal and a.nodal_lens:
         ap.error("--time-reversal builds its own (per-cell) medium")
     if a.time_reversal and (a.array or int(os.environ.get("WORLD_SIZE", "1")) > 1):
@@ -123,6 +141,18 @@ def main():
         axis = np.stack([np.linspace(0.0, L, 64), np.full(64, focus[1]), np.full(64, focus[2])], axis=1)
         pts = np.concatenate([focus[None, :], axis])
         probes = (pts, sens.PointSensors(mesh, pts, float_type, peak=True))
+    if a.source_waveform:
+        src = fusgpu_loader.submodule("sources")
+        try:
+            wf = src.SampledWaveform(np.load(a.source_waveform[0]), float(a.source_waveform[1]))
+            if source is None:  # the scalar source: one element that holds every source facet
+                source = src.SourceArray(lambda cen: np.zeros(len(cen), dtype=np.int64), n_elements=1, waveform=wf)
+            else:
+                source = src.SourceArray(source.element_of_facet, delay=source.delay, n_elements=source.n_elements, waveform=wf)
+        except (OSError, ValueError) as e:
+            raise SystemExit(f"--source-waveform: {e}") from None
+        if rank == 0:
+            print(f"Source waveform: {wf.n_rows} row(s) of {wf.n_samples} samples every {wf.dt:g} s (until t = {wf.t_end:g} s)", flush=True)
     sponge = None
     if a.sponge:
         sp = fusgpu_loader.submodule("sponge")
@@ -236,6 +266,8 @@ def time_reversal_run(a, mesh, sponge, float_type, c0, density, f0, p0):
     grid = src.grid_elements(ny, nz, (0.0, L[1]), (0.0, L[2]))
     print(f"Time reversal: focus {tuple(float(v) for v in focus[0])}, {ny} x {nz} elements, slab of {int(slab.sum())} cells at c = {2.0 * c0}, "
           f"{int(round(tf / dt))} steps per run", flush=True)
+    if a.pulse is not None:
+        return pulse_reversal_run(a, mesh, kw, grid, focus, float_type, c0, f0, p0, dt)
     listen = ls.LinearSpectral3D(mesh, float_type, source_amplitude=0.0, point_source=src.PointSources(focus), **kw)
     rx = rxm.ElementReceivers(mesh, grid, float_type, harmonics=(1,), frequency=f0, n_elements=ny * nz, detJ=listen.detJ_f1)
     listen.init()
@@ -255,6 +287,45 @@ def time_reversal_run(a, mesh, sponge, float_type, c0, density, f0, p0):
     bound = s.p0 * s.w0 / s.c0 / density * float(np.sum(rx.areas() * np.abs(R)))  # reciprocity: sum_e |G_e|
     print(f"First-harmonic amplitude at the focus: time reversal {a_tr:.6g}, geometric (focus_phases) {a_geo:.6g}")
     print(f"Time-reversal gain over the geometric phases: {a_tr / a_geo:.3f} ({a_tr / bound:.3f} of the reciprocity bound {bound:.6g})")
+
+
+def pulse_reversal_run(a, mesh, kw, grid, focus, float_type, c0, f0, p0, dt):
+    """--time-reversal --pulse: the listen, reverse and transmit chain with the signals themselves.  The virtual source emits
+    exp(-((t - t_c) / sigma)^2 / 2) cos(w0 (t - t_c)), 4 sigma = CYCLES periods, from a table; every element records every step; the
+    array re-emits row e reversed in time, and the pressure at the focus peaks at T_run - t_c."""
+    import fusgpu_loader
+
+    ls, src, rxm, sens = (fusgpu_loader.submodule(m) for m in ("linear_solver", "sources", "receivers", "sensors"))
+    L, period = mesh.length, 1.0 / f0
+    ny, nz = a.elements
+    sigma = 0.25 * a.pulse * period
+    t_c = 4.0 * sigma
+    nsteps = int(np.ceil((2.0 * t_c + 1.5 * L[0] / c0 + 2.0 * period) / dt))  # the pulse, the transit with room for the slab's echoes
+    if a.max_steps is not None:
+        nsteps = min(nsteps, a.max_steps)
+    t_run = nsteps * dt
+    t = np.arange(nsteps + 2) * dt
+    pulse = src.SampledWaveform(np.exp(-0.5 * ((t - t_c) / sigma) ** 2) * np.cos(2.0 * np.pi * f0 * (t - t_c)), dt)
+    listen = ls.LinearSpectral3D(mesh, float_type, source_amplitude=0.0, point_source=src.PointSources(focus, waveform=pulse), **kw)
+    rx = rxm.ElementReceivers(mesh, grid, float_type, capacity=nsteps, n_elements=ny * nz, detJ=listen.detJ_f1)
+    listen.init()
+    listen.rk4(0.0, t_run + dt, dt, max_steps=nsteps, receivers=rx)
+
+    def transmit(array):
+        s = ls.LinearSpectral3D(mesh, float_type, source_amplitude=p0, source=array, **kw)
+        probe = sens.PointSensors(mesh, focus, float_type, capacity=nsteps)
+        s.init()
+        s.rk4(0.0, t_run + dt, dt, max_steps=nsteps, sensors=probe)
+        p = np.abs(probe.series()[:, 0])
+        k = int(np.argmax(p))
+        return float(p[k]), (k + 1) * dt
+
+    p_tr, t_tr = transmit(rxm.time_reversed_waveform(rx, dt, taper=0.05))
+    centres = src.grid_centres(ny, nz, 0.0, (0.0, L[1]), (0.0, L[2]))
+    p_geo, _ = transmit(src.SourceArray(grid, delay=src.focus_delays(centres, focus[0], c0), n_elements=ny * nz, waveform=pulse))
+    print(f"Pulse of {a.pulse:g} cycles centred at t_c = {t_c:.6g} s; {nsteps} steps per run, T_run = {t_run:.6g} s")
+    print(f"Refocus time: {t_tr:.6g} s (expected T_run - t_c = {t_run - t_c:.6g} s, {abs(t_tr - (t_run - t_c)) / period:.3f} periods off)")
+    print(f"Peak |p| at the focus: time-reversed signals {p_tr:.6g}, geometric delays (focus_delays) {p_geo:.6g}, ratio {p_tr / p_geo:.3f}")
 
 
 if __name__ == "__main__":

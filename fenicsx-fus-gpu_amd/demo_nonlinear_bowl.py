@@ -79,6 +79,11 @@ def main():
                          "inclusion (c 1480 -> 1780 m/s, rho 1000 -> 1200 kg/m^3, beta 3.5 -> 5, alpha 0.2 -> 5 dB/m, radius L/6) at the centre "
                          "of the box; the cell pass takes 1/rho and delta/(rho c^2) inside its two contractions "
                          "(csrc/westervelt_geom_nodal.hpp).  Composes with --sponge, --array, --field-stats, --intensity, --thermal and ranks")
+    ap.add_argument("--source-waveform", nargs=2, default=None, metavar=("FILE.npy", "DT"),
+                    help="drive the source with the sampled rows of FILE.npy ([Nt] or [R, Nt], sample interval DT seconds, first sample at "
+                         "t = 0, zero after the last; sources.SampledWaveform) instead of the analytic waveform: the whole bowl (R = 1) or, "
+                         "with --array, its elements (R = 1 or one row per element, on top of the focusing delays).  The interpolant's "
+                         "derivative is the dg/dt of the Westervelt source term")
     a = ap.parse_args()
     if a.nodal_lens and (a.power_law or a.geometry == "array"):
         ap.error("--nodal-lens: the nodal cell pass forms G in the kernel (not --geometry array), and --power-law fits its own attenuation")
@@ -165,6 +170,18 @@ def main():
                                  n_elements=ny * nz)
         if rank == 0:
             print(f"Array elements: {ny} x {nz}, focus: {tuple(float(v) for v in focus)}", flush=True)
+    if a.source_waveform:
+        src = fusgpu_loader.submodule("sources")
+        try:
+            wf = src.SampledWaveform(np.load(a.source_waveform[0]), float(a.source_waveform[1]))
+            if source is None:  # the scalar source: one element that holds every source facet
+                source = src.SourceArray(lambda cen: np.zeros(len(cen), dtype=np.int64), n_elements=1, waveform=wf)
+            else:
+                source = src.SourceArray(source.element_of_facet, delay=source.delay, n_elements=source.n_elements, waveform=wf)
+        except (OSError, ValueError) as e:
+            raise SystemExit(f"--source-waveform: {e}") from None
+        if rank == 0:
+            print(f"Source waveform: {wf.n_rows} row(s) of {wf.n_samples} samples every {wf.dt:g} s (until t = {wf.t_end:g} s)", flush=True)
     sponge = None
     if a.sponge:
         sp = fusgpu_loader.submodule("sponge")

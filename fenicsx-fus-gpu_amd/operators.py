@@ -589,7 +589,11 @@ def facet_source_terms(y, bound_array, field, stage=None, stage_dev=None):
 
     The stage block ``{t, w0, A, f0, alpha, D}`` (fp64) is ``stage`` (host, ``bound_array.stage_scalars(t)``: copied into
     the launch) or ``stage_dev`` (a float64 device tensor read by the kernel, ``fus_facet_source_array_dev_*``: a captured
-    hipGraph replays with new stage times).  Exactly one of them is given."""
+    hipGraph replays with new stage times).  Exactly one of them is given.
+
+    A bound array that carries a sampled waveform (``bound_array.table``, sources.SampledWaveform) takes the table route
+    (csrc/source_wave.hpp, ``fus_facet_source_wave_*``): ``g_e = a_e A w_r(t - tau_e)`` with ``r = row_of_element[e]``, interpolated
+    in the kernel; same stage block (only ``t`` and ``A`` are read), same ``stage`` / ``stage_dev``."""
     ba = bound_array
     dt = y.dtype if isinstance(y, torch.Tensor) else None
     _req(y, dt, "y")
@@ -605,25 +609,62 @@ def facet_source_terms(y, bound_array, field, stage=None, stage_dev=None):
             _req(t, torch.float64, name)
         if ba.detJ.shape != ba.dofmap.shape or ba.coeff1.numel() != nA or ba.dofmap.shape[0] != nA:
             raise ValueError("source facet arrays: detJ must have the dofmap's shape, one constant and one element id per facet")
+    wave = getattr(ba, "table", None) is not None
+    if wave:
+        wave_args = _wave_table(ba, ba.array.waveform, ba.table, ba.row_of_element, ba.n_elements, y.device, "row_of_element")
     pB, nB, N = _facet_field(dt, field, ba.dofmap.shape[1] if nA else None)
     if nA + nB == 0:
         return
     if (stage is None) == (stage_dev is None):
         raise ValueError("facet_source_terms: give exactly one of stage (host) and stage_dev (device)")
-    args = [y.data_ptr(), *_ptrs(nA, ba.coeff1, ba.coeff2, ba.detJ, ba.dofmap, ba.element_of_facet), int(nA),
-            *_ptrs(nA, ba.amplitude, ba.phase, ba.delay), int(ba.n_elements), *pB, int(nB), int(N)]
+    args = [y.data_ptr(), *_ptrs(nA, ba.coeff1, ba.coeff2, ba.detJ, ba.dofmap, ba.element_of_facet), int(nA)]
+    if wave:
+        args += [*_ptrs(nA, ba.amplitude, ba.delay, ba.row_of_element), int(ba.n_elements), *wave_args, *pB, int(nB), int(N)]
+        family = "fus_facet_source_wave"
+    else:
+        args += [*_ptrs(nA, ba.amplitude, ba.phase, ba.delay), int(ba.n_elements), *pB, int(nB), int(N)]
+        family = "fus_facet_source_array"
     if stage_dev is not None:
         _req(stage_dev, torch.float64, "stage_dev")
         if stage_dev.numel() < 6:
             raise ValueError("stage_dev must hold {t, w0, A, f0, alpha, D}")
-        fn = getattr(_lib.load(), f"fus_facet_source_array_dev_{_lib.suffix(dt)}")
-        _lib.check(fn(*args, stage_dev.data_ptr(), _lib.stream_ptr()), "fus_facet_source_array_dev")
+        fn = getattr(_lib.load(), f"{family}_dev_{_lib.suffix(dt)}")
+        _lib.check(fn(*args, stage_dev.data_ptr(), _lib.stream_ptr()), f"{family}_dev")
         return
     st = np.ascontiguousarray(np.asarray(stage, dtype=np.float64).reshape(-1))
     if st.size < 6:
         raise ValueError("stage must hold {t, w0, A, f0, alpha, D}")
-    fn = getattr(_lib.load(), f"fus_facet_source_array_{_lib.suffix(dt)}")
-    _lib.check(fn(*args, st.ctypes.data, _lib.stream_ptr()), "fus_facet_source_array")
+    fn = getattr(_lib.load(), f"{family}_{_lib.suffix(dt)}")
+    _lib.check(fn(*args, st.ctypes.data, _lib.stream_ptr()), family)
+
+
+def _wave_table(holder, wf, table, row_of, n, device, name):
+    """The table arguments ``(table, R, Nt, t0, dt)`` of the sampled-waveform entry points (csrc/source_wave.hpp), checked: ``table``
+    fp64 ``[R, Nt, 2]`` with the ``Nt`` of the waveform ``wf``, 16-byte aligned, ``row_of`` int32 ``[n]`` with entries in ``[-1, R)``, both
+    on ``device``.  The launch is launch-bound and runs four times per step, so the bound object ``holder`` remembers the two tensors
+    it was checked with: the checks (the range check reads the map back) run again only when one of them is replaced."""
+    seen = holder.__dict__.get("_wave_checked")
+    if seen is not None and seen[0] is table and seen[1] is row_of and seen[2] == device:
+        return seen[3]
+    _req(table, torch.float64, "waveform table")
+    _req(row_of, torch.int32, name)
+    if table.dim() != 3 or table.shape[0] < 1 or table.shape[1] != wf.n_samples or table.shape[1] < 2 or table.shape[2] != 2:
+        raise ValueError(f"waveform table: [R, {wf.n_samples}, 2] (value and derivative interleaved), got {tuple(table.shape)}")
+    if row_of.shape != (n,):
+        raise ValueError(f"{name}: one row per entry ({n}), got shape {tuple(row_of.shape)}")
+    if table.device != device or row_of.device != device:
+        raise ValueError("the waveform table and its row map must be on y's device")
+    if table.data_ptr() % 16:
+        raise ValueError("waveform table: must be 16-byte aligned")
+    R = int(table.shape[0])
+    args = [table.data_ptr(), R, int(table.shape[1]), float(wf.t0), float(wf.dt)]
+    # (while a graph is captured the read-back would end the capture: the range is then checked by the next launch outside one; the
+    # kernel skips a row outside [0, R) in any case)
+    if not torch.cuda.is_current_stream_capturing():
+        if n and (int(row_of.min()) < -1 or int(row_of.max()) >= R):
+            raise ValueError(f"{name}: rows must lie in [-1, {R})")
+        holder._wave_checked = (table, row_of, device, args)
+    return args
 
 
 def sponge_terms(y, u, v, bound):
@@ -703,7 +744,10 @@ def point_source_terms(y, bound, stage):
         y[rows[cells[p]][ijk]] += g_p(t) Lx[i] Ly[j] Lz[k]
 
     ``y`` is the stage's right-hand side.  The adds are float atomics (points may share dofs; next to a halo the launch runs while
-    the interior cells add into the same y).  No points is a no-op."""
+    the interior cells add into the same y).  No points is a no-op.
+
+    Bound point sources that carry a sampled waveform (``bound.table``) take the table route (csrc/source_wave.hpp,
+    ``fus_point_source_wave_*``): ``g_p = a_p A w_r(t - tau_p)`` with ``r = row_of_point[p]``."""
     bp = bound
     dt = y.dtype if isinstance(y, torch.Tensor) else None
     _req(y, dt, "y")
@@ -723,11 +767,20 @@ def point_source_terms(y, bound, stage):
         raise ValueError(f"point_source_terms: y has {y.numel()} entries, the dofmap rows were checked against {bp.ndofs}")
     if any(t.device != y.device for t in (bp.weights, bp.cells, bp.rows, bp.amplitude, bp.phase, bp.delay)):
         raise ValueError("point_source_terms: every operand must be on y's device")
+    wave = getattr(bp, "table", None) is not None
+    if wave:
+        wave_args = _wave_table(bp, bp.sources.waveform, bp.table, bp.row_of_point, m, y.device, "row_of_point")
     if m == 0:
         return
     st = np.ascontiguousarray(np.asarray(stage, dtype=np.float64).reshape(-1))
     if st.size < 6:
         raise ValueError("stage must hold {t, w0, A, f0, alpha, D}")
+    if wave:
+        fn = getattr(_lib.load(), f"fus_point_source_wave_{_lib.suffix(dt)}")
+        _lib.check(fn(y.data_ptr(), bp.cells.data_ptr(), int(m), bp.rows.data_ptr(), int(bp.rows.shape[0]), bp.weights.data_ptr(),
+                      int(bp.P), bp.amplitude.data_ptr(), bp.delay.data_ptr(), bp.row_of_point.data_ptr(), *wave_args, st.ctypes.data,
+                      _lib.stream_ptr()), "fus_point_source_wave")
+        return
     fn = getattr(_lib.load(), f"fus_point_source_{_lib.suffix(dt)}")
     _lib.check(fn(y.data_ptr(), bp.cells.data_ptr(), int(m), bp.rows.data_ptr(), int(bp.rows.shape[0]), bp.weights.data_ptr(), int(bp.P),
                   bp.amplitude.data_ptr(), bp.phase.data_ptr(), bp.delay.data_ptr(), st.ctypes.data, _lib.stream_ptr()),

@@ -167,3 +167,45 @@ def time_reversal(receivers_or_harmonic, harmonic=1, amplitude="uniform", durati
     phi = np.pi - np.mod(np.pi - phi, 2.0 * np.pi)
     amp = mag / mag.max() if amplitude == "conjugate" else heard.astype(np.float64)
     return SourceArray(element_of_facet, amplitude=amp, phase=np.where(heard, phi, 0.0), duration=duration, n_elements=R.size)
+
+
+def time_reversed_waveform(receivers_or_series, dt, element_of_facet=None, taper=0.0, amplitude="uniform"):
+    """The ``SourceArray`` that re-emits the recorded SIGNALS reversed in time (``time_reversal`` fires one conjugate phase per element
+    at one harmonic; this is the broadband form, which refocuses a pulse through a reverberating medium): element e emits row e of
+    ``sources.SampledWaveform(series[::-1].T, dt, t0=0)``, i.e. ``w_e(s) = S_e(T_rec - s)`` with ``T_rec = (nrec - 1) dt`` -- an
+    ``ElementReceivers`` (one rank: its ``series()`` and its ``element_of_facet``) or the merged ``[nrec, E]`` array itself
+    (``element_of_facet`` is then required).  ``dt``: the recording interval.  ``amplitude``: ``"uniform"`` (each row divided by its own
+    largest absolute value) or ``"recorded"`` (every row divided by the largest over all elements: the relative levels are kept).
+    ``taper``: the fraction of the window, at each end, that is multiplied by a cosine ramp (0: none, at most 0.5).  An element that
+    heard nothing (all zero, or NaN: no facets) gets row -1, a silent element."""
+    from .sources import SampledWaveform
+
+    if amplitude not in ("uniform", "recorded"):
+        raise ValueError(f"amplitude must be 'uniform' or 'recorded', got {amplitude!r}")
+    taper = float(taper)
+    if not 0.0 <= taper <= 0.5:
+        raise ValueError(f"taper must lie in [0, 0.5], got {taper}")
+    if isinstance(receivers_or_series, ElementReceivers):
+        S = receivers_or_series.series()
+        element_of_facet = receivers_or_series.element_of_facet if element_of_facet is None else element_of_facet
+    else:
+        S = np.asarray(receivers_or_series, dtype=np.float64)
+    if element_of_facet is None:
+        raise ValueError("time_reversed_waveform: an array of series needs element_of_facet")
+    if S.ndim != 2 or S.shape[0] < 2:
+        raise ValueError(f"time_reversed_waveform: a series [nrec, E] of at least two records, got shape {S.shape}")
+    nrec, E = S.shape
+    finite = np.all(np.isfinite(S), axis=0)
+    rows = np.where(finite[:, None], S[::-1].T, 0.0)  # [E, nrec], reversed in time
+    peak = np.abs(rows).max(axis=1) if E else np.zeros(0)
+    heard = peak > 0.0
+    if not heard.any():
+        raise ValueError("time_reversed_waveform: no element received anything")
+    rows = rows / (np.where(heard, peak, 1.0)[:, None] if amplitude == "uniform" else peak.max())
+    nt = int(round(taper * (nrec - 1)))
+    if nt > 0:
+        ramp = 0.5 * (1.0 - np.cos(np.pi * np.arange(nt) / nt))  # 0 at the end sample, below 1 at sample nt - 1
+        rows[:, :nt] *= ramp
+        rows[:, nrec - nt:] *= ramp[::-1]
+    wf = SampledWaveform(rows, dt, t0=0.0)
+    return SourceArray(element_of_facet, waveform=wf, waveform_of_element=np.where(heard, np.arange(E), -1), n_elements=E)

@@ -61,6 +61,158 @@ def _waveform(t, frequency, scale, amplitude, phase, delay, duration, alpha=ALPH
     return env * a * cs, denv * a * cs - env * a * w0 * sn
 
 
+def stencil_derivative(f, dt):
+    """``df/ds`` at the samples of ``f`` [..., Nt] (interval ``dt``), fourth order: the five-point central stencil, and at the first
+    two and the last two samples the one-sided five-point stencils (no zero padding: a table that does not end at 0 would get a
+    derivative error that grows like 1 / dt).  Fewer than five samples leave no five-point stencil: second-order differences then
+    (``Nt`` 3 or 4), the one difference quotient for ``Nt = 2``."""
+    f = np.asarray(f, dtype=np.float64)
+    Nt = f.shape[-1]
+    if Nt < 5:
+        return np.gradient(f, float(dt), axis=-1, edge_order=2 if Nt >= 3 else 1)
+    d = np.empty_like(f)
+    d[..., 2:-2] = (f[..., :-4] - 8.0 * f[..., 1:-3] + 8.0 * f[..., 3:-1] - f[..., 4:]) / 12.0
+    d[..., 0] = (-25.0 * f[..., 0] + 48.0 * f[..., 1] - 36.0 * f[..., 2] + 16.0 * f[..., 3] - 3.0 * f[..., 4]) / 12.0
+    d[..., 1] = (-3.0 * f[..., 0] - 10.0 * f[..., 1] + 18.0 * f[..., 2] - 6.0 * f[..., 3] + f[..., 4]) / 12.0
+    d[..., -1] = (25.0 * f[..., -1] - 48.0 * f[..., -2] + 36.0 * f[..., -3] - 16.0 * f[..., -4] + 3.0 * f[..., -5]) / 12.0
+    d[..., -2] = (3.0 * f[..., -1] + 10.0 * f[..., -2] - 18.0 * f[..., -3] + 6.0 * f[..., -4] - f[..., -5]) / 12.0
+    return d / float(dt)
+
+
+class SampledWaveform:
+    """An arbitrary source signal per row, sampled: ``wf = SampledWaveform(samples, dt, t0=0.0, derivative=None)``.
+
+    ``samples``: ``[R, Nt]`` (or ``[Nt]``: one row), ``R >= 1``, ``Nt >= 2``, finite; ``dt > 0``: the sample interval; ``t0``: the time
+    of sample 0.  Row ``r`` defines ``w_r(s)`` on ``[t0, t0 + (Nt - 1) dt]``; outside that interval it is ZERO.  ``derivative``: ``dw/ds``
+    at the samples, of the shape of ``samples``; ``None`` forms it with ``stencil_derivative`` (fourth order, one-sided at the ends).
+
+    The interpolant is the cubic Hermite of value and derivative on each interval: C1, exact at the nodes, fourth order in the value
+    and third in the derivative, which is the ``dg/dt`` the Westervelt source term needs.  With ``x = (s - t0) / dt``:
+
+        x < 0, x > Nt - 1 or x not a number: nothing is contributed
+        k = min(floor(x), Nt - 2), th = x - k        (the last node: k = Nt - 2, th = 1)
+        w  = h00 w_k + h10 dt d_k + h01 w_{k+1} + h11 dt d_{k+1}
+        dw = (h00' w_k + h01' w_{k+1}) / dt + h10' d_k + h11' d_{k+1}
+        h00 = (1 + 2 th)(1 - th)^2,  h10 = th (1 - th)^2,  h01 = th^2 (3 - 2 th),  h11 = th^2 (th - 1)
+
+    ``values`` is that in numpy (fp64), the arithmetic of the kernels (csrc/source_wave.hpp); ``table`` is what they read,
+    ``double[R][Nt][2]``, value and derivative interleaved."""
+
+    def __init__(self, samples, dt, t0=0.0, derivative=None):
+        w = np.asarray(samples, dtype=np.float64)
+        if w.ndim == 1:
+            w = w[None, :]
+        if w.ndim != 2 or w.shape[0] < 1:
+            raise ValueError(f"samples: [R, Nt] or [Nt], got shape {np.shape(samples)}")
+        if w.shape[1] < 2:
+            raise ValueError(f"samples: at least two samples per row (Nt >= 2), got Nt = {w.shape[1]}")
+        if not np.all(np.isfinite(w)):
+            raise ValueError("samples: values must be finite")
+        dt, t0 = float(dt), float(t0)
+        if not (np.isfinite(dt) and dt > 0.0):
+            raise ValueError(f"dt must be a positive number of seconds, got {dt}")
+        if not np.isfinite(t0):
+            raise ValueError(f"t0 must be finite, got {t0}")
+        if derivative is None:
+            d = stencil_derivative(w, dt)
+        else:
+            d = np.asarray(derivative, dtype=np.float64)
+            if d.ndim == 1:
+                d = d[None, :]
+            if d.shape != w.shape:
+                raise ValueError(f"derivative: the shape of samples {w.shape}, got {d.shape}")
+            if not np.all(np.isfinite(d)):
+                raise ValueError("derivative: values must be finite")
+        self.samples, self.derivative = np.ascontiguousarray(w), np.ascontiguousarray(d)
+        self.dt, self.t0 = dt, t0
+        self.n_rows, self.n_samples = int(w.shape[0]), int(w.shape[1])
+
+    @property
+    def t_end(self):
+        return self.t0 + (self.n_samples - 1) * self.dt
+
+    def table(self, rows=None):
+        """``double[R'][Nt][2]`` of ``rows`` (default: every row), value and derivative interleaved: what the kernels read."""
+        rows = slice(None) if rows is None else np.asarray(rows, dtype=np.int64)
+        return np.ascontiguousarray(np.stack([self.samples[rows], self.derivative[rows]], axis=-1))
+
+    def values(self, s, rows=0):
+        """``(w, dw)`` of row ``rows`` at time ``s`` (broadcast against each other), fp64; a row outside ``[0, R)`` is silent (zero)."""
+        s, rows = np.broadcast_arrays(np.asarray(s, dtype=np.float64), np.asarray(rows, dtype=np.int64))
+        Nt, dt = self.n_samples, self.dt
+        x = (s - self.t0) / dt
+        with np.errstate(invalid="ignore"):
+            live = (x >= 0.0) & (x <= float(Nt - 1)) & (rows >= 0) & (rows < self.n_rows)
+        w, dw = np.zeros(s.shape), np.zeros(s.shape)
+        if live.any():
+            xl, r = x[live], rows[live]
+            k = np.minimum(xl.astype(np.int64), Nt - 2)
+            th = xl - k
+            wk, dk, wk1, dk1 = self.samples[r, k], self.derivative[r, k], self.samples[r, k + 1], self.derivative[r, k + 1]
+            um = 1.0 - th
+            h00, h10 = (1.0 + 2.0 * th) * (um * um), th * (um * um)
+            h01, h11 = (th * th) * (3.0 - 2.0 * th), (th * th) * (th - 1.0)
+            w[live] = h00 * wk + h10 * (dt * dk) + h01 * wk1 + h11 * (dt * dk1)
+            d00, d10, d11 = 6.0 * th * (th - 1.0), um * (1.0 - 3.0 * th), th * (3.0 * th - 2.0)
+            dw[live] = (d00 * wk - d00 * wk1) / dt + d10 * dk + d11 * dk1
+        return w, dw
+
+    @classmethod
+    def from_pressure(cls, p, dt, p0, f0, t0=0.0):
+        """The waveform that makes the source facets emit the surface pressure ``p`` [R, Nt] (or [Nt]), sampled every ``dt``: the
+        facet source term is ``(1 / c0) dp/dt``, and the solvers' source constant is ``A = p0 w0 / c0`` (which is why today's source
+        multiplies a cosine), so ``w = (dp/dt) / (p0 2 pi f0)``, with ``dp/dt`` from ``stencil_derivative``."""
+        p = np.asarray(p, dtype=np.float64)
+        if not np.all(np.isfinite(p)):
+            raise ValueError("p: values must be finite")
+        if not (float(p0) > 0.0 and float(f0) > 0.0):
+            raise ValueError("p0 and f0 must be positive")
+        return cls(stencil_derivative(np.atleast_2d(p), dt) / (float(p0) * 2.0 * np.pi * float(f0)), dt, t0=t0)
+
+
+def _row_map(row_of, n, wf, name, what):
+    """The row of the waveform per element / point, int64 [n]: ``row_of`` checked against ``[-1, R)`` (-1: silent) or, when None, row
+    0 for everyone (``R == 1``) or the identity (``R == n``)."""
+    R = wf.n_rows
+    if row_of is None:
+        if R == 1:
+            return np.zeros(n, dtype=np.int64)
+        if R == n:
+            return np.arange(n, dtype=np.int64)
+        raise ValueError(f"{name}: a waveform of {R} rows for {n} {what} needs a row per {what[:-1]} (R is neither 1 nor {n})")
+    rows = np.asarray(row_of)
+    if rows.shape != (n,) or not np.issubdtype(rows.dtype, np.integer):
+        raise ValueError(f"{name}: one integer row per {what[:-1]} ({n}), got shape {rows.shape}, dtype {rows.dtype}")
+    if rows.size and (rows.min() < -1 or rows.max() >= R):
+        raise ValueError(f"{name}: rows must lie in [-1, {R}), got [{rows.min()}, {rows.max()}]")
+    return rows.astype(np.int64)
+
+
+def _check_waveform(wf, phase, duration):
+    if not isinstance(wf, SampledWaveform):
+        raise ValueError(f"waveform: a SampledWaveform, got {type(wf).__name__}")
+    if duration is not None or np.any(np.asarray(phase, dtype=np.float64) != 0.0):
+        raise ValueError("phase and duration belong to the analytic waveform: with waveform= they must keep their defaults")
+
+
+def _sampled_values(wf, rows, t, scale, amplitude, delay):
+    """Host ``(g, dg/dt)`` per element / point of a sampled source: ``g = a A w_r(t - tau)``."""
+    w, dw = wf.values(float(t) - delay, rows)
+    a = amplitude * float(scale)
+    return a * w, a * dw
+
+
+def _upload_rows(wf, rows, used):
+    """The table of the rows that the elements / points ``used`` (bool mask) refer to, and ``rows`` renumbered into it (int32; an
+    element that is not used, or silent, gets -1): a rank uploads the rows its own facets or points use.  A rank that uses none
+    uploads row 0, which nothing refers to (the entry points want a table)."""
+    live = used & (rows >= 0)
+    keep = np.unique(rows[live])
+    local = np.full(rows.shape, -1, dtype=np.int32)
+    local[live] = np.searchsorted(keep, rows[live]).astype(np.int32)
+    return wf.table(keep if keep.size else [0]), local
+
+
 def facet_centroids(mesh, facets):
     """``[m, 3]`` centroids of the boundary facets ``facets`` (``(cell, local facet)`` rows): the mean of the facet's four
     vertices, from ``x_dofs`` / ``x_g`` (any mesh the solvers take: ``BoxMesh``, ``dolfinx_adaptor.ArrayMesh``)."""
@@ -92,9 +244,15 @@ class SourceArray:
 
     ``amplitude`` / ``phase`` (radians) / ``delay`` (seconds): scalars or one value per element; ``duration``: the burst
     length ``D`` in seconds (at least two ramps, ``2 alpha / f0``, checked when bound) or ``None`` (continuous wave);
-    ``n_elements``: ``E`` (default: the length of an array parameter, else the largest id + 1)."""
+    ``n_elements``: ``E`` (default: the length of an array parameter, else the largest id + 1).
 
-    def __init__(self, element_of_facet, amplitude=1.0, phase=0.0, delay=0.0, duration=None, n_elements=None):
+    ``waveform``: a ``SampledWaveform`` instead of the analytic form, ``g_e(t) = a_e A w_{r(e)}(t - tau_e)`` with ``dg_e/dt`` alike
+    (csrc/source_wave.hpp, ``fus_facet_source_wave_*``); ``waveform_of_element``: the row ``r(e)`` per element, int [E] in ``[-1, R)``
+    (-1: a silent element; default: row 0 for every element when ``R == 1``, the identity when ``R == E``).  ``phase`` and ``duration``
+    belong to the analytic form and must keep their defaults then."""
+
+    def __init__(self, element_of_facet, amplitude=1.0, phase=0.0, delay=0.0, duration=None, n_elements=None, waveform=None,
+                 waveform_of_element=None):
         self.element_of_facet = element_of_facet
         if not callable(element_of_facet):
             ids = np.asarray(element_of_facet)
@@ -103,7 +261,8 @@ class SourceArray:
             self.element_of_facet = ids.astype(np.int64)
         E = n_elements
         if E is None:
-            lens = {np.size(v) for v in (amplitude, phase, delay) if np.ndim(v) > 0}
+            lens = {np.size(v) for v in (amplitude, phase, delay) + (() if waveform_of_element is None else (waveform_of_element,))
+                    if np.ndim(v) > 0}
             if len(lens) > 1:
                 raise ValueError(f"per-element parameters of different lengths {sorted(lens)}")
             if lens:
@@ -124,6 +283,12 @@ class SourceArray:
             if not (np.isfinite(duration) and duration > 0.0):
                 raise ValueError(f"duration must be a positive number of seconds or None, got {duration}")
         self.duration = duration
+        self.waveform, self.waveform_of_element = waveform, None
+        if waveform is not None:
+            _check_waveform(waveform, phase, duration)
+            self.waveform_of_element = _row_map(waveform_of_element, E, waveform, "waveform_of_element", "elements")
+        elif waveform_of_element is not None:
+            raise ValueError("waveform_of_element needs waveform=")
 
     # -- host evaluation -----------------------------------------------------------------------
     def check_duration(self, frequency, alpha=ALPHA):
@@ -132,6 +297,8 @@ class SourceArray:
 
     def values(self, t, frequency, scale, alpha=ALPHA):
         """Host ``(g_e(t), dg_e/dt)``, ``[E]`` each, for carrier ``frequency`` and source constant ``scale`` (``A``)."""
+        if self.waveform is not None:
+            return _sampled_values(self.waveform, self.waveform_of_element, t, scale, self.amplitude, self.delay)
         return _waveform(t, frequency, scale, self.amplitude, self.phase, self.delay, self.duration, alpha)
 
     def stage_scalars(self, t, frequency, scale, alpha=ALPHA):
@@ -168,9 +335,13 @@ class SourceArray:
         td = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(device)  # noqa: E731
         if dofmap is None:
             dofmap = td(np.asarray(mesh.facet_dofmap(np.asarray(facets).reshape(-1, 2)), dtype=np.int32))
+        table = rows = None
+        if self.waveform is not None:  # the rows this rank's facets use
+            table, rows = _upload_rows(self.waveform, self.waveform_of_element, np.bincount(ids[ids >= 0], minlength=self.n_elements) > 0)
+            table, rows = td(table), td(rows)
         return BoundSourceArray(self, _lib.torch_dtype(dtype), td(ids), td(self.amplitude), td(self.phase), td(self.delay),
                                 None if frequency is None else float(frequency), None if scale is None else float(scale),
-                                coeff1, coeff2, detJ, dofmap, ids)
+                                coeff1, coeff2, detJ, dofmap, ids, table, rows)
 
 
 @dataclass
@@ -190,6 +361,8 @@ class BoundSourceArray:
     detJ: object = None  # T [m, n^2]
     dofmap: object = None  # int32 [m, n^2]
     ids: np.ndarray = None  # host copy of element_of_facet
+    table: object = None  # float64 [R', Nt, 2] or None: the rows of ``array.waveform`` this rank uses (csrc/source_wave.hpp)
+    row_of_element: object = None  # int32 [E]: the row of ``table`` per element, -1: silent or not on this rank
 
     @property
     def n_elements(self):
@@ -249,9 +422,12 @@ class PointSources:
         solver = LinearSpectral3D(mesh, source_amplitude=0.0, point_source=PointSources(focus))
 
     ``points``: ``[m, 3]`` (or one point); ``amplitude`` / ``phase`` (radians) / ``delay`` (seconds): scalars or one value per point;
-    ``duration``: burst length in seconds or ``None`` (continuous wave), as ``SourceArray``."""
+    ``duration``: burst length in seconds or ``None`` (continuous wave), as ``SourceArray``.
 
-    def __init__(self, points, amplitude=1.0, phase=0.0, delay=0.0, duration=None):
+    ``waveform`` / ``waveform_of_point``: a ``SampledWaveform`` and its row per point, with the rules of ``SourceArray``:
+    ``g_p(t) = a_p w_{r(p)}(t - tau_p)`` (csrc/source_wave.hpp, ``fus_point_source_wave_*``)."""
+
+    def __init__(self, points, amplitude=1.0, phase=0.0, delay=0.0, duration=None, waveform=None, waveform_of_point=None):
         pts = np.asarray(points, dtype=np.float64)
         if pts.ndim == 1 and pts.size == 3:
             pts = pts[None, :]
@@ -269,12 +445,20 @@ class PointSources:
             if not (np.isfinite(duration) and duration > 0.0):
                 raise ValueError(f"duration must be a positive number of seconds or None, got {duration}")
         self.duration = duration
+        self.waveform, self.waveform_of_point = waveform, None
+        if waveform is not None:
+            _check_waveform(waveform, phase, duration)
+            self.waveform_of_point = _row_map(waveform_of_point, m, waveform, "waveform_of_point", "points")
+        elif waveform_of_point is not None:
+            raise ValueError("waveform_of_point needs waveform=")
 
     check_duration = SourceArray.check_duration
     stage_scalars = SourceArray.stage_scalars
 
     def values(self, t, frequency, scale=1.0, alpha=ALPHA):
         """Host ``(g_p(t), dg_p/dt)``, ``[m]`` each, as ``SourceArray.values`` (a one-point source equals a one-element array)."""
+        if self.waveform is not None:
+            return _sampled_values(self.waveform, self.waveform_of_point, t, scale, self.amplitude, self.delay)
         return _waveform(t, frequency, scale, self.amplitude, self.phase, self.delay, self.duration, alpha)
 
     def setup(self, mesh, locator=None):
@@ -316,7 +500,15 @@ class PointSources:
         td = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(device)  # noqa: E731
         return BoundPointSources(self, _lib.torch_dtype(dtype), int(mesh.P), int(mesh.ndofs), ids, td(su.cell_index[keep].astype(np.int32)),
                                  td(su.rows.astype(np.int32).reshape(-1, n**3)), td(su.weights[keep].astype(ft).reshape(-1, 3, n)),
-                                 td(self.amplitude[ids]), td(self.phase[ids]), td(self.delay[ids]), float(frequency))
+                                 td(self.amplitude[ids]), td(self.phase[ids]), td(self.delay[ids]), float(frequency),
+                                 *self._bind_waveform(ids, td))
+
+    def _bind_waveform(self, ids, td):
+        """``(table, row_of_point)`` on the device for the points ``ids`` this rank injects (device order); Nones without a waveform."""
+        if self.waveform is None:
+            return None, None
+        table, rows = _upload_rows(self.waveform, self.waveform_of_point[ids], np.ones(ids.size, dtype=bool))
+        return td(table), td(rows)
 
 
 def claim_points(per_rank, npoints):
@@ -348,6 +540,8 @@ class BoundPointSources:
     phase: object
     delay: object
     frequency: float
+    table: object = None  # float64 [R', Nt, 2] or None: the rows of ``sources.waveform`` this rank's points use
+    row_of_point: object = None  # int32 [m]: the row of ``table`` per point (device order), -1: silent
 
     @property
     def npoints(self):
