@@ -284,7 +284,7 @@ def test_planned_kernel_builds(gpu, oracle_c, P, pv, runs):
     mesh = pb["mesh"]
     y_ref = np.zeros(mesh.ndofs)
     oracle_c.stiffness_apply(P, pb["D"], pb["x"], pb["cc"], y_ref, pb["G"], mesh.dofmap)
-    old = lib.get_tuning(lib.TUNE_PLAN_VARIANT)
+    old, old_runs = lib.get_tuning(lib.TUNE_PLAN_VARIANT), lib.get_tuning(lib.TUNE_PLAN_RUNS)
     try:
         lib.set_tuning(lib.TUNE_PLAN_VARIANT, pv)
         lib.set_tuning(lib.TUNE_PLAN_RUNS, runs)
@@ -307,7 +307,7 @@ def test_planned_kernel_builds(gpu, oracle_c, P, pv, runs):
         _check(y.copy_to_host(), y_ref, np.float64, f"planned mass, runs={runs} P={P}")
     finally:
         lib.set_tuning(lib.TUNE_PLAN_VARIANT, old)
-        lib.set_tuning(lib.TUNE_PLAN_RUNS, 1)
+        lib.set_tuning(lib.TUNE_PLAN_RUNS, old_runs)
         ops._PLANS.clear()
 
 
