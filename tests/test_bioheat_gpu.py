@@ -29,9 +29,10 @@ def _dev(a):
 
 
 # ---- 1. the stage kernel against numpy -----------------------------------------------------------------------------------------
-def _stage_case(kind, dtype, shift, ntotal, nlocal, with_pr, with_s, with_cem, with_tmax, init, seed=0):
+def _stage_case(kind, dtype, shift, ntotal, nlocal, with_pr, with_s, with_cem, with_tmax, init, seed=0, figures=None):
     """Launch one stage through _lib on random operands (every operand sliced ``shift`` elements into its allocation) and check
-    every vector against the fp64 reference: outputs within 8 eps sum|terms|, b zero over [0, ntotal), the rest bitwise."""
+    every vector against the fp64 reference: outputs within 8 eps sum|terms|, b zero over [0, ntotal), the rest bitwise.  Returns
+    every vector as the launch left it."""
     import torch
 
     lib_mod = pkg("_lib")
@@ -90,6 +91,13 @@ def _stage_case(kind, dtype, shift, ntotal, nlocal, with_pr, with_s, with_cem, w
             assert np.all(np.abs(got["cem43"] - own_dose) <= 4 * EPS64 * own_dose)
     for name in set(got) - written:  # untouched outputs and every input: bitwise unchanged
         assert np.array_equal(got[name], cem_host if name == "cem43" else host[name]), f"{name} changed"
+    if figures is not None:  # the largest error as a ratio to its bound, per output (tests/test_stream_builds_gpu.py prints them)
+        for name in ("T0", "Tn", "acc"):
+            if name in ref:
+                figures[name] = float(np.max(np.abs(got[name][:n].astype(np.float64) - ref[name]) / (8 * eps * terms[name])))
+        if kind == 2 and with_cem:
+            figures["cem43"] = float(np.max(np.abs(got["cem43"] - own_dose) / (4 * EPS64 * own_dose)))
+    return got
 
 
 @pytest.mark.parametrize("shift", [0, 1], ids=["aligned", "one-element-in"])

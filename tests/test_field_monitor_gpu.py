@@ -52,7 +52,7 @@ class _Buffers:
         return True
 
 
-def _accumulate(lib, dtype, b, outs, u, v, coef, init):
+def _accumulate(lib, dtype, b, outs, u, v, coef, init, launched=None):
     import torch
 
     fn = getattr(lib, "fus_field_accumulate_" + ("f64" if dtype == np.float64 else "f32"))
@@ -61,6 +61,8 @@ def _accumulate(lib, dtype, b, outs, u, v, coef, init):
     cd = torch.from_numpy(np.ascontiguousarray(coef)).cuda() if coef is not None else None
     on = lambda name, t: t.data_ptr() if name in outs else None  # noqa: E731
     H = b.H if "harm" in outs else 0
+    if launched is not None:  # the H this launch is called with: the instantiation it dispatches
+        launched.append(H)
     rc = fn(b.u.data_ptr(), b.v.data_ptr() if "vsq" in outs else None, b.n, on("peak", b.pmax), on("peak", b.pmin), on("usq", b.usq),
             on("vsq", b.vsq), on("harm", b.hre), on("harm", b.him), b.stride, cd.data_ptr() if H else None, H, int(init),
             pkg("_lib").stream_ptr())
@@ -68,7 +70,7 @@ def _accumulate(lib, dtype, b, outs, u, v, coef, init):
     assert rc == 0
 
 
-def _window(lib, dtype, b, outs, rng, records):
+def _window(lib, dtype, b, outs, rng, records, figures=None, launched=None):
     """``records`` records of seeded random (u, v), the first with ``init``; checks every output that is on against numpy, and that
     every output that is off, and every guard element, still holds the sentinel."""
     n, H = b.n, b.H
@@ -76,7 +78,7 @@ def _window(lib, dtype, b, outs, rng, records):
     vs = [(1e3 * rng.standard_normal(n)).astype(dtype) for _ in range(records)]
     coefs = [rng.uniform(-1.0, 1.0, 2 * H) for _ in range(records)]
     for k in range(records):
-        _accumulate(lib, dtype, b, outs, us[k], vs[k], coefs[k] if H else None, k == 0)
+        _accumulate(lib, dtype, b, outs, us[k], vs[k], coefs[k] if H else None, k == 0, launched)
     U, V = np.asarray(us, dtype=np.float64), np.asarray(vs, dtype=np.float64)  # an fp32 field converts exactly
     eps = 2.0 ** -52
 
@@ -86,6 +88,8 @@ def _window(lib, dtype, b, outs, rng, records):
             acc = acc + terms[k]
         bound = 2 * records * eps * np.abs(terms).sum(axis=0)
         err = np.abs(_np(got)[:n] - acc)
+        if figures is not None:  # the largest error over its bound
+            figures.append(float(np.max(err / bound)))
         assert np.all(err <= bound), (float(err.max()), float(bound.min()))
 
     if "peak" in outs:
@@ -111,18 +115,27 @@ def _window(lib, dtype, b, outs, rng, records):
     assert b.guards_untouched()
 
 
-def _kernel_case(dtype, H, shift, sizes=SIZES):
+def _output_sets(H):
+    return [("peak",), ("usq",), ("vsq",), ("peak", "usq", "vsq", "harm")] + ([("harm",)] if H else [])
+
+
+def _kernel_case(dtype, H, shift, sizes=SIZES, sets=None, windows=(5, 3), collect=None, figures=None, launched=None):
+    """``sets``: the output sets to run (default: all of ``_output_sets``); ``windows``: records per window; ``collect``: a list that
+    receives every output buffer, guards included, as the last window of each (size, set) left it; ``figures``: a list that receives
+    every sum's largest error as a ratio to its bound; ``launched``: a list that receives the H of every launch (0 for an output set
+    without "harm": such a launch runs the H = 0 build whatever the buffers' H)."""
     import torch
 
     torch.cuda.set_device(0)
     lib = pkg("_lib").load()
     rng = np.random.default_rng(100 * H + shift)
-    sets = [("peak",), ("usq",), ("vsq",), ("peak", "usq", "vsq", "harm")] + ([("harm",)] if H else [])
     for n in sizes:
-        for outs in sets:
+        for outs in (_output_sets(H) if sets is None else sets):
             b = _Buffers(n, dtype, H, shift)
-            _window(lib, dtype, b, outs, rng, 5)
-            _window(lib, dtype, b, outs, rng, 3)  # a second window: its first record (init) must not see the first window
+            for records in windows:  # a second window: its first record (init) must not see the first window
+                _window(lib, dtype, b, outs, rng, records, figures, launched)
+            if collect is not None:
+                collect.append([_np(t) for t in (b.pmax, b.pmin, b.usq, b.vsq, b.hre, b.him)])
 
 
 @pytest.mark.parametrize("shift", [0, 1], ids=["aligned", "offset-by-one"])

@@ -1636,59 +1636,71 @@ def test_rk4_stage_kinds_equal_the_numpy_table(gpu, dtype, entry):
     well.  Sizes: below, at and above one 16-byte group and one block, a scalar tail of the owned range and a ghost block of ``b``; operands 16-byte aligned
     and shifted by one element (the scalar build of ``rk4_stage_kernel``).  What a kind does not write is bitwise untouched, also beyond nlocal and
     outside the operand; ``b`` is zero over [0, n); ``m`` is m0 over the owned range and 0 beyond."""
+    rng = np.random.default_rng(29)
+    for n in (1, 2, 3, 255, 257, 4099):
+        nl = n - min(n // 7, 5)
+        for off in (0, 1):
+            for kind in range(4 if entry == "nl" else 8):
+                _rk4_table_case(dtype, entry, n, nl, off, kind, rng)
+
+
+def _rk4_table_case(dtype, entry, n, nl, off, kind, rng, figures=None):
+    """One launch of ``test_rk4_stage_kinds_equal_the_numpy_table`` and its checks: kind ``kind`` of entry point ``entry`` on ``n`` dofs,
+    ``nl`` of them owned, every operand ``off`` elements into its allocation, inputs drawn from ``rng``.  Returns {vector: the whole
+    allocation as the launch left it}; ``figures`` receives per written vector the largest error as a ratio to its bound."""
     import torch
 
     lib_mod = pkg("_lib")
     lib = lib_mod.load()
     suf = "f64" if dtype == np.float64 else "f32"
     tol = 1e-14 if dtype == np.float64 else 1e-6
-    rng = np.random.default_rng(29)
     bw, aw, kappa = dtype(0.3), dtype(0.7), dtype(0.25)
     mass = {"stage": ["minv"], "nl": ["m0", "m"]}.get(entry, ["m0", "w2", "w5"])
     names = mass + ["b", "u", "v", "u0", "v0", "ku", "un"] + (["w"] if entry.startswith("nl2") else [])
-    for n in (1, 2, 3, 255, 257, 4099):
-        nl = n - min(n // 7, 5)
-        for off in (0, 1):
-            for kind in range(4 if entry == "nl" else 8):
-                host = {k: rng.uniform(0.5, 1.5, n + off + 1).astype(dtype) for k in names}  # one element before (off = 1) and one after the operand
-                if "w2" in host:
-                    host["w2"] *= dtype(0.01)
-                dev = {k: torch.from_numpy(a).cuda() for k, a in host.items()}
-                p = {k: t[off:].data_ptr() for k, t in dev.items()}
-                vecs = [p[k] for k in ("b", "u", "v", "u0", "v0", "ku", "un")]
-                if entry == "stage":
-                    rc = getattr(lib, f"fus_rk4_stage_{suf}")(bw, aw, kind, p["minv"], *vecs, nl, n, lib_mod.stream_ptr())
-                elif entry == "nl":
-                    rc = getattr(lib, f"fus_rk4_stage_nl_{suf}")(bw, aw, kind, p["m0"], p["m"], *vecs, nl, n, lib_mod.stream_ptr())
-                else:
-                    rc = getattr(lib, f"fus_rk4_stage_nl2_{suf}")(bw, aw, kind, p["m0"], p["w2"], p["w5"], *vecs, kappa, p["w"] if entry == "nl2_w" else None,
-                                                               nl, n, lib_mod.stream_ptr())
-                assert rc == 0
-                x = {k: a[off:off + nl] for k, a in host.items()}  # the owned range
-                if entry == "stage":
-                    kv = x["b"] * x["minv"]
-                elif entry == "nl":
-                    kv = x["b"] / x["m"]
-                else:  # (u_n, v_n): the stage's inputs
-                    s, t = (x["u0"], x["v0"]) if kind in (2, 4) else (x["un"], x["ku"])
-                    kv = (x["b"] + x["w5"] * t * t) / (x["m0"] + x["w2"] * s)
-                new = _rk4_table_numpy(kind, bw, aw, kv, x)
-                assert all(a.dtype == dtype for a in new.values())
-                if entry == "nl2_w":  # the next stage's inputs
-                    s, t = (new["u0"], new["v0"]) if kind == 3 else (x["u0"], new["v0"]) if kind == 7 else (new["un"], new["ku"])
-                    new["w"] = s + kappa * t
-                for k in names:
-                    where = f"{entry} {suf} kind {kind} n {n} offset {off}: {k}"
-                    got, want = dev[k].cpu().numpy(), host[k].copy()
-                    if k == "b":
-                        want[off:off + n] = 0
-                    elif k == "m":
-                        want[off:off + nl], want[off + nl:off + n] = host["m0"][off:off + nl], 0
-                    elif k in new:
-                        err = float(np.abs(got[off:off + nl].astype(np.float64) - new[k].astype(np.float64)).max())
-                        assert err <= tol * float(np.abs(new[k]).max()), f"{where}: {err:.3e} of {float(np.abs(new[k]).max()):.3e}"
-                        want[off:off + nl] = got[off:off + nl]
-                    assert np.array_equal(got, want), where
+    host = {k: rng.uniform(0.5, 1.5, n + off + 1).astype(dtype) for k in names}  # one element before (off = 1) and one after the operand
+    if "w2" in host:
+        host["w2"] *= dtype(0.01)
+    dev = {k: torch.from_numpy(a).cuda() for k, a in host.items()}
+    p = {k: t[off:].data_ptr() for k, t in dev.items()}
+    vecs = [p[k] for k in ("b", "u", "v", "u0", "v0", "ku", "un")]
+    if entry == "stage":
+        rc = getattr(lib, f"fus_rk4_stage_{suf}")(bw, aw, kind, p["minv"], *vecs, nl, n, lib_mod.stream_ptr())
+    elif entry == "nl":
+        rc = getattr(lib, f"fus_rk4_stage_nl_{suf}")(bw, aw, kind, p["m0"], p["m"], *vecs, nl, n, lib_mod.stream_ptr())
+    else:
+        rc = getattr(lib, f"fus_rk4_stage_nl2_{suf}")(bw, aw, kind, p["m0"], p["w2"], p["w5"], *vecs, kappa, p["w"] if entry == "nl2_w" else None,
+                                                   nl, n, lib_mod.stream_ptr())
+    assert rc == 0
+    x = {k: a[off:off + nl] for k, a in host.items()}  # the owned range
+    if entry == "stage":
+        kv = x["b"] * x["minv"]
+    elif entry == "nl":
+        kv = x["b"] / x["m"]
+    else:  # (u_n, v_n): the stage's inputs
+        s, t = (x["u0"], x["v0"]) if kind in (2, 4) else (x["un"], x["ku"])
+        kv = (x["b"] + x["w5"] * t * t) / (x["m0"] + x["w2"] * s)
+    new = _rk4_table_numpy(kind, bw, aw, kv, x)
+    assert all(a.dtype == dtype for a in new.values())
+    if entry == "nl2_w":  # the next stage's inputs
+        s, t = (new["u0"], new["v0"]) if kind == 3 else (x["u0"], new["v0"]) if kind == 7 else (new["un"], new["ku"])
+        new["w"] = s + kappa * t
+    result = {}
+    for k in names:
+        where = f"{entry} {suf} kind {kind} n {n} offset {off}: {k}"
+        got, want = dev[k].cpu().numpy(), host[k].copy()
+        result[k] = got
+        if k == "b":
+            want[off:off + n] = 0
+        elif k == "m":
+            want[off:off + nl], want[off + nl:off + n] = host["m0"][off:off + nl], 0
+        elif k in new:
+            err = float(np.abs(got[off:off + nl].astype(np.float64) - new[k].astype(np.float64)).max())
+            if figures is not None:
+                figures[k] = err / (tol * float(np.abs(new[k]).max()))
+            assert err <= tol * float(np.abs(new[k]).max()), f"{where}: {err:.3e} of {float(np.abs(new[k]).max()):.3e}"
+            want[off:off + nl] = got[off:off + nl]
+        assert np.array_equal(got, want), where
+    return result
 
 
 def _round_exact(x, dtype):

@@ -34,14 +34,22 @@ def _numpy_stage(kind, bw, aw, aw_u, itau, kd, x0, xn, acc, ub, vn):
     return x0, xn, acc, ur
 
 
-@pytest.mark.parametrize("n", [1, 7, 1027, 65541])
-@pytest.mark.parametrize("nr", [1, 2, 3, 4])
-@pytest.mark.parametrize("dtype", [np.float64, np.float32], ids=["f64", "f32"])
-def test_relax_stage_kernel(dtype, nr, n):
-    """FIRST, MIDDLE and LAST, scalar and per-dof weights, operands 256-byte aligned and every one of them one element further (the
-    W = 1 form), on arrays filled with nonzero values: against numpy in fp64, to round-off of the type (every output is a sum of at
-    most 3 + NR terms of size <= 4: 16 eps of the largest); what a kind does not write, the row padding and the entries past nlocal
-    keep their bits."""
+def _relax_stage_case(dtype, nr, n, offsets=(0, 1), mode=None, perdofs=(False, True), kinds=(0, 1, 2), odd_stride=False, figures=None):
+    """The launches of ``test_relax_stage_kernel`` on ``n`` owned dofs and their checks; ``mode``: ``TUNE_VECTOR_STREAM`` for the
+    launches (None: as it stands); ``odd_stride``: one more entry per row (rows that do not start 16-byte aligned).  Returns
+    {(offset, perdof, kind): (x0, xn, acc, ur) as the launch left them}; ``figures`` collects the largest error over its bound."""
+    if mode is None:
+        return _relax_stage_launches(dtype, nr, n, offsets, perdofs, kinds, odd_stride, figures)
+    lib = pkg("_lib")
+    before_mode = lib.get_tuning(lib.TUNE_VECTOR_STREAM)
+    lib.set_tuning(lib.TUNE_VECTOR_STREAM, mode)
+    try:
+        return _relax_stage_launches(dtype, nr, n, offsets, perdofs, kinds, odd_stride, figures)
+    finally:
+        lib.set_tuning(lib.TUNE_VECTOR_STREAM, before_mode)
+
+
+def _relax_stage_launches(dtype, nr, n, offsets, perdofs, kinds, odd_stride, figures):
     import torch
 
     torch.cuda.set_device(0)
@@ -49,7 +57,7 @@ def test_relax_stage_kernel(dtype, nr, n):
     tdt = torch.from_numpy(np.zeros(1, dtype)).dtype
     eps = np.finfo(dtype).eps
     w = 16 // np.dtype(dtype).itemsize
-    stride, nlocal = -(-(n + 3) // w) * w, n  # a few entries past nlocal in every row
+    stride, nlocal = -(-(n + 3) // w) * w + int(odd_stride), n  # a few entries past nlocal in every row
     rng = np.random.default_rng(1000 * nr + n)
     tau = rng.uniform(0.5, 2.0, nr)
     itau = (1.0 / tau).astype(dtype).astype(np.float64)  # the kernel rounds 1 / tau to the field's type
@@ -67,9 +75,10 @@ def test_relax_stage_kernel(dtype, nr, n):
         assert view.data_ptr() % 256 == offset * a.itemsize
         return view
 
-    for offset in (0, 1):
-        for perdof in (False, True):
-            for kind in (0, 1, 2):
+    results = {}
+    for offset in offsets:
+        for perdof in perdofs:
+            for kind in kinds:
                 d = {k_: dev(v_, offset) for k_, v_ in host.items()}
                 kd_d, ub_d, vn_d, ur_d = dev(kd, offset), dev(ub, offset), dev(vn, offset), dev(ur0, offset)
                 au = 0.0 if kind == 2 else aw_u
@@ -88,6 +97,22 @@ def test_relax_stage_kernel(dtype, nr, n):
                 assert np.max(np.abs(got[3][:n] - ref[3])) <= 16 * eps * max(1.0, np.max(np.abs(ref[3]))), (what, "ur")
                 assert np.array_equal(got[3][n:].view(np.uint8), ur0[n:].view(np.uint8)), (what, "ur past nlocal")
                 assert np.array_equal(ub_d.cpu().numpy().view(np.uint8), ub.view(np.uint8)) and np.array_equal(vn_d.cpu().numpy().view(np.uint8), vn.view(np.uint8))
+                results[offset, perdof, kind] = got
+                if figures is not None:
+                    figures[offset, perdof, kind] = max(float(np.max(np.abs(g[..., :n] - r)) / (16 * eps * max(1.0, np.max(np.abs(r)))))
+                                                        for g, r in zip(got, ref))
+    return results
+
+
+@pytest.mark.parametrize("n", [1, 7, 1027, 65541])
+@pytest.mark.parametrize("nr", [1, 2, 3, 4])
+@pytest.mark.parametrize("dtype", [np.float64, np.float32], ids=["f64", "f32"])
+def test_relax_stage_kernel(dtype, nr, n):
+    """FIRST, MIDDLE and LAST, scalar and per-dof weights, operands 256-byte aligned and every one of them one element further (the
+    W = 1 form), on arrays filled with nonzero values: against numpy in fp64, to round-off of the type (every output is a sum of at
+    most 3 + NR terms of size <= 4: 16 eps of the largest); what a kind does not write, the row padding and the entries past nlocal
+    keep their bits."""
+    _relax_stage_case(dtype, nr, n)
 
 
 def test_relax_stage_argument_checks():

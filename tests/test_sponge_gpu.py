@@ -28,13 +28,20 @@ def _lateral(mesh, c, cells=1):
 def test_sponge_terms_kernel(dtype, n, offset):
     """y[idx] -= cv v[idx] + cu u[idx] on a y filled with nonzero values; operands 256-byte aligned, and every one of them one element
     further; the entries of y outside the list keep their bits."""
+    _sponge_case(dtype, n, offset)
+
+
+def _sponge_case(dtype, n, offset, nd=3000, idx=None, figures=None):
+    """The launch of ``test_sponge_terms_kernel`` and its checks on a vector of ``nd`` entries; ``idx``: the list (ascending, distinct;
+    default: the test's own for ``n``).  Returns y as the launch left it."""
     import torch
 
     torch.cuda.set_device(0)
     ops = pkg("operators")
-    nd = 3000
     rng = np.random.default_rng(100 * n + offset)
-    if n == 1000:  # gaps: 1000 of 3000, runs and holes of every small length
+    if idx is not None:
+        assert idx.dtype == np.int32 and idx.size == n and np.all(np.diff(idx) > 0) and idx[-1] < nd
+    elif n == 1000:  # gaps: 1000 of 3000, runs and holes of every small length
         idx = np.sort(rng.choice(nd, size=n, replace=False)).astype(np.int32)
         assert np.any(np.diff(idx) > 1) and np.any(np.diff(idx) == 1)
     else:  # one run: more than one workgroup at 257
@@ -63,6 +70,9 @@ def test_sponge_terms_kernel(dtype, n, offset):
     outside = np.ones(nd, dtype=bool)
     outside[idx] = False
     assert np.array_equal(got[outside].view(np.uint8), y[outside].view(np.uint8))
+    if figures is not None and n:
+        figures["list"] = float(np.max(np.abs(got[idx] - ref[idx])) / (tol["mx"] * 6.0))
+    return got
 
 
 def test_sponge_terms_argument_checks():
