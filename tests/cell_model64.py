@@ -7,6 +7,12 @@ tests/test_cell_builds_gpu.py (built as tests/nodal_model64.py is for the two no
     westervelt   b += K(c3) u + K(c4) v + M(c5) v^2,  m += M(c2) u   westervelt_cell_kernel       (MASS; without: b += K(c3) u + K(c4) v)
     westervelt_geom   the same, G and detJ from the cell vertices    westervelt_cell_geom_kernel
 
+and, for tests/test_cell_op_builds_gpu.py,
+
+    mass         y += M(c) x on cells, detJ read from its array      mass_plan_kernel, mass_kernel
+    facet_mass   the same on boundary facets, N = n^2                mass_plan_kernel, mass_kernel
+    gradient     y3 += C(c) x, the geometry from the cell vertices   gradient_plan_geom_kernel
+
 The model reads what each kernel reads.  General G: ``G`` and ``detJ`` of ``build_problem(dtype=T)`` cast to float64 -- not
 re-formed from the vertices.  Affine: ``f64(G_T[c, 0, :]) * f64(wratio_T[q])`` with ``wratio_T = (w / w[0]).astype(T)`` as
 ``operators._StiffnessOperator`` builds it, on an unperturbed box that a fixed linear map shears (the cells stay affine, all six
@@ -23,14 +29,24 @@ that do not meet, so that any swap among them is an O(1) error: c3 is the geomet
 [0.2, 0.4], c5 = s x [2, 3] with s = rms(K(c3) u + K(c4) v) / rms(M(1) v^2), a power of two, so that the mass term of ``b`` is as large
 as its stiffness terms (on a unit box detJ is orders of magnitude below the entries of K; with c5 = O(1) a wrong c5 would vanish in
 ``b``).  y0 / b0 / m0 are Gaussian at 0.1 x the rms of what is added.  Cases are read-only.  CPU only.  Not a test module; what the
-GPU tests take for granted about it is checked in tests/test_cell_model64.py."""
+GPU tests take for granted about it is checked in tests/test_cell_model64.py.
+
+The two mass kinds read ``dofmap`` [entities, N], ``detJ`` of the same shape and ``cc`` (one constant per entity) of any geometry that
+holds them (``box``, ``colliding``, ``facet_box``, ``entities``); the apply is ``oracle_c.mass_apply``.  The gradient kind is
+``gradient_cpu.weak_gradient`` in float64 on the rounded vertices and tables, with one record per component (``gx``, ``gy``, ``gz``);
+its fp32 evaluation is the same function with ``dtype=np.float32``, whose einsum order is not the kernel's and whose rel max error
+reaches several units of 2^-23 on thin boxes: every record carries ``e_bar``, the e_cpu that enters the fp32 bar, which for the
+gradient is e_cpu capped at ``E_CAP`` = 2 units (the bound the other kinds meet) and for every other kind e_cpu itself."""
 
 import numpy as np
 
+import gradient_cpu
 import nodal_model64 as nodal
 from conftest import build_problem, pkg
 
 KINDS = {"general": 3, "affine": 4, "geom": 5, "westervelt": 6, "westervelt_geom": 7}  # (1, 2: nodal_model64's)
+OP_KINDS = {"mass": 8, "facet_mass": 9, "gradient": 10}  # the kinds of tests/test_cell_op_builds_gpu.py: the ids go on, no draw above changes
+E_CAP = 2 * 2.0**-23  # the cap on the gradient restatement's e_cpu in the fp32 bar
 # the linear map of the affine box: det 0.83, every entry of J^-1 J^-T non-zero
 SHEAR = np.array([[1.0, 0.3, -0.2], [0.1, 0.8, 0.25], [-0.15, 0.2, 1.2]])
 
@@ -106,7 +122,7 @@ def affine_G(geo, dtype):
 
 
 def _rng(kind, geo, salt):
-    return np.random.default_rng([KINDS[kind], geo["P"], geo["dtype"].itemsize, salt])
+    return np.random.default_rng([KINDS[kind] if kind in KINDS else OP_KINDS[kind], geo["P"], geo["dtype"].itemsize, salt])
 
 
 def _freeze(case):
@@ -186,5 +202,67 @@ def westervelt(kind, geo, salt=0, swap=()):
     return _freeze(dict(geo, kind=kind, u=u, v=v, c2=c2, c3=c3, c4=c4, c5=c5, out=out, ks=ks, mb=full - ks))
 
 
+def facet_box(P, shape, dtype, perturb=0.2):
+    """The boundary facets of a perturbed box as mass entities: ``dofmap`` [facets, n^2], ``detJ`` (the scaled surface determinant in
+    ``dtype``, formed as the solvers form it) and ``cc``, one constant per facet around 1."""
+    gll, pre = pkg("gll"), pkg("precompute")
+    mesh = pkg("boxmesh").BoxMesh(P, shape, perturb=perturb, seed=40 + P, dtype=dtype)
+    pts, wts, _ = gll.tabulate_1d(P, dtype)
+    bd = mesh.boundary_facets()
+    dF = np.zeros((bd.shape[0], (P + 1) ** 2), dtype=dtype)
+    pre.compute_boundary_facets_scaled_jacobian_determinant(dF, (mesh.x_dofs, mesh.x_g), bd, pre.tabulate_facet_gradients(pts, dtype),
+                                                            gll.tensor_weights_2d(wts).astype(dtype))
+    cc = (1.0 + 0.25 * np.random.default_rng(77 + P).standard_normal(bd.shape[0])).astype(dtype)
+    return dict(P=P, dtype=np.dtype(dtype), ndofs=mesh.ndofs, ncells=bd.shape[0], dofmap=np.ascontiguousarray(mesh.facet_dofmap(bd), dtype=np.int32),
+                detJ=dF, cc=cc)
+
+
+def entities(dtype, N, nent, ndofs, seed=5):
+    """A synthetic entity set for the plan-free mass kernel: ``dofmap`` rows are random integers in [0, ndofs) (N = 1 included), ``detJ``
+    uniform on [0.5, 1.5], ``cc`` around 1.  ``P`` is N (it only seeds the draws)."""
+    rng = np.random.default_rng([seed, N, nent])
+    return dict(P=N, dtype=np.dtype(dtype), ndofs=ndofs, ncells=nent, dofmap=rng.integers(0, ndofs, size=(nent, N), dtype=np.int32),
+                detJ=rng.uniform(0.5, 1.5, (nent, N)).astype(dtype), cc=(1.0 + 0.25 * rng.standard_normal(nent)).astype(dtype))
+
+
+def mass(kind, geo, salt=0):
+    """One case of ``y += M(cc) x`` on the entities of ``geo``: ``x``, ``out["y"]``."""
+    dtype, dm, nd = geo["dtype"], geo["dofmap"], geo["ndofs"]
+    rng = _rng(kind, geo, salt)
+    x = rng.standard_normal(nd).astype(dtype)
+    orc = oracle()
+    add = np.zeros(nd)
+    orc.mass_apply(_f64(x), _f64(geo["cc"]), add, _f64(geo["detJ"]), dm)
+    y = _record(geo, add, rng, lambda y: orc.mass_apply(x, geo["cc"], y, geo["detJ"], dm))
+    y["e_bar"] = y["e_cpu"]
+    return _freeze(dict(geo, kind=kind, x=x, out={"y": y}))
+
+
+COMPONENTS = ("gx", "gy", "gz")
+
+
+def gradient(kind, geo, salt=0):
+    """One case of ``y3 += C(cc) x``: ``x`` and one record per component under ``out`` (``COMPONENTS``), each with its own y0."""
+    dtype, dm, nd = geo["dtype"], geo["dofmap"], geo["ndofs"]
+    rng = _rng(kind, geo, salt)
+    x = rng.standard_normal(nd).astype(dtype)
+    tables = (geo["x_dofs"], geo["x_g"], geo["pts"], geo["wts"], geo["D"])
+    add = gradient_cpu.weak_gradient(*tables, dm, _f64(x), _f64(geo["cc"]), nd)
+    out = {}
+    if dtype == np.float32:  # what weak_gradient(..., y3=y0, dtype=np.float32) adds, component by component
+        r32 = gradient_cpu.weighted_gradient(*tables, dm, x, np.float32)
+        cr32 = geo["cc"].astype(np.float32)[:, None, None] * r32
+        assert cr32.dtype == np.float32
+    for d, k in enumerate(COMPONENTS):
+        out[k] = _record(geo, np.ascontiguousarray(add[d]), rng, lambda y, d=d: np.add.at(y, dm.reshape(-1), cr32[..., d].reshape(-1)))
+        e = out[k]["e_cpu"]
+        out[k]["e_bar"] = None if e is None else (min(e[0], E_CAP), min(e[1], E_CAP))
+    return _freeze(dict(geo, kind=kind, x=x, out=out))
+
+
 def model(kind, geo, salt=0):
+    if kind in ("mass", "facet_mass"):
+        return mass(kind, geo, salt)
+    if kind == "gradient":
+        return gradient(kind, geo, salt)
     return (westervelt if kind.startswith("westervelt") else stiffness)(kind, geo, salt)

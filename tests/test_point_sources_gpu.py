@@ -13,6 +13,8 @@ pytestmark = pytest.mark.gpu
 
 F0 = 0.5e6
 T0 = 1.0 / F0
+# every degree point_source_kernel is compiled for (tests/test_cell_model64.py compares this list with the compiled names)
+DEGREES = list(range(1, 11))
 
 
 # ---- the kernel --------------------------------------------------------------------------------------------------------------------
@@ -34,7 +36,7 @@ def _kernel_points(mesh, m, rng):
 
 
 @pytest.mark.parametrize("m", [0, 1, 300])
-@pytest.mark.parametrize("P", [2, 4, 7])
+@pytest.mark.parametrize("P", DEGREES)
 @pytest.mark.parametrize("dtype", [np.float64, np.float32], ids=["f64", "f32"])
 def test_point_source_kernel(dtype, P, m):
     """y += the points' terms at t = 12.3 T of a burst of 12 T, on a y filled with non-zero values, against np.add.at in fp64.  The
@@ -91,7 +93,7 @@ def test_point_source_kernel(dtype, P, m):
         assert np.array_equal(y.cpu().numpy().view(np.uint8), y0.view(np.uint8))
 
 
-@pytest.mark.parametrize("P", [2, 4, 7])
+@pytest.mark.parametrize("P", DEGREES)
 @pytest.mark.parametrize("dtype", [np.float64, np.float32], ids=["f64", "f32"])
 def test_point_source_is_the_adjoint_of_the_probe(dtype, P):
     """With ONE SensorSetup: sum_j inject(q)[j] x[j] == sum_p q_p probe(x)_p for random x and q, relative to the sum of the terms'

@@ -13,6 +13,9 @@ from oracle import rk4_oracle
 
 pytestmark = pytest.mark.gpu
 
+# every degree probe_eval_kernel is compiled for (tests/test_cell_model64.py compares this list with the compiled names)
+DEGREES = list(range(1, 11))
+
 
 def _bowl(L, N):
     def warp(xg):
@@ -64,7 +67,7 @@ def _dev(a, dt):
 
 @pytest.mark.parametrize("dtype", [np.float64, np.float32], ids=["f64", "f32"])
 @pytest.mark.parametrize("kind", ["affine", "perturbed", "bowl", "array"])
-@pytest.mark.parametrize("P", list(range(2, 11)))
+@pytest.mark.parametrize("P", DEGREES)
 def test_device_evaluation_matches_eval_function(P, kind, dtype):
     import torch
 

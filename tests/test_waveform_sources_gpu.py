@@ -18,6 +18,9 @@ pytestmark = pytest.mark.gpu
 
 F0, P0, C0 = 0.5e6, 60000.0, 1500.0
 T0 = 1.0 / F0
+# every degree point_source_wave_kernel is compiled for (tests/test_cell_model64.py compares this list with the compiled names); the
+# facet kernel's test runs the same list
+DEGREES = list(range(1, 11))
 _lockstep = pkg("solver_base").run_lockstep
 
 # the table of the kernel tests: a power-of-two interval, so that node times and (s - t0) / dt are exact
@@ -48,7 +51,7 @@ def _dt(mesh, P, L, c=C0, f0=F0):
 # ---- 8. the facet kernel ---------------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("nt", [33, 2], ids=["Nt33", "Nt2"])
 @pytest.mark.parametrize("rows", ["R1", "RE"])
-@pytest.mark.parametrize("P", [2, 4, 7])
+@pytest.mark.parametrize("P", DEGREES)
 @pytest.mark.parametrize("dtype", [np.float64, np.float32], ids=["f64", "f32"])
 def test_facet_wave_kernel(dtype, P, rows, nt):
     """The nine source facets of a 3 x 3 x 3 box: eight elements and one inactive facet; element 6 is mapped to row -1; the delays of
@@ -150,7 +153,7 @@ def _kernel_points(mesh, m, rng):
 
 
 @pytest.mark.parametrize("m", [0, 1, 300])
-@pytest.mark.parametrize("P", [2, 4, 7])
+@pytest.mark.parametrize("P", DEGREES)
 @pytest.mark.parametrize("dtype", [np.float64, np.float32], ids=["f64", "f32"])
 def test_point_wave_kernel(dtype, P, m):
     """y += the points' terms on a y filled with non-zero values, against np.add.at in fp64: 5 rows for 300 points, every ninth point
