@@ -10,6 +10,7 @@ import numpy as np
 import pytest
 
 from conftest import TOL, build_problem, golden_files, pkg, ref_field, rel_l2, rel_max
+from plan_model import gather_random_dofmap
 
 pytestmark = pytest.mark.gpu
 
@@ -1283,27 +1284,8 @@ def test_mass_gather_random_dofmaps(gpu, seed):
 
     lib = pkg("_lib")
     L = lib.load()
-    rng = np.random.default_rng(100 + seed)
-    N = int(rng.choice([1, 3, 8, 27, 64]))
-    nent = int(rng.integers(1, 4000))
-    nd = int(rng.integers(5, 20000))
-    dm = rng.integers(0, nd, size=(nent, N))
-    # a few hot dofs (at most 250 entries each, the plan's limit is 255) and a dead zone nobody touches
-    hot = rng.choice(nd, size=min(3, nd), replace=False)
-    flat = dm.reshape(-1)
-    for h in hot:
-        idx = rng.choice(flat.size, size=min(80, flat.size), replace=False)
-        flat[idx] = h
-    lo = nd // 3
-    flat[(flat >= lo) & (flat < lo + nd // 10)] = 0 if seed % 2 else lo  # empties a range of dofs
-    counts = np.bincount(flat, minlength=nd)
-    if counts.max() > 255:  # keep inside the plan's limit: spread the excess
-        for d in np.nonzero(counts > 250)[0]:
-            where = np.nonzero(flat == d)[0][250:]
-            flat[where] = rng.integers(lo + nd // 10, nd, size=where.size) if lo + nd // 10 < nd else d
-        counts = np.bincount(flat, minlength=nd)
+    rng, N, nent, nd, dm, counts = gather_random_dofmap(seed)  # shared with tests/test_plan_builders_gpu.py, which compares the plans themselves
     assume_ok = counts.max() <= 255
-    dm = flat.reshape(nent, N).astype(np.int32)
     x = rng.standard_normal(nd)
     c = rng.standard_normal(nent)
     dj = rng.uniform(0.5, 1.5, size=(nent, N))
