@@ -9,6 +9,7 @@ from fractions import Fraction
 import numpy as np
 import pytest
 
+import facet_cpu
 from conftest import TOL, build_problem, golden_files, pkg, ref_field, rel_l2, rel_max
 from plan_model import gather_random_dofmap
 
@@ -1020,26 +1021,20 @@ def test_facet_terms_one_launch(gpu, oracle_c, path):
     g, dg = dt.type(0.37), dt.type(-1.9)
     c2 = (0.5 + np.random.default_rng(2).random(half)).astype(dt)
     v = d["x"]
-    ref = d["y0"].copy()
-    ones = np.ones_like(v)
-    oracle_c.mass_apply((g * ones).astype(dt), np.ascontiguousarray(fc[A]), ref, np.ascontiguousarray(dJf[A]), np.ascontiguousarray(fdm[A]))
-    oracle_c.mass_apply((dg * ones).astype(dt), c2, ref, np.ascontiguousarray(dJf[A]), np.ascontiguousarray(fdm[A]))
-    oracle_c.mass_apply(v, np.ascontiguousarray(fc[B]), ref, np.ascontiguousarray(dJf[B]), np.ascontiguousarray(fdm[B]))
+    field = (v, fc[B], dJf[B], fdm[B])
+    ref = facet_cpu.terms_oracle(oracle_c, d["y0"], g, fc[A], dg, c2, dJf[A], fdm[A], field)
     y = dev.to_device(d["y0"])
     td = lambda a: dev.to_device(np.ascontiguousarray(a))  # noqa: E731
     ops.facet_terms(y, (td(fc[A]), float(g), td(c2), float(dg), td(dJf[A]), td(fdm[A])), (td(v), td(fc[B]), td(dJf[B]), td(fdm[B])))
     _check(y.copy_to_host(), ref, dt, "facet terms (two source constants + field)")
     # linear solver form: no second source constant; and an empty source set
-    ref = d["y0"].copy()
-    oracle_c.mass_apply((g * ones).astype(dt), np.ascontiguousarray(fc[A]), ref, np.ascontiguousarray(dJf[A]), np.ascontiguousarray(fdm[A]))
-    oracle_c.mass_apply(v, np.ascontiguousarray(fc[B]), ref, np.ascontiguousarray(dJf[B]), np.ascontiguousarray(fdm[B]))
+    ref = facet_cpu.terms_oracle(oracle_c, d["y0"], g, fc[A], dg, None, dJf[A], fdm[A], field)
     y = dev.to_device(d["y0"])
     ops.facet_terms(y, (td(fc[A]), float(g), None, 0.0, td(dJf[A]), td(fdm[A])), (td(v), td(fc[B]), td(dJf[B]), td(fdm[B])))
     _check(y.copy_to_host(), ref, dt, "facet terms (linear solver form)")
     y2 = dev.to_device(d["y0"])
     ops.facet_terms(y2, (td(fc[:0]), 1.0, None, 0.0, td(dJf[:0]), td(fdm[:0])), (td(v), td(fc[B]), td(dJf[B]), td(fdm[B])))
-    ref2 = d["y0"].copy()
-    oracle_c.mass_apply(v, np.ascontiguousarray(fc[B]), ref2, np.ascontiguousarray(dJf[B]), np.ascontiguousarray(fdm[B]))
+    ref2 = facet_cpu.terms_oracle(oracle_c, d["y0"], g, fc[:0], dg, None, dJf[:0], fdm[:0], field)
     _check(y2.copy_to_host(), ref2, dt, "facet terms (no source facets on this rank)")
 
 
