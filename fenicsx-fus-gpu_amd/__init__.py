@@ -21,6 +21,8 @@ gll         GLL nodes, weights, derivative tables
 device      numba.cuda-like shim over torch tensors (to_device, ...)
 sources     SourceArray (phased-array facet sources), PointSources (monopoles inside the volume)
 receivers   ElementReceivers (what each array element receives), time_reversal
+reductions  Reducer: sums of products, max |x| and the non-finite count of device vectors (csrc/reduce.hpp)
+diagnostics EnergyRecorder, FieldGuard (rk4(..., energy=, guard=)); the solvers' stable_time_step() uses stability.py
 _lib        ctypes binding of csrc/libfusgpu.so (fails loudly if missing)
 """
 

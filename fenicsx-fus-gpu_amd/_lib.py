@@ -28,7 +28,8 @@ ADDITION_HEADER_PATHS = (os.path.join(os.path.dirname(_HERE), "include", "fus_gp
 # functions land in LATER, and no test pins that set to what it holds today
 LATER_HEADER_PATHS = (os.path.join(os.path.dirname(_HERE), "include", "fus_gpu_nodal.h"),
                       os.path.join(os.path.dirname(_HERE), "include", "fus_gpu_westervelt_nodal.h"),
-                      os.path.join(os.path.dirname(_HERE), "include", "fus_gpu_waveform.h"))
+                      os.path.join(os.path.dirname(_HERE), "include", "fus_gpu_reduce.h"),
+                      os.path.join(os.path.dirname(_HERE), "include", "fus_gpu_waveform.h"))  # (tests/test_waveform_sources.py: the last)
 
 
 class FusGpuError(RuntimeError):

@@ -74,6 +74,13 @@ def main():
                     help="drive the source with the sampled rows of FILE.npy ([Nt] or [R, Nt], sample interval DT seconds, first sample at "
                          "t = 0, zero after the last; sources.SampledWaveform) instead of the analytic waveform: the whole source face "
                          "(R = 1) or, with --array, its elements (R = 1 or one row per element, on top of the focusing delays)")
+    ap.add_argument("--energy", type=int, default=0, metavar="EVERY",
+                    help="record the energy 1/2 v.Mv + 1/2 u.Ku on the device after every EVERY-th step (diagnostics.EnergyRecorder); the series "
+                         "goes to <--out or linear_box>.energy.npz")
+    ap.add_argument("--guard", type=int, default=0, metavar="EVERY",
+                    help="check max |u| and the non-finite count every EVERY steps (diagnostics.FieldGuard): a run that goes unstable stops there")
+    ap.add_argument("--stable-dt", action="store_true",
+                    help="print the operator-based RK4 limit of this mesh and medium (solver.stable_time_step) beside the snapped CFL step")
     ap.add_argument("--elements", type=int, nargs=2, default=(4, 4), metavar=("NY", "NZ"), help="elements of the --time-reversal array (default 4 4)")
     a = ap.parse_args()
     if a.focus and not a.array:
@@ -187,17 +194,31 @@ def main():
     if sponge is not None:
         n_layer = solver._sponge[0].numel()
         print(f"Sponge layer (rank {rank}): {a.sponge} cell(s) wide, {n_layer} owned dofs, sigma_max dt = {sponge.sigma_max * dt:.3f}", flush=True)
+    if a.stable_dt:
+        dt_op = solver.stable_time_step(0.8)
+        if rank == 0:
+            print(f"Stable step from the operators: {dt_op:.6e} s at safety 0.8 (limit {solver.stable_limit:.6e} s: lambda_max "
+                  f"{solver.lambda_max:.4e}, damping_max {solver.damping_max:.4e}); snapped CFL step: {dt:.6e} s", flush=True)
+    diag = fusgpu_loader.submodule("diagnostics")
+    energy = diag.EnergyRecorder(solver, every=a.energy, capacity=nstep // a.energy + 1) if a.energy else None
+    guard = diag.FieldGuard(every=a.guard) if a.guard else None
     if rank == 0:
         print("Solve!", flush=True)
     torch.cuda.synchronize()
     t0 = time.perf_counter()
-    t, steps = solver.rk4(0.0, tf, dt, max_steps=a.max_steps, sensors=probes[1] if probes else None)
+    t, steps = solver.rk4(0.0, tf, dt, max_steps=a.max_steps, sensors=probes[1] if probes else None, energy=energy, guard=guard)
     torch.cuda.synchronize()
     el = time.perf_counter() - t0
     if rank == 0:
         print(f"t: {t:5.5},\t Steps: {steps}/{nstep}", flush=True)
         print(f"Solve time: {el}")
         print(f"Solve time per step: {el / max(steps, 1)}")
+    if energy is not None:
+        te, kin, pot, tot, amax, bad = energy.energies()
+        if rank == 0 and len(te):
+            name = f"{a.out or 'linear_box'}.energy.npz"
+            np.savez(name, t=te, kinetic=kin, potential=pot, total=tot, absmax=amax, nonfinite=bad)
+            print(f"Energy: {len(te)} records, first {tot[0]:.6e} (t = {te[0]:.4e}), last {tot[-1]:.6e} (t = {te[-1]:.4e}) -> {name}", flush=True)
     if probes is not None:
         pts, s = probes
         pmax = s.peak()[0][None, :]

@@ -24,6 +24,7 @@ with several ranks every rank appends its owned points, as the reference's ranks
 """
 
 import argparse
+import functools
 import os
 import sys
 import time
@@ -79,6 +80,13 @@ def main():
                          "inclusion (c 1480 -> 1780 m/s, rho 1000 -> 1200 kg/m^3, beta 3.5 -> 5, alpha 0.2 -> 5 dB/m, radius L/6) at the centre "
                          "of the box; the cell pass takes 1/rho and delta/(rho c^2) inside its two contractions "
                          "(csrc/westervelt_geom_nodal.hpp).  Composes with --sponge, --array, --field-stats, --intensity, --thermal and ranks")
+    ap.add_argument("--energy", type=int, default=0, metavar="EVERY",
+                    help="record the energy of the linear part, 1/2 v.M0 v + 1/2 u.Ku, on the device after every EVERY-th step "
+                         "(diagnostics.EnergyRecorder); the series goes to <--out-dir or .>/energy.npz")
+    ap.add_argument("--guard", type=int, default=0, metavar="EVERY",
+                    help="check max |u| and the non-finite count every EVERY steps (diagnostics.FieldGuard): a run that goes unstable stops there")
+    ap.add_argument("--stable-dt", action="store_true",
+                    help="print the operator-based RK4 limit of this mesh and medium (solver.stable_time_step) beside the snapped CFL step")
     ap.add_argument("--source-waveform", nargs=2, default=None, metavar=("FILE.npy", "DT"),
                     help="drive the source with the sampled rows of FILE.npy ([Nt] or [R, Nt], sample interval DT seconds, first sample at "
                          "t = 0, zero after the last; sources.SampledWaveform) instead of the analytic waveform: the whole bowl (R = 1) or, "
@@ -231,6 +239,28 @@ def main():
     if world > 1:
         dist.barrier()
 
+    if a.stable_dt:
+        dt_op = solver.stable_time_step(0.8)
+        if rank == 0:
+            print(f"Stable step from the operators: {dt_op:.6e} s at safety 0.8 (limit {solver.stable_limit:.6e} s: lambda_max "
+                  f"{solver.lambda_max:.4e}, damping_max {solver.damping_max:.4e}); snapped CFL step: {dt:.6e} s", flush=True)
+    energy = None
+    if a.energy or a.guard:  # every rk4 call of the run paths below carries the two diagnostics (their cadence spans the calls)
+        diag = fusgpu_loader.submodule("diagnostics")
+        energy = diag.EnergyRecorder(solver, every=a.energy, capacity=nstep // a.energy + 1) if a.energy else None
+        solver.rk4 = functools.partial(solver.rk4, energy=energy, guard=diag.FieldGuard(every=a.guard) if a.guard else None)
+
+    def report_energy():
+        if energy is None:
+            return
+        te, kin, pot, tot, amax, bad = energy.energies()
+        if rank == 0 and len(te):
+            name = os.path.join(a.out_dir or ".", "energy.npz")
+            np.savez(name, t=te, kinetic=kin, potential=pot, total=tot, absmax=amax, nonfinite=bad)
+            print(f"Energy of the linear part: {len(te)} records, first {tot[0]:.6e} (t = {te[0]:.4e}), last {tot[-1]:.6e} "
+                  f"(t = {te[-1]:.4e}) -> {name}", flush=True)
+
+    a.report_energy = report_energy  # (the run paths below report before they take the process group down)
     if rank == 0:
         print("Solve!", flush=True)
     torch.cuda.synchronize()
@@ -267,6 +297,7 @@ def main():
         print(f"Fields collected over the last period: {step_period}/{step_per_period}")
         print(f"Solve time: {el}")
         print(f"Solve time per step: {el / max(steps, 1)}")
+    report_energy()
     if world > 1:
         dist.destroy_process_group()
 
@@ -313,6 +344,7 @@ def run_with_sensors(a, solver, mesh, comm, rank, world, L, float_type, t0, tf, 
             keep = np.nonzero(~np.isnan(allc[0]))[0]
             rows = np.column_stack([points[keep, 0], points[keep, 1], allc[:, keep].T])
             np.savetxt(a.peak_out, rows, fmt="%.8f", delimiter=",")
+    a.report_energy()
     if world > 1:
         dist.destroy_process_group()
 
@@ -355,6 +387,7 @@ def run_with_monitor(a, solver, mesh, comm, rank, world, float_type, t0, tf, dt,
         run_intensity(solver, m, comm, rank, world)
     if a.thermal and m.nacc:
         run_thermal(a, solver, m, mesh, comm, rank, world, float_type)
+    a.report_energy()
     if world > 1:
         dist.destroy_process_group()
 

@@ -201,6 +201,14 @@ class LinearSpectral3D(SpectralSolver3D):
             yield from self.halo.apply_schedule(u_n, self.cell_coeff2, self.b, self.G, self.dofmap,
                                                 extra_forward=[(self.fwd_v, v_n)], boundary_terms=facets)
 
+    def _stiffness_operator(self):
+        """K(-1/rho) as the stages apply it (``solver_base._stiffness_of``: the energy record and ``stable_time_step``)."""
+        return self.stiff, self.cell_coeff2, self.G, self.dofmap
+
+    def _energy_mass(self):
+        """The lumped mass the stage divides by."""
+        return self.m
+
     # -- reference launch sequence ----------------------------------------------------------------
     def _stage_reference(self, i, t, dt):
         copy, fill, axpy = ops.copy, ops.fill, self.axpy

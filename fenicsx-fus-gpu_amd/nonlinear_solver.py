@@ -290,6 +290,24 @@ class WesterveltSpectral3D(SpectralSolver3D):
             yield from self.halo.schedule(cells, self._percell, [(self.fwd_u, self.w if self.kappa is not None else u_n), (self.fwd_v, v_n)],
                                           [(self.halo.rev, self.b)], facets)
 
+    def _stiffness_operator(self):
+        """K(-1/rho) of u alone, with the operator this solver holds for it (``solver_base._stiffness_of``: the energy record and
+        ``stable_time_step``): the nodal kernel, G formed in the kernel where the fused stage does so, else the G array."""
+        if self.nodal_medium is not None:
+            return self.stiff_nodal3, self.cc3, self.x_dofs, self.dofmap
+        if self.in_kernel_geometry and self.fused:
+            return self.stiff_geom, self.cc3, self.x_dofs, self.dofmap
+        return self.stiff, self.cc3, self.G, self.dofmap
+
+    def _energy_mass(self):
+        """The steady lumped mass m0: the energy of the linear part."""
+        return self.m0
+
+    def _diffusive_ratio(self):
+        if self.nodal_medium is not None:
+            return float(np.max(self.delta_nodal / self.c_nodal**2))
+        return float(np.max(self.delta_cells / self.c_cells**2))
+
     def _vector_pass(self, bw, aw, new_step):
         fn = getattr(_lib.load(), f"fus_rk4_stage_nl2_{_lib.suffix(self.tdt)}")
         _lib.check(

@@ -247,6 +247,9 @@ class SpectralSolver3D(MeshSolver3D):
         """The attributes both wave solvers set first; returns the source and absorbing facet sets and the device geometry:
         ``bd1, bd2, D, G, detJ, (dF1, dF2)``."""
         self.fused, self.source_time = bool(fused), source_time
+        # what stable_time_step() leaves: the two operator bounds and the unscaled RK4 limit they give (None until it has run)
+        self.lambda_max = self.damping_max = self.stable_limit = None
+        self._warned_step = False
         self.lean_stages = os.environ.get("FUS_RK4_LEAN", "1") != "0"  # the fused stage's vector pass: kinds 4-7 of csrc/rk4.hpp (_stage_args)
         # the two tagged facet sets (cuda/demo_linear_box.py:230-243, cuda/utils.py:81-114): a structured box names them by its
         # faces (x = 0: source, x = L: absorbing), a mesh handed over as arrays (dolfinx_adaptor.ArrayMesh) by its facet tags
@@ -388,35 +391,53 @@ class SpectralSolver3D(MeshSolver3D):
         ops.copy(self.v0, self.v)
 
     # -- the time loop -----------------------------------------------------------------------------------------------------
-    def rk4(self, start_time, final_time, dt, max_steps=None, sensors=None, record_from=None, monitor=None, receivers=None):
+    def rk4(self, start_time, final_time, dt, max_steps=None, sensors=None, record_from=None, monitor=None, receivers=None, energy=None,
+            guard=None):
         """Advance from ``start_time`` to ``final_time`` (cuda/demo_linear_box.py:487-566).
         Returns ``(t, steps)``.  ``sensors``: a ``sensors.PointSensors`` recorded after every step that ends after
         ``record_from`` (default: every step) while its series has room -- the supported way to observe the field mid-run.
         ``monitor``: a ``field_monitor.FieldMonitor`` that accumulates (u, v) over the owned dofs after the same steps (one
         launch, no exchange); it may be given together with ``sensors``.  ``receivers``: a ``receivers.ElementReceivers`` (the surface
-        integral of the field over each element of an array, one launch) recorded after the same steps as the sensors."""
-        result = run_schedule(self.rk4_schedule(start_time, final_time, dt, max_steps, sensors, record_from, monitor, receivers))
+        integral of the field over each element of an array, one launch) recorded after the same steps as the sensors.
+        ``energy``: a ``diagnostics.EnergyRecorder`` (the conserved quadratic form after every ``every``-th of those steps: one
+        stiffness apply and one reduction, no host sync).  ``guard``: a ``diagnostics.FieldGuard`` (every ``every`` steps ``max |u|``
+        and the non-finite count are read back: ``FusGpuError`` when the field has blown up).  ``None`` leaves every launch as it is.
+        A ``dt`` above the limit an earlier ``stable_time_step`` call found warns once; ``rk4`` never computes the limit itself."""
+        result = run_schedule(self.rk4_schedule(start_time, final_time, dt, max_steps, sensors, record_from, monitor, receivers, energy,
+                                                guard))
         # N > 1: every device-side wait of the exchange is bounded, so a late or dead neighbour cannot hang this
         # rank -- it must not hand back a field computed from stale ghosts either (the reference would block in
         # MPI Waitall, cuda/scatterer.py:175): raise.  One synchronisation per rk4() call.
         self.check_halo_health(f"{type(self).__name__}.rk4")
         return result
 
-    def _recording(self, start_time, final_time, dt, max_steps, record_from, sensors, monitor, receivers):
+    def _warn_step(self, dt):
+        if self.stable_limit is not None and dt > self.stable_limit and not self._warned_step:
+            import warnings
+
+            self._warned_step = True
+            warnings.warn(f"{type(self).__name__}: dt = {dt:g} s exceeds the RK4 stability limit {self.stable_limit:g} s of this mesh and "
+                          "medium (stable_time_step(safety=1)): the field will grow without bound", RuntimeWarning, stacklevel=4)
+
+    def _recording(self, start_time, final_time, dt, max_steps, record_from, sensors, monitor, receivers, energy=None, guard=None):
         """Plan the recorders for this ``rk4`` call (``expect_steps``) and return ``record(t)``: the generator that records what is
         due after a step ending at ``t``.  On a partitioned mesh the ghost entries of the field are not current after a step: the
         forward exchange the sensors and the receivers read after is posted first -- once, if either is due -- with a ``yield`` after
         posting (the solvers' schedules post their stage exchanges the same way, so in-process lockstep drivers keep working); the
-        monitor reads owned dofs only."""
-        for recorder in (sensors, monitor, receivers):
+        monitor reads owned dofs only.  ``energy`` applies the stiffness to the field through the halo schedule (its own exchanges and
+        yields); ``guard`` is asked after EVERY step, whatever ``record_from``."""
+        self._warn_step(dt)
+        for recorder in (sensors, monitor, receivers, energy, guard):
             if recorder is not None:
                 recorder.expect_steps(start_time, final_time, dt, max_steps, record_from)
         rf = -np.inf if record_from is None else float(record_from)
 
         def record(t):
+            u, v = (self.u0, self.v0) if self.fused else (self.u, self.v)
+            if guard is not None:
+                guard.check(self, u, t)
             if not t > rf:
                 return
-            u, v = (self.u0, self.v0) if self.fused else (self.u, self.v)
             due = [r for r in (sensors, receivers) if r is not None and not r.full]
             if due:
                 if self.halo is not None:
@@ -427,10 +448,13 @@ class SpectralSolver3D(MeshSolver3D):
                     r.record(u, t)
             if monitor is not None:
                 monitor.record(u, v, t)
+            if energy is not None:
+                yield from energy.record_schedule(u, v, t)
 
         return record
 
-    def rk4_schedule(self, start_time, final_time, dt, max_steps=None, sensors=None, record_from=None, monitor=None, receivers=None):
+    def rk4_schedule(self, start_time, final_time, dt, max_steps=None, sensors=None, record_from=None, monitor=None, receivers=None,
+                     energy=None, guard=None):
         """``rk4`` as a generator that yields whenever this rank has posted halo exchanges (see
         ``HaloApply.schedule``); its return value is ``(t, steps)``.  A driver that advances several ranks' generators
         itself calls ``check_halo_health()`` when they are exhausted (``rk4`` does).  ``u`` / ``v`` are valid only once
@@ -439,7 +463,7 @@ class SpectralSolver3D(MeshSolver3D):
         field first, with a yield) or, over every owned dof, through ``monitor`` (no exchange, no yield)."""
         t, step = float(start_time), 0
         self._check_relaxation_step(dt)
-        record = self._recording(t, final_time, dt, max_steps, record_from, sensors, monitor, receivers)
+        record = self._recording(t, final_time, dt, max_steps, record_from, sensors, monitor, receivers, energy, guard)
         if self.fused:
             self._fused_enter()
         elif self.relaxation is not None:
@@ -492,11 +516,12 @@ class SpectralSolver3D(MeshSolver3D):
             self._graph_plans[dt] = held
         return g
 
-    def rk4_graph(self, start_time, final_time, dt, max_steps=None, sensors=None, record_from=None, monitor=None, receivers=None):
+    def rk4_graph(self, start_time, final_time, dt, max_steps=None, sensors=None, record_from=None, monitor=None, receivers=None,
+                  energy=None, guard=None):
         """``rk4`` with the full-size steps replayed from ONE captured hipGraph.  Same kernels in the same
         order on the same data as ``rk4``.  One rank, fused path; a last shorter step runs through ``rk4``.
-        ``sensors`` / ``monitor`` / ``receivers`` / ``record_from`` as in ``rk4``: their launches follow a replay on the same stream,
-        outside the captured graph.  A solver with point sources cannot be replayed (their stage time is a launch argument; a device
+        ``sensors`` / ``monitor`` / ``receivers`` / ``energy`` / ``guard`` / ``record_from`` as in ``rk4``: their launches follow a replay
+        on the same stream, outside the captured graph.  A solver with point sources cannot be replayed (their stage time is a launch argument; a device
         stage block for them does not exist yet): ``FusGpuError``.  Returns ``(t, steps)``."""
         if not self.fused or self.halo is not None:
             raise _lib.FusGpuError("rk4_graph: single-rank fused path only")
@@ -506,7 +531,7 @@ class SpectralSolver3D(MeshSolver3D):
         self._check_relaxation_step(dt)
         t, tf = float(start_time), float(final_time)
         rows, ends = [], []
-        record = self._recording(t, tf, dt, max_steps, record_from, sensors, monitor, receivers)
+        record = self._recording(t, tf, dt, max_steps, record_from, sensors, monitor, receivers, energy, guard)
         for t0, h in rk4_steps(t, tf, dt, max_steps):
             if h != dt:
                 break
@@ -529,9 +554,135 @@ class SpectralSolver3D(MeshSolver3D):
             self._fused_exit()
         steps = len(rows)
         if t < tf and (max_steps is None or steps < max_steps):
-            t, more = self.rk4(t, tf, dt, None if max_steps is None else max_steps - steps, sensors, record_from, monitor, receivers)
+            t, more = self.rk4(t, tf, dt, None if max_steps is None else max_steps - steps, sensors, record_from, monitor, receivers, energy,
+                               guard)
             steps += more
         return t, steps
+
+    # -- the stiffness of the field by itself: the energy record (diagnostics.py) and the step bound below ---------------------------
+    def _stiffness_of(self, x, y):
+        """Generator: ``y += K(-1/rho) x`` with the operator this solver holds (``_stiffness_operator``: ``(operator, cell constants,
+        what travels in its G position, dofmap)``), complete over the owned dofs; on a partitioned mesh through the halo schedule
+        (forward exchange of ``x``, reverse exchange of ``y``), yielding where ``HaloApply`` yields.  Nothing of the solver's is written."""
+        op, cc, G, dofmap = self._stiffness_operator()
+        if self.halo is None:
+            op(x, cc, y, G, dofmap)
+        else:
+            op = self.halo.concurrent_safe(op)
+            yield from self.halo.schedule(lambda c_, G_, d_: op(x, c_, y, G_, d_), (cc, G, dofmap), [(self.halo.fwd, x)], [(self.halo.rev, y)])
+
+    def _gather(self, values, reduce, seq):
+        """Generator: every rank's ``values`` as an array [size, len(values)] (``bioheat.BioheatSpectral3D._gather``)."""
+        if self.halo is None:
+            return np.asarray([[float(v) for v in values]])
+        if reduce is not None:
+            reduce.put(seq, self.comm.rank, values)
+            yield "reduce"
+            return reduce.get(seq)
+        from .scatterer import gather_floats
+
+        every = gather_floats(self.comm, values)
+        if len(every) != self.comm.size:  # the local row alone: no bootstrap spans the ranks
+            raise _lib.FusGpuError(f"{type(self).__name__}: ranks driven from one process share no collective: pass "
+                                   "reduce=InProcessGather(nranks) and drive the schedules in lock step")
+        return every
+
+    def _damping_rates(self, rates):
+        """Generator: add to ``rates`` (fp64, local dofs, zero on entry) the diagonal damping rate of every owned dof: the absorbing
+        facets' ``M_f2(1/(rho c)) 1 / M`` and ``2 sigma`` of a sponge layer.  Returns the largest ``sigma^2`` of this rank."""
+        coef, detJ, fdm = self._absorbing_set
+        diag = torch.zeros(self.ndofs, dtype=self.tdt, device=self.dev)
+        if fdm.shape[0]:
+            self.mass_facet(torch.ones_like(diag), coef, diag, detJ, fdm)  # coef = -1/(rho c): the sign of the stage's right-hand side
+        if self.halo is not None:  # a facet dof may be another rank's: complete the owned entries
+            wk = self.halo.rev.begin(diag)
+            yield "reverse"
+            self.halo.rev.end(diag, wk)
+        n = self.nlocal
+        rates[:n] -= diag[:n].to(torch.float64) / self._energy_mass()[:n].to(torch.float64)
+        sigma2 = 0.0
+        if self._sponge_term is not None:
+            idx, sigma = self._sponge_term.built
+            if len(idx):
+                rates[torch.from_numpy(np.asarray(idx, dtype=np.int64)).to(self.dev)] += torch.from_numpy(2.0 * np.asarray(sigma)).to(self.dev)
+                sigma2 = float(np.max(np.asarray(sigma) ** 2))
+        return sigma2
+
+    def _diffusive_ratio(self):
+        """The largest ``delta / c^2`` of this rank's medium (0: no diffusivity term in the equation)."""
+        return 0.0
+
+    def stable_time_step_schedule(self, safety=0.8, reduce=None, rtol=0.01, min_iterations=16, max_iterations=200):
+        """Generator form of ``stable_time_step`` (yields where ``HaloApply`` yields, and after depositing partial sums in
+        ``reduce``, an ``InProcessGather`` the ranks of one process share)."""
+        from .reductions import Reducer
+        from .stability import rk4_stable_step
+
+        n, f64, red = self.nlocal, torch.float64, Reducer(self.dev)
+        gen = torch.Generator().manual_seed(1234 + (self.comm.rank if self.halo is not None else 0))
+        m = self._energy_mass()[:n].to(f64)
+        x, y = (torch.zeros(self.ndofs, dtype=self.tdt, device=self.dev) for _ in range(2))
+        v = (torch.rand(n, generator=gen, dtype=f64) - 0.5).to(self.dev)
+        every = yield from self._gather(red.terms(sum0=(v, v, m)).tolist()[:1], reduce, 0)
+        seq, vv = 1, float(every.sum())
+        v, v_prev, beta = v / np.sqrt(vv), torch.zeros_like(v), 0.0
+        alphas, betas, lam_prev, lam = [], [], None, None
+        for it in range(max_iterations):
+            x[:n] = v.to(self.tdt)
+            y.zero_()
+            yield from self._stiffness_of(x, y)  # y = -K x, complete over the owned dofs
+            w = -y[:n].to(f64) / m - beta * v_prev  # minv K v - beta v_prev
+            every = yield from self._gather(red.terms(sum0=(w, v, m)).tolist()[:1], reduce, seq)
+            alpha = float(every.sum())
+            w -= alpha * v
+            every = yield from self._gather(red.terms(sum0=(w, w, m)).tolist()[:1], reduce, seq + 1)
+            seq, beta = seq + 2, float(np.sqrt(every.sum()))
+            alphas.append(alpha)
+            lam = float(np.linalg.eigvalsh(np.diag(alphas) + np.diag(betas, 1) + np.diag(betas, -1))[-1])
+            if lam_prev is not None and it + 1 >= min_iterations and abs(lam - lam_prev) <= rtol * lam:
+                break
+            if not beta > 1e-14 * abs(lam):  # the Krylov space is exhausted: lam is exact
+                break
+            lam_prev = lam
+            betas.append(beta)
+            v_prev, v = v, w / beta
+        else:
+            raise _lib.FusGpuError(f"stable_time_step: the iteration did not settle to {rtol:g} in {max_iterations} applies")
+        rates = torch.zeros(self.ndofs, dtype=f64, device=self.dev)
+        sigma2 = yield from self._damping_rates(rates)
+        dmax, bad = red.absmax(rates, n=n)
+        if bad:
+            raise _lib.FusGpuError(f"stable_time_step: {bad} damping rate(s) are not finite (a zero of the lumped mass?)")
+        every = yield from self._gather([dmax, sigma2, self._diffusive_ratio()], reduce, seq)
+        self.lambda_max = lam
+        self.damping_max = float(every[:, 0].max()) + float(every[:, 2].max()) * lam
+        self.stable_limit = rk4_stable_step(lam + float(every[:, 1].max()), self.damping_max)
+        self._warned_step = False
+        return safety * self.stable_limit
+
+    def stable_time_step(self, safety=0.8):
+        """``safety`` times the explicit RK4 step this mesh and medium admit, from the solver's own operators:
+
+        ``lambda_max``    the largest Ritz value of the Lanczos recurrence for ``M^-1 K(1/rho)`` in the ``M`` inner product (``M``: the
+                          lumped mass the stage divides by), its applies the solver's stiffness with its exchanges, its dot products
+                          ``Reducer.terms`` on fp64 vectors; at least 16 applies, then until two successive values agree to 1 %.  Every
+                          estimate is a lower bound of the eigenvalue.
+        ``damping_max``   the largest diagonal damping rate over the owned dofs of every rank: the absorbing facets'
+                          ``M_f2(1/(rho c)) 1 / M``, ``2 sigma`` of a sponge layer and, for Westervelt, ``max(delta / c^2) lambda_max``,
+                          which bounds ``lambda_max(M^-1 K(delta / (rho c^2)))`` because the cell matrices are positive semi-definite.
+        the limit         ``stability.rk4_stable_step(lambda_max + max sigma^2, damping_max)``: the largest ``dt`` for which the roots
+                          of ``mu^2 + d mu + lambda = 0`` stay inside RK4's stability region for every stiffness and damping rate up
+                          to the two bounds -- ``2 sqrt 2 / sqrt(lambda_max)`` without damping, ``2.785 / damping_max`` without
+                          stiffness.  In between it is a model problem, not a proof: stiffness and damping do not commute, and the two
+                          maxima belong to different dofs in general.
+
+        ``lambda_max``, ``damping_max`` and the unscaled limit ``stable_limit`` stay on the solver; ``rk4`` with a longer ``dt`` warns
+        once.  The nonlinear term of Westervelt, relaxation mechanisms and the source are not part of the bound.  On a partitioned mesh
+        every rank calls this (``scatterer.gather_floats`` joins the sums); ranks driven from one process drive
+        ``stable_time_step_schedule(safety, reduce=InProcessGather(nranks))`` in lock step."""
+        dt = run_schedule(self.stable_time_step_schedule(safety))
+        self.check_halo_health(f"{type(self).__name__}.stable_time_step")
+        return dt
 
     # -- the solution on the host ------------------------------------------------------------------------------------------
     def u_sol(self, with_ghosts=False):

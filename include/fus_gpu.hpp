@@ -32,6 +32,7 @@
 #include "fus_gpu_relaxation.h"
 #include "fus_gpu_nodal.h"
 #include "fus_gpu_westervelt_nodal.h"
+#include "fus_gpu_reduce.h"
 
 namespace fus_gpu {
 
