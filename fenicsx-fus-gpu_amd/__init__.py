@@ -23,6 +23,7 @@ sources     SourceArray (phased-array facet sources), PointSources (monopoles in
 receivers   ElementReceivers (what each array element receives), time_reversal
 reductions  Reducer: sums of products, max |x| and the non-finite count of device vectors (csrc/reduce.hpp)
 diagnostics EnergyRecorder, FieldGuard (rk4(..., energy=, guard=)); the solvers' stable_time_step() uses stability.py
+shock_capture ShockCapture: a per-cell modal sensor adds artificial diffusivity where a Westervelt wave steepens (csrc/modal_sensor.hpp)
 _lib        ctypes binding of csrc/libfusgpu.so (fails loudly if missing)
 """
 

@@ -29,6 +29,7 @@ ADDITION_HEADER_PATHS = (os.path.join(os.path.dirname(_HERE), "include", "fus_gp
 LATER_HEADER_PATHS = (os.path.join(os.path.dirname(_HERE), "include", "fus_gpu_nodal.h"),
                       os.path.join(os.path.dirname(_HERE), "include", "fus_gpu_westervelt_nodal.h"),
                       os.path.join(os.path.dirname(_HERE), "include", "fus_gpu_reduce.h"),
+                      os.path.join(os.path.dirname(_HERE), "include", "fus_gpu_sensor.h"),
                       os.path.join(os.path.dirname(_HERE), "include", "fus_gpu_waveform.h"))  # (tests/test_waveform_sources.py: the last)
 
 

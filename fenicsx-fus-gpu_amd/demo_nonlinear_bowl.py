@@ -15,6 +15,7 @@ cells (G varies per quadrature point; P1 geometry, cuda/demo_nonlinear_bowl.py:3
     python fenicsx-fus-gpu_amd/demo_nonlinear_bowl.py --field-stats maps.npz     # last-period maps of every dof, accumulated on the device
     python fenicsx-fus-gpu_amd/demo_nonlinear_bowl.py --intensity                # the focus of the intensity |I| and the peak radiation force density |F|
     python fenicsx-fus-gpu_amd/demo_nonlinear_bowl.py --nodal-lens               # c, rho, beta and alpha given at the dofs: a smooth inclusion
+    python fenicsx-fus-gpu_amd/demo_nonlinear_bowl.py --shock-capture            # a per-cell sensor adds diffusivity where the wave steepens
     python fenicsx-fus-gpu_amd/demo_nonlinear_bowl.py --thermal 10 20            # then heat for 10 s and cool for 20 s with the last period's q (bioheat.py)
     python -m torch.distributed.run --nproc-per-node 8 fenicsx-fus-gpu_amd/demo_nonlinear_bowl.py
 
@@ -92,7 +93,14 @@ def main():
                          "t = 0, zero after the last; sources.SampledWaveform) instead of the analytic waveform: the whole bowl (R = 1) or, "
                          "with --array, its elements (R = 1 or one row per element, on top of the focusing delays).  The interpolant's "
                          "derivative is the dg/dt of the Westervelt source term")
+    ap.add_argument("--shock-capture", nargs="?", type=float, const=-1.0, default=None, metavar="STRENGTH",
+                    help="shock capturing (shock_capture.ShockCapture): after every step a per-cell smoothness sensor adds up to "
+                         "STRENGTH c h / P^2 of artificial diffusivity to the cells where the wave steepens (default strength: the "
+                         "attachment's); prints the number of active cells and the largest diffusivity at the end.  Composes with "
+                         "--stable-dt (the bound then covers the largest diffusivity), --guard and --sponge; not with --nodal-lens")
     a = ap.parse_args()
+    if a.shock_capture is not None and a.nodal_lens:
+        ap.error("--shock-capture: shock capturing for nodal media is out of scope (not with --nodal-lens)")
     if a.nodal_lens and (a.power_law or a.geometry == "array"):
         ap.error("--nodal-lens: the nodal cell pass forms G in the kernel (not --geometry array), and --power-law fits its own attenuation")
     if a.thermal is not None and (len(a.thermal) > 2 or min(a.thermal) < 0.0):
@@ -214,9 +222,13 @@ def main():
             print(f"Power law {a.power_law[0]:g} dB/cm/MHz^{a.power_law[1]:g}: tau = {fit.tau}, kappa = {fit.kappa}, delta = {fit.delta:.4g} "
                   f"(thermoviscous part {attenuation_coefficient_dB:.4g} dB/m at f0), largest relative error of the fit {fit.max_rel_error:.4f}",
                   flush=True)
+    capture = None
+    if a.shock_capture is not None:
+        sc = fusgpu_loader.submodule("shock_capture")
+        capture = sc.ShockCapture() if a.shock_capture < 0.0 else sc.ShockCapture(strength=a.shock_capture)
     solver = nls.WesterveltSpectral3D(mesh, float_type, speed_of_sound, density, source_frequency, source_amplitude,
                                       nonlinear_coefficient, attenuation_coefficient_dB, comm=comm, fused=not a.reference_sequence, source=source,
-                                      sponge=sponge, relaxation=relaxation, nodal_medium=medium,
+                                      sponge=sponge, relaxation=relaxation, nodal_medium=medium, shock_capture=capture,
                                       in_kernel_geometry=True if (a.in_kernel_geometry or a.geometry == "kernel") else ("auto" if a.geometry == "auto" else False))
     solver.init()
     if medium is not None and rank == 0:
@@ -251,6 +263,11 @@ def main():
         solver.rk4 = functools.partial(solver.rk4, energy=energy, guard=diag.FieldGuard(every=a.guard) if a.guard else None)
 
     def report_energy():
+        if capture is not None:  # (every run path ends here)
+            eps = capture.artificial_diffusivity()
+            print(f"Shock capture (rank {rank}): {capture.active_cells()} of {mesh.ncells} cells active after {capture.launches} sensor "
+                  f"launches, largest artificial diffusivity {eps.max() if eps.size else 0.0:.4e} m^2/s (at most "
+                  f"{capture.eps_max.max():.4e}; physical {solver.delta:.4e})", flush=True)
         if energy is None:
             return
         te, kin, pot, tot, amax, bad = energy.energies()

@@ -38,7 +38,7 @@ class WesterveltSpectral3D(SpectralSolver3D):
                  attenuation_coefficient_dB=0.2, comm=None, source_time="tn", overlap=True, fused=False,
                  in_kernel_geometry="auto", uniform_ratio="auto", halo_plan=None, defer_setup_exchange=False,
                  reference_speed_of_sound=None, reference_density=None, keep_G=False, source=None, sponge=None,
-                 point_source=None, point_claim=None, relaxation=None, nodal_medium=None, nodal_cell_pass="auto"):
+                 point_source=None, point_claim=None, relaxation=None, nodal_medium=None, nodal_cell_pass="auto", shock_capture=None):
         """``speed_of_sound``, ``density``, ``nonlinear_coefficient``, ``attenuation_coefficient_dB``: scalars, or one value per
         cell in the caller's cell order (the DG0 material arrays of cuda/demo_nonlinear_bowl.py:166-178 -- water / skull / ...).
         ``reference_speed_of_sound`` / ``reference_density``: the scalars of the source term and of the default source amplitude
@@ -68,7 +68,20 @@ class WesterveltSpectral3D(SpectralSolver3D):
         ``c_cells`` / ``rho_cells`` / ``delta_cells`` the per-cell means, ``c0`` / ``rho0`` default to the means over the source facets'
         dofs.  ``fused=False`` runs two launches of the nodal stiffness operator and pointwise products with ``w2`` / ``w5`` (no
         reverse scatter of m).  ``nodal_cell_pass``: ``"fused"`` (the one-pass kernel), ``"two-launch"`` (the fused stage takes the
-        two launches of the nodal stiffness operator instead) or ``"auto"``: ``NODAL_CELL_PASS_DEFAULT``."""
+        two launches of the nodal stiffness operator instead) or ``"auto"``: ``NODAL_CELL_PASS_DEFAULT``.
+        ``shock_capture``: a ``shock_capture.ShockCapture`` -- after a step (every ``every``-th) one sensor launch on the new field adds
+        artificial diffusivity to ``delta`` of the cells where the wave steepens, by rewriting ``self.cc4`` in place (``cc4_base`` keeps
+        the physical constants); the cell pass and the reference launch sequence read ``self.cc4`` as before, the facet coefficients
+        keep the physical ``delta``, and ``stable_time_step`` counts the largest diffusivity a cell can get.  On a partitioned mesh a
+        due launch posts one forward exchange of the field first.  ``uniform_ratio=True`` (the single-gather form needs ONE ratio
+        delta / c^2) and ``nodal_medium=`` (there ``cc4`` is a unit multiplier of a nodal coefficient: out of scope) raise
+        ``ValueError``.  ``None`` leaves every launch as it is."""
+        if shock_capture is not None and uniform_ratio is True:
+            raise ValueError("shock_capture= with uniform_ratio=True: the single-gather form needs one ratio delta / c^2 for the whole "
+                             "medium, the artificial diffusivity differs from cell to cell")
+        if shock_capture is not None and nodal_medium is not None:
+            raise ValueError("shock_capture= with nodal_medium=: the nodal cell pass takes delta / (rho c^2) at the dofs and cc4 is a "
+                             "unit multiplier there; shock capturing for nodal media is out of scope (DESIGN 7)")
         self.nodal_medium = nodal_medium
         if nodal_medium is not None:
             given = {"speed_of_sound": speed_of_sound, "density": density, "nonlinear_coefficient": nonlinear_coefficient,
@@ -256,6 +269,15 @@ class WesterveltSpectral3D(SpectralSolver3D):
             self._cell_pass = lambda u_n, v_n, c3, c4, G_, dm_: stiff(self.w, c3, self.b, G_, dm_)
         else:
             self._cell_pass = lambda u_n, v_n, c3, c4, G_, dm_: pair.stiffness_only(u_n, v_n, c3, c4, self.b, G_, dm_)
+        # the attachment writes self.cc4 -- the array object _percell and the reference launch sequence hold -- from this copy
+        self.shock_capture = shock_capture
+        if shock_capture is not None:
+            self.cc4_base = shock_capture.bind(self)._base
+
+    def init(self):
+        super().init()
+        if self.shock_capture is not None:
+            self.shock_capture.reset()
 
     def setup_schedule(self):
         yield from self._reverse_setup((self.m0, self.w2, self.w5))
@@ -306,6 +328,8 @@ class WesterveltSpectral3D(SpectralSolver3D):
     def _diffusive_ratio(self):
         if self.nodal_medium is not None:
             return float(np.max(self.delta_nodal / self.c_nodal**2))
+        if self.shock_capture is not None:  # the worst case: every cell at its largest artificial diffusivity
+            return float(np.max((self.delta_cells + self.shock_capture.eps_max) / self.c_cells**2))
         return float(np.max(self.delta_cells / self.c_cells**2))
 
     def _vector_pass(self, bw, aw, new_step):

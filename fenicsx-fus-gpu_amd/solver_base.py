@@ -425,31 +425,37 @@ class SpectralSolver3D(MeshSolver3D):
         forward exchange the sensors and the receivers read after is posted first -- once, if either is due -- with a ``yield`` after
         posting (the solvers' schedules post their stage exchanges the same way, so in-process lockstep drivers keep working); the
         monitor reads owned dofs only.  ``energy`` applies the stiffness to the field through the halo schedule (its own exchanges and
-        yields); ``guard`` is asked after EVERY step, whatever ``record_from``."""
+        yields); ``guard`` is asked after EVERY step, whatever ``record_from``.  A Westervelt solver's ``shock_capture`` attachment
+        (shock_capture.py) launches its sensor last, after every step it is due, and shares the forward exchange."""
         self._warn_step(dt)
         for recorder in (sensors, monitor, receivers, energy, guard):
             if recorder is not None:
                 recorder.expect_steps(start_time, final_time, dt, max_steps, record_from)
         rf = -np.inf if record_from is None else float(record_from)
+        shock = getattr(self, "shock_capture", None)
 
         def record(t):
             u, v = (self.u0, self.v0) if self.fused else (self.u, self.v)
             if guard is not None:
                 guard.check(self, u, t)
-            if not t > rf:
+            sense = shock is not None and shock.due()  # after EVERY step, whatever record_from
+            if not t > rf and not sense:
                 return
-            due = [r for r in (sensors, receivers) if r is not None and not r.full]
-            if due:
+            due = [r for r in (sensors, receivers) if r is not None and not r.full] if t > rf else []
+            if due or sense:  # one exchange serves the recorders and the sensor launch
                 if self.halo is not None:
                     wk = self.halo.fwd.begin(u)
                     yield "forward"
                     self.halo.fwd.end(u, wk)
                 for r in due:
                     r.record(u, t)
-            if monitor is not None:
-                monitor.record(u, v, t)
-            if energy is not None:
-                yield from energy.record_schedule(u, v, t)
+            if t > rf:
+                if monitor is not None:
+                    monitor.record(u, v, t)
+                if energy is not None:
+                    yield from energy.record_schedule(u, v, t)
+            if sense:  # after the recorders: they see the step as it was computed, cc4 changes for the steps that follow
+                shock.launch(u)
 
         return record
 

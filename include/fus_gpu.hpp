@@ -33,6 +33,7 @@
 #include "fus_gpu_nodal.h"
 #include "fus_gpu_westervelt_nodal.h"
 #include "fus_gpu_reduce.h"
+#include "fus_gpu_sensor.h"
 
 namespace fus_gpu {
 

@@ -26,7 +26,7 @@ def compile_tree(root):
     csrc = os.path.join(root, "fenicsx-fus-gpu_amd", "csrc")
     out = os.path.join(csrc, "_asm", "compare")
     os.makedirs(out, exist_ok=True)
-    srcs = [os.path.join(csrc, f) for f in os.listdir(csrc) if f.endswith((".hip", ".hpp"))] + [p for p in (os.path.join(root, "include", h) for h in ("fus_gpu.h", "fus_gpu_array.h", "fus_gpu_relaxation.h", "fus_gpu_nodal.h", "fus_gpu_westervelt_nodal.h", "fus_gpu_waveform.h", "fus_gpu_reduce.h")) if os.path.exists(p)]
+    srcs = [os.path.join(csrc, f) for f in os.listdir(csrc) if f.endswith((".hip", ".hpp"))] + [p for p in (os.path.join(root, "include", h) for h in ("fus_gpu.h", "fus_gpu_array.h", "fus_gpu_relaxation.h", "fus_gpu_nodal.h", "fus_gpu_westervelt_nodal.h", "fus_gpu_waveform.h", "fus_gpu_reduce.h", "fus_gpu_sensor.h")) if os.path.exists(p)]
     newest = max(os.path.getmtime(p) for p in srcs)
     procs, files = [], []
     for src, defs in ru.UNITS:

@@ -71,7 +71,7 @@ def cached_remarks():
     """Remarks of the current sources, cached under csrc/_asm keyed on source mtimes."""
     cache = os.path.join(CSRC, "_asm", "resource_usage_device.txt")
     srcs = [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith((".hip", ".hpp"))]
-    srcs += [os.path.join(ROOT, "include", h) for h in ("fus_gpu.h", "fus_gpu_array.h", "fus_gpu_relaxation.h", "fus_gpu_nodal.h", "fus_gpu_westervelt_nodal.h", "fus_gpu_waveform.h", "fus_gpu_reduce.h")]
+    srcs += [os.path.join(ROOT, "include", h) for h in ("fus_gpu.h", "fus_gpu_array.h", "fus_gpu_relaxation.h", "fus_gpu_nodal.h", "fus_gpu_westervelt_nodal.h", "fus_gpu_waveform.h", "fus_gpu_reduce.h", "fus_gpu_sensor.h")]
     newest = max(os.path.getmtime(p) for p in srcs)
     if os.path.exists(cache) and os.path.getmtime(cache) >= newest:
         return open(cache).read()
