@@ -1,5 +1,5 @@
 """include/fus_gpu.hpp through the compiler (no GPU, no library): tests/host/fus_gpu_hpp_check.cpp instantiates every functor class for
-double and float (and P = 1, 4, 10), so every typed forward is checked against its prototype in include/fus_gpu.h.  hipcc, host pass only."""
+double and float (and P = 1 ... 10), so every typed forward is checked against its prototype in include/fus_gpu.h.  hipcc, host pass only."""
 
 import os
 import shutil
